@@ -17,7 +17,9 @@ all-gather) followed by the planner sweep (BASELINE.json config 4).  With `--joi
 and on an even number of ranks PAIRS of ranks share its knot elimination (rbp_session_shard_joint; swarm_simulator_amd/sharded.py) --
 `--gpus 2 --backend gloo` runs that pair on a one-GPU box as a correctness line (both ranks on the one device: its time means nothing).
 
-Prints ONE JSON line (rank 0).
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0).  `--full` adds the legs beside the headline
+figure: the single-mission latency, the one-sweep rate, the in-kernel phase rate of the row sweeps (roofline.sweep_phase_gbs), the
+joint-QP leg and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import hashlib
@@ -93,6 +95,38 @@ def build_inputs(map_ids, n_agents, param):
         worlds.append(w)
         plans.append(pr.clone_inputs())   # every map keeps its own M = makespan + 2: a ragged session, nothing is padded
     return m, worlds, plans
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_MISSIONS, DUMP_SAMPLE_SEED = 16, 0
+
+
+def dump_outputs(dirname, plans, status):
+    """--dump-outputs: what the timed path handed its caller after the last step (Session.download into the PlanResult objects), as
+    DIR/<name>.npy in float32 / float64.  The per-mission scalars of EVERY mission: status, total_cost, time_scale, sfc_count [K][N].
+    The arrays of a fixed, seeded sample of missions (every map keeps its own M, so each sampled mission k has files of its own,
+    <name>_k<k>.npy): sfc_box, sfc_time, rsfc_normal, rsfc_time, coef, ctrl; sample_missions.npy lists k.  At most 64 MiB in all."""
+    os.makedirs(dirname, exist_ok=True)
+    K = len(plans)
+    out = {"status": np.asarray(status, np.float64), "total_cost": np.array([p.total_cost for p in plans], np.float64),
+           "time_scale": np.array([p.time_scale for p in plans], np.float64),
+           "sfc_count": np.stack([p.sfc_count for p in plans]).astype(np.float64)}
+    total = sum(a.nbytes for a in out.values())
+    sample = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(K, min(K, DUMP_SAMPLE_MISSIONS), replace=False))
+    taken = []
+    for k in sample:
+        p = plans[k]
+        arrs = {f"{name}_k{k:04d}": getattr(p, name) for name in ("sfc_box", "sfc_time", "rsfc_normal", "rsfc_time", "coef", "ctrl")}
+        size = sum(a.nbytes for a in arrs.values())
+        if total + size + 8 * (len(taken) + 1) > DUMP_LIMIT_BYTES:
+            break
+        out.update(arrs)
+        taken.append(k)
+        total += size
+    out["sample_missions"] = np.array(taken, np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(out)
 
 
 # ---- CPU baseline: the oracle (a port: CPLEX is proprietary and absent), timed on this box's host cores -------------------------
@@ -368,8 +402,13 @@ def main():
     ap.add_argument("--qp-far-slack", type=float, default=None, help="rbp_solver_opts.qp_far_slack [m] (A/B runs; default: the library's 0.7)")
     ap.add_argument("--joint-schedule", type=int, default=0, help="rbp_solver_opts.joint_schedule (A/B runs: 2 = bulk, 3 = bulk with two pivot tiles per pass)")
     ap.add_argument("--plain-order", action="store_true", help="rbp_solver_opts.qp_block_order = 0 (A/B runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true", help="skip the single-mission latency leg (profiling runs: keeps the kernel list clean)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline (default config, one rank): single-mission latency, one-sweep rate, "
+                         "sweep_phase_gbs (a run of the profiling build), the joint-QP leg, and the CPU baseline (any config, one rank)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the latency, one-sweep, sweep-phase and joint legs (profiling runs: keeps the kernel list clean)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32/float64, <= 64 MiB; dump_outputs)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for the CPU test of the launcher)")
     ap.add_argument("--dry-run", action="store_true", help="launcher test: initialise the ranks, print the JSON skeleton, plan nothing")
     ap.add_argument("--native-pair", action="store_true",
@@ -426,6 +465,8 @@ def main():
     pkw = dict(batch_size=args.batch_size, iteration=args.iteration, sequential=not args.joint)
     param = Param.test_sweep(**pkw)
     if args.config == "c4" and args.native_pair and args.joint:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the --native-pair solve runs in lib/rbp_c4_joint_rank, whose outputs do not reach this process")
         return bench_c4_native(args, rank, n_ranks, local_rank, dist)
     if args.config == "c4":
         return bench_c4(args, param, pkw, rank, n_ranks, local_rank, dist)
@@ -483,6 +524,8 @@ def main():
     ct = sess.counters(stream)  # of the last step
     status = sess.download(stream)
     unpolished = int(sum(p.qp_unpolished for p in plans))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, plans, status)
 
     if rank == 0:
         value = n_total / secs
@@ -578,7 +621,7 @@ def main():
             except Exception:
                 pass
         # the single-mission latency and the CPU baseline are rank-0, N = 1 legs (the other ranks would only wait for them)
-        if world_size == 1 and N == 64 and args.batch_size == 4 and args.iteration == 1 and not args.joint and not args.no_latency:
+        if args.full and world_size == 1 and N == 64 and args.batch_size == 4 and args.iteration == 1 and not args.joint and not args.no_latency:
             try:
                 out["latency_ms_single_mission"] = single_mission_latency(mission, param, worlds[0], plans[0])
             except Exception as e:
@@ -606,7 +649,7 @@ def main():
                 out["roofline_joint"] = {"error": str(e)}
             out["single_mission_two_calls_ms"] = lat.get("two_calls_ms") if isinstance(lat, dict) else None
             out["single_sweep_value"] = ss.get("value") if isinstance(ss, dict) else None
-        if world_size == 1 and not args.no_cpu_baseline:
+        if args.full and world_size == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.agents, pkw)
             except Exception as e:  # the oracle is optional equipment of the bench
@@ -731,6 +774,8 @@ def bench_c4(args, param, pkw, rank, n_ranks, local_rank, dist):
     if dist is not None:
         dist.barrier()
     secs = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [pr], [0 if ok else 1])
     if dist is not None:
         t = torch.tensor([secs], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -10,9 +10,9 @@ run python bench.py --config c2 --no-cpu-baseline
 run python bench.py --config c5 --no-cpu-baseline
 run python bench.py --config c4 --no-cpu-baseline
 run python bench.py --agents 16 --joint --missions-per-gpu 250 --steps 2 --no-cpu-baseline
-run python bench.py --missions-per-gpu 50 --no-cpu-baseline
-run python bench.py --missions-per-gpu 250 --no-cpu-baseline
-run python bench.py --missions-per-gpu 500 --no-cpu-baseline
+run python bench.py --missions-per-gpu 50 --full --no-cpu-baseline
+run python bench.py --missions-per-gpu 250 --full --no-cpu-baseline
+run python bench.py --missions-per-gpu 500 --full --no-cpu-baseline
 run python bench.py --config c4 --joint --no-cpu-baseline
 run python bench.py --agents 64 --joint --missions-per-gpu 50 --steps 2 --no-cpu-baseline
 cat $L

@@ -5,7 +5,7 @@ set -u
 TAG=${1:-r01}; K=${2:-1000}
 OUT=$PWD/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py --missions-per-gpu $K > $OUT/bench.log 2>&1
+python bench.py --full --missions-per-gpu $K > $OUT/bench.log 2>&1
 python -m pytest tests -m gpu -q > $OUT/gpu_tests.log 2>&1
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python $GRAFT_REPO_ROOT/bench.py --missions-per-gpu $K --no-cpu-baseline --no-latency > $OUT/kt.log 2>&1

@@ -27,7 +27,7 @@ PY
 }
 for part in "$@"; do case $part in
 bench)
-  python bench.py > $OUT/bench.log 2>&1
+  python bench.py --full > $OUT/bench.log 2>&1
   B="python $R/bench.py --no-cpu-baseline --no-latency"
   cd /tmp
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- $B > $OUT/kt.log 2>&1

@@ -13,7 +13,7 @@ port=29511
 for N in 1 2 4 8; do
   [ "$N" -gt "$NGPU" ] && { echo "skip N=$N (only $NGPU GPU(s))"; continue; }
   if [ "$N" -eq 1 ]; then
-    python bench.py --gpus 1 --steps $STEPS --warmup $WARM | tail -1 >> $OUT
+    python bench.py --gpus 1 --steps $STEPS --warmup $WARM --full | tail -1 >> $OUT
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((port++)) bench.py --gpus $N --steps $STEPS --warmup $WARM --no-cpu-baseline | tail -1 >> $OUT
   fi
