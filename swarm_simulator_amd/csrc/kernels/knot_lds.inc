@@ -13,7 +13,15 @@
 //   U  [NK][KL_LDU]  the rank-NK update X D^-1 X' of the next block, MFMA tiles written in the C/D layout; overlays C
 // With M explicit, the coupling factor costs 3 multiply-adds per entry (the coupling block T_{j+1,j} is 3x3-block diagonal) and the
 // substitutions become matrix-vector products instead of 36-step dependent chains.
+//
+// The column loop (kl_ldl, kl_follow_LinvT) pays one ds_read_b128 broadcast per two multiply-adds: 23 cycles per pair against 9 for the
+// arithmetic, ~275 cycles per column, and the broadcasts queue in the LDS that a co-resident workgroup shares.  Blocks of
+// NK >= KL_PANEL_MIN_NK columns (the 36 x 36 blocks of the flagship missions) take the PANEL path in the second half of this file
+// instead: S and the running inverse live in the accumulators of v_mfma_f64_16x16x4_f64, a step eliminates 4 columns, C holds one
+// small image per panel in place of the column images (knot_panel_layout.h), and I, MX, U and the progress words keep their meaning.
+// tools/ubench/knot.hip times both paths (-DKL_PANEL=0/1) in the product's arrangement; profiles/knot_panel_ubench.txt has the figures.
 #pragma once
+#include "knot_panel_layout.h"
 
 #define KL_LD 38   // doubles per row: 16-byte aligned rows, and rows 0..15 of a ds_read_b128 land on distinct banks (38 * 2 = 76 = 12 mod 64)
 #define KL_LDU 50
@@ -283,4 +291,323 @@ __device__ __forceinline__ void kl_syrk(const kl_lds* MX, const kl_lds* I, kl_ld
             }
     }
     kl_sync();
+}
+
+// ---- panel-blocked formulation: 4 columns per step, trailing updates on v_mfma_f64_16x16x4_f64 (index maps: knot_panel_layout.h) -------
+// The column loop above is bound by the LDS broadcasts of one wave (one ds_read_b128 per two multiply-adds, 23 cycles per pair against
+// 9 for the arithmetic).  Here the Schur complement S lives in the accumulators of the MFMA instruction (upper 16 x 16 tiles of the
+// block padded with a unit diagonal), and a step eliminates a PANEL of 4 columns:
+//   (i)   the 4 panel rows of S go to an LDS image -- every lane owns exactly one entry per tile, one ds_write_b64 per tile;
+//   (ii)  every lane reads the 4 x 4 diagonal block (broadcast) and factorises it redundantly in registers: 4 reciprocals per panel and
+//         no cross-lane exchange inside a panel; the same L, D and 1 / d as the scalar recursion, in another order of roundings;
+//   (iii) every lane eliminates the rows it serves as an MFMA operand (16 t + (lane & 15), t = the live tile rows) against that block
+//         and keeps the entry of column lane >> 4: L is the A operand, L d the B operand of the rank-4 update of the live tiles, at
+//         most 6 MFMAs per panel and 31 per block for NK = 36.  The tile row of the NEXT panel is updated first and that panel's
+//         image leaves, its loads are issued, before the remaining tiles are updated.
+//   (iv)  L of the panel replaces S in the image (the A operands just formed: one ds_write_b64 per tile), and the image is announced.
+// The following wave computes N = L^-1 on the same panels: it reads the image of panel p (the rows of L it serves and the unit lower
+// diagonal block L_pp), forms G = -L_p (L_pp)^-1 and applies N <- N + G N[panel rows] -- rank 4, the B operand being registers of
+// its own lower tiles (see knot_panel_layout.h); it needs no reciprocal and no factorisation of its own.  M = L^-T is N transposed; it leaves the tiles for MX row by row.
+// Every lane only ever writes inside the panel images, the (padded) rows of MX and I: there is no lane >= NK to keep out.
+// Part of what is written there is UNDEFINED: in the panel's own tile row the lanes that serve rows above the panel (already eliminated)
+// and the panel's own rows right of the diagonal run the row elimination on stale accumulator contents, and that junk -- possibly Inf or
+// NaN after a failed pivot -- goes into the image as "L" and into the MFMA operands.  It only reaches finished rows and columns of the
+// tiles (an entry of D depends on its own row of A and column of B), and the following wave never uses those image entries: it reads
+// the strict lower part of the diagonal block, and masks the rows at and above the panel BITWISE (kl_pick; 0 * NaN would not do).
+// Keep kl_pick a bit operation, and do not start reading those rows.
+// Progress word: *P = pbase + p + 1 once the images 0 .. p hold L (p < NP <= NK), pbase + NK + 1 once every 1 / d is in I --
+// every count is published whatever the pivots are.
+#ifndef KL_PANEL
+#define KL_PANEL 1
+#endif
+#ifndef KL_PANEL_MIN_NK
+#define KL_PANEL_MIN_NK 36  // smaller blocks keep the column loop: NK = 9 loses on panels, 18 and 27 gain in tools/ubench/knot.hip but have not been through the product's A/B
+#endif
+__host__ __device__ constexpr bool kl_panel_path(int nk) { return KL_PANEL && nk >= KL_PANEL_MIN_NK; }
+
+template <int NK>
+struct KlPanels {
+    static constexpr int NT = kp_nt(NK), NP = kp_np(NK), TILES = kp_ntiles(NT);
+    static_assert(kp_img_total(NK) <= KlArea<NK>::CSZ, "the panel images must fit the C / U region");
+};
+
+__device__ __forceinline__ double kl_recip(double d) {  // rcp + one Newton step (2e-15), as in kl_ldl
+    const double inv = __builtin_amdgcn_rcp(d);
+    return __builtin_fma(__builtin_fma(-d, inv, 1.0), inv, inv);
+}
+// c ? a : b on the bits: a ?: on doubles that are computed nearby comes out as divergent branches (the compiler sinks the arithmetic into
+// them), which split the unrolled panel loop into basic blocks -- measured at twice the time of a panel step
+__device__ __forceinline__ double kl_pick(bool c, double a, double b) {
+    const long long m = -(long long)c;
+    return __longlong_as_double((__double_as_longlong(a) & m) | (__double_as_longlong(b) & ~m));
+}
+__device__ __forceinline__ double kl_sel4(const double (&v)[4], int k) {
+    return kl_pick((k & 2) != 0, kl_pick((k & 1) != 0, v[3], v[2]), kl_pick((k & 1) != 0, v[1], v[0]));
+}
+
+// the 4 x 4 diagonal block of a panel: raw entries (lower triangle) as loaded, then its L D L'
+struct KlPivot {
+    double d0, d10, d11, d20, d21, d22, d30, d31, d32, d33;  // raw S[4p + a][4p + k], k <= a
+    double i0, i1, i2, i3;                                    // 1 / d
+    double w10, w20, w21, w30, w31, w32;                      // L d
+    double l10, l20, l21, l30, l31, l32;                      // L
+    bool ok;
+};
+__device__ __forceinline__ void kl_pivot_load(KlPivot& f, const kl_lds* img, int p) {  // wave-uniform addresses: broadcasts
+    const kl_lds* b = img + kp_img_entry(KP_W * p, 0);
+    f.d0 = b[0];
+    const kl_d2 r1 = *(const kl_lds2*)(b + 4), r2 = *(const kl_lds2*)(b + 8), r3 = *(const kl_lds2*)(b + 12), r3b = *(const kl_lds2*)(b + 14);
+    f.d22 = b[10];
+    f.d10 = r1[0], f.d11 = r1[1], f.d20 = r2[0], f.d21 = r2[1], f.d30 = r3[0], f.d31 = r3[1], f.d32 = r3b[0], f.d33 = r3b[1];
+}
+__device__ __forceinline__ void kl_pivot_factor(KlPivot& f) {
+    f.i0 = kl_recip(f.d0);
+    f.w10 = f.d10, f.l10 = f.w10 * f.i0;
+    f.w20 = f.d20, f.l20 = f.w20 * f.i0;
+    f.w30 = f.d30, f.l30 = f.w30 * f.i0;
+    const double d1 = __builtin_fma(-f.l10, f.w10, f.d11);
+    f.i1 = kl_recip(d1);
+    f.w21 = __builtin_fma(-f.l20, f.w10, f.d21), f.l21 = f.w21 * f.i1;
+    f.w31 = __builtin_fma(-f.l30, f.w10, f.d31), f.l31 = f.w31 * f.i1;
+    const double d2 = __builtin_fma(-f.l21, f.w21, __builtin_fma(-f.l20, f.w20, f.d22));
+    f.i2 = kl_recip(d2);
+    f.w32 = __builtin_fma(-f.l31, f.w21, __builtin_fma(-f.l30, f.w20, f.d32)), f.l32 = f.w32 * f.i2;
+    const double d3 = __builtin_fma(-f.l32, f.w32, __builtin_fma(-f.l31, f.w31, __builtin_fma(-f.l30, f.w30, f.d33)));
+    f.i3 = kl_recip(d3);
+    f.ok = f.d0 > 0 && d1 > 0 && d2 > 0 && d3 > 0;
+}
+// one row of the panel against the factorised diagonal block: s (raw) -> W = L d and L
+__device__ __forceinline__ void kl_panel_row(const KlPivot& f, const kl_d2 s01, const kl_d2 s23, double (&L)[4], double (&W)[4]) {
+    W[0] = s01[0], L[0] = W[0] * f.i0;
+    W[1] = __builtin_fma(-L[0], f.w10, s01[1]), L[1] = W[1] * f.i1;
+    W[2] = __builtin_fma(-L[1], f.w21, __builtin_fma(-L[0], f.w20, s23[0])), L[2] = W[2] * f.i2;
+    W[3] = __builtin_fma(-L[2], f.w32, __builtin_fma(-L[1], f.w31, __builtin_fma(-L[0], f.w30, s23[1]))), L[3] = W[3] * f.i3;
+}
+
+// S -> upper tiles: entry(mx, mn) returns the element (mx, mn), mx >= mn, of the symmetric NK x NK source (its lower triangle); rows and
+// columns >= NK are the unit diagonal of the padding.  SUB: subtract from the tiles instead.  BOTH: the source holds both triangles
+// of the diagonal tiles (the LDS images of T_j and U do) -- entry is then called with (column, row) of the tile entry as it stands,
+// which is (mx, mn) above the diagonal and the mirrored, equal element below it: a lane's addresses are one base plus constants,
+// instead of one register per diagonal-tile entry for the lane-dependent choice (the factorisation only consumes entries at and above
+// the diagonal anyway).
+template <int NK, bool SUB, bool BOTH, class F>
+__device__ __forceinline__ void kl_tiles_load(kl_d4 (&s)[KlPanels<NK>::TILES], int lane, F&& entry) {
+    constexpr int NT = KlPanels<NK>::NT;
+    const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int tj = ti; tj < NT; ++tj)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i = KP_T * ti + lk + 4 * g, j = KP_T * tj + li;
+                const int mx = BOTH ? j : i > j ? i : j, mn = BOTH ? i : i > j ? j : i;
+                const bool full = KP_T * tj + KP_T <= NK;  // (compile time: tj >= ti)
+                const bool pad = !full && (i >= NK || j >= NK);
+                const double v = entry(full || mx < NK ? mx : NK - 1, full || mn < NK ? mn : NK - 1);
+                const int tile = kp_upper(ti, tj, NT);
+                if (SUB)
+                    s[tile][g] -= pad ? 0.0 : v;
+                else
+                    s[tile][g] = pad ? (i == j ? 1.0 : 0.0) : v;
+            }
+}
+
+// image of panel p: rows 4p .. 4p+3 of S (= its columns), one entry per lane and tile
+template <int NK>
+__device__ __forceinline__ void kl_panel_out(const kl_d4 (&s)[KlPanels<NK>::TILES], kl_lds* C, int p, int li, int lk) {
+    constexpr int NT = KlPanels<NK>::NT;
+    kl_lds* img = C + kp_img_off(NK, p);
+#pragma unroll
+    for (int tj = 0; tj < NT; ++tj)
+        if (tj >= kp_panel_tile(p)) img[kp_img_entry(KP_T * tj + li, lk)] = s[kp_upper(kp_panel_tile(p), tj, NT)][kp_panel_reg(p)];
+}
+
+// the rows a lane serves (16 t + li, t >= t_first) of panel p from the LDS image
+template <int NK>
+__device__ __forceinline__ void kl_rows_load(kl_d2 (&raw)[KlPanels<NK>::NT][2], const kl_lds* img, int t_first, int li) {
+#pragma unroll
+    for (int t = 0; t < KlPanels<NK>::NT; ++t)
+        if (t >= t_first) raw[t][0] = *(const kl_lds2*)(img + kp_img_entry(KP_T * t + li, 0)), raw[t][1] = *(const kl_lds2*)(img + kp_img_entry(KP_T * t + li, 2));
+}
+
+// S (upper tiles, consumed) = L D L': panel images into C, 1 / d into I, progress through P (see above); returns "every pivot positive"
+template <int NK>
+__device__ __forceinline__ bool kl_ldl_panels(kl_d4 (&s)[KlPanels<NK>::TILES], kl_lds* C, kl_lds* I, int lane, kl_ldsi* P, int pbase) {
+    constexpr int NT = KlPanels<NK>::NT, NP = KlPanels<NK>::NP;
+    const int li = lane & 15, lk = lane >> 4;
+    bool ok = true;
+    KlPivot f;
+    kl_d2 raw[NT][2];
+    kl_panel_out<NK>(s, C, 0, li, lk);
+    kl_sync();
+    kl_pivot_load(f, C, 0);
+    kl_rows_load<NK>(raw, C, 0, li);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int tc = kp_panel_tile(p), t0 = kp_first_live_tile(p);
+        kl_lds* img = C + kp_img_off(NK, p);
+        kl_pivot_factor(f);
+        ok = ok && f.ok;
+        if (KP_W * p + 0 < NK) I[KP_W * p + 0] = f.i0;  // (every lane holds the same values: plain stores, no control flow)
+        if (KP_W * p + 1 < NK) I[KP_W * p + 1] = f.i1;
+        if (KP_W * p + 2 < NK) I[KP_W * p + 2] = f.i2;
+        if (KP_W * p + 3 < NK) I[KP_W * p + 3] = f.i3;
+        const double inv[4] = {f.i0, f.i1, f.i2, f.i3};
+        const double isel = kl_sel4(inv, lk);
+        double a[NT], b[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+            if (t >= tc) {
+                double L[4], W[4];
+                kl_panel_row(f, raw[t][0], raw[t][1], L, W);
+                b[t] = kl_sel4(W, lk);
+                const double l = b[t] * isel;  // (= L[lk], the same product)
+                a[t] = -l;
+                img[kp_img_entry(KP_T * t + li, lk)] = l;  // L replaces S in the image: this wave's reads of the row are served first (in order)
+            }
+        // the tile row of the next panel first; its image and the loads of the next step leave before the other tiles are updated
+        if (p + 1 < NP) {
+#pragma unroll
+            for (int tj = 0; tj < NT; ++tj)
+                if (tj >= t0) s[kp_upper(t0, tj, NT)] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t0], b[tj], s[kp_upper(t0, tj, NT)], 0, 0, 0);
+        }
+        kl_sync();
+        kl_publish(P, pbase + p + 1);
+        if (p + 1 < NP) {
+            kl_panel_out<NK>(s, C, p + 1, li, lk);
+            kl_sync();
+            kl_pivot_load(f, C + kp_img_off(NK, p + 1), p + 1);
+            kl_rows_load<NK>(raw, C + kp_img_off(NK, p + 1), kp_panel_tile(p + 1), li);
+            __builtin_amdgcn_sched_barrier(0);  // (the scheduler would put all MFMAs of the step in front of the image: 3 x 64 cycles of issue more on the chain)
+#pragma unroll
+            for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+                for (int tj = ti; tj < NT; ++tj)
+                    if (ti > t0) s[kp_upper(ti, tj, NT)] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ti], b[tj], s[kp_upper(ti, tj, NT)], 0, 0, 0);
+        }
+    }
+    kl_publish(P, pbase + NK + 1);  // every reciprocal pivot is in I
+    return ok;
+}
+
+// One knot on the panel path, as the callers form it: S = T (- U) into the tiles, then its factorisation.  t_entry(mx, mn) returns
+// T[mx][mn] of the assembled lower triangle (mx >= mn), t_loaded() runs once T's values have been requested (where the caller waits
+// for them and releases their source); U is the rank-NK update that kl_syrk left in the C / U region.
+// T_BOTH: T's source holds both triangles (see kl_tiles_load).
+template <int NK, bool T_BOTH, class TF, class LF>
+__device__ __forceinline__ bool kl_knot_panels(TF&& t_entry, LF&& t_loaded, bool minus_u, kl_lds* C, kl_lds* I, int lane, kl_ldsi* P, int pbase) {
+    kl_d4 s[KlPanels<NK>::TILES];
+    kl_tiles_load<NK, false, T_BOTH>(s, lane, t_entry);
+    t_loaded();
+    if (minus_u) kl_tiles_load<NK, true, true>(s, lane, [&](int mx, int mn) { return (double)C[mx * KL_LDU + mn]; });  // (kl_syrk writes whole diagonal tiles)
+    kl_sync();  // (U is read: the panel images overlay it)
+    return kl_ldl_panels<NK>(s, C, I, lane, P, pbase);
+}
+
+// N = L^-1 (lower tiles) from the panel images, panel by panel behind the chain (WAIT) or after it
+template <int NK, bool WAIT>
+__device__ __forceinline__ void kl_inverse_panels(kl_d4 (&n)[KlPanels<NK>::TILES], const kl_lds* C, int lane, kl_ldsi* P, int pbase) {
+    constexpr int NT = KlPanels<NK>::NT, NP = KlPanels<NK>::NP;
+    const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int tj = 0; tj <= ti; ++tj)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) n[kp_lower(ti, tj)][g] = (ti == tj && lk + 4 * g == li) ? 1.0 : 0.0;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int tc = kp_panel_tile(p), q = kp_panel_reg(p);
+        if (WAIT) kl_await_opaque(P, pbase + p + 1);
+        const kl_lds* img = C + kp_img_off(NK, p);
+        // the unit lower L_pp of the diagonal block (rows 4p + 1 .. 4p + 3 of the image, broadcasts), K = strict lower part of its inverse
+        const kl_lds* bl = img + kp_img_entry(KP_W * p, 0);
+        const double l10 = bl[4], l32 = bl[14];
+        const kl_d2 r2 = *(const kl_lds2*)(bl + 8), r3 = *(const kl_lds2*)(bl + 12);
+        kl_d2 raw[NT][2];
+        kl_rows_load<NK>(raw, img, tc, li);
+        const double l20 = r2[0], l21 = r2[1], l30 = r3[0], l31 = r3[1];
+        const double k10 = -l10, k21 = -l21, k32 = -l32;
+        const double k20 = __builtin_fma(-l21, k10, -l20), k31 = __builtin_fma(-l32, k21, -l31);
+        const double k30 = __builtin_fma(-l32, k20, __builtin_fma(-l31, k10, -l30));
+        double a[NT], b[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+            if (t >= tc) {
+                const double L[4] = {raw[t][0][0], raw[t][0][1], raw[t][1][0], raw[t][1][1]};
+                double G[4];  // row of -L_p (L_pp)^-1
+                G[3] = -L[3];
+                G[2] = -__builtin_fma(L[3], k32, L[2]);
+                G[1] = -__builtin_fma(L[3], k31, __builtin_fma(L[2], k21, L[1]));
+                G[0] = -__builtin_fma(L[3], k30, __builtin_fma(L[2], k20, __builtin_fma(L[1], k10, L[0])));
+                if (t == tc) {  // rows of the panel itself: K; rows above it: nothing
+                    const int ar = KP_T * t + li - KP_W * p;
+                    G[0] = kl_pick(ar >= 4, G[0], kl_pick(ar == 1, k10, kl_pick(ar == 2, k20, kl_pick(ar == 3, k30, 0.0))));
+                    G[1] = kl_pick(ar >= 4, G[1], kl_pick(ar == 2, k21, kl_pick(ar == 3, k31, 0.0)));
+                    G[2] = kl_pick(ar >= 4, G[2], kl_pick(ar == 3, k32, 0.0));
+                    G[3] = kl_pick(ar >= 4, G[3], 0.0);
+                }
+                a[t] = kl_sel4(G, lk);
+            }
+#pragma unroll
+        for (int tj = 0; tj < NT; ++tj)
+            if (tj <= tc) b[tj] = n[kp_lower(tc, tj)][q];
+#pragma unroll
+        for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+            for (int tj = 0; tj <= ti; ++tj)
+                if (ti >= tc && tj <= tc) n[kp_lower(ti, tj)] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ti], b[tj], n[kp_lower(ti, tj)], 0, 0, 0);
+    }
+}
+
+// N (lower tiles) -> rows of M = N' in MX (zeros below the diagonal are stored; padding lands in row NK), then row r back into m[]
+template <int NK>
+__device__ __forceinline__ void kl_tiles_to_rows(const kl_d4 (&n)[KlPanels<NK>::TILES], double (&m)[NK], kl_lds* MX, int lane, int r, bool act) {
+    constexpr int NT = KlPanels<NK>::NT;
+    const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < NT; ++tj)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (KP_T * ti + 4 * g >= NK) continue;  // columns of the padding only (compile time)
+                const int col = KP_T * ti + lk + 4 * g, row = KP_T * tj + li;  // M[row][col] = N[col][row]
+                const bool in = (KP_T * tj + KP_T <= NK || row < NK) && (KP_T * ti + 4 * g + 4 <= NK || col < NK);
+                MX[in ? row * KL_LD + col : NK * KL_LD + li] = tj <= ti ? n[kp_lower(ti, tj)][g] : 0.0;
+            }
+    kl_sync();
+    const kl_lds* row = MX + (act ? r : NK) * KL_LD;
+#pragma unroll
+    for (int k = 0; k + 1 < NK; k += 2) {
+        const kl_d2 t = *(const kl_lds2*)(row + k);
+        m[k] = t[0], m[k + 1] = t[1];
+    }
+    if (NK & 1) m[NK - 1] = row[NK - 1];
+    kl_sync();
+}
+
+// M = L^-T of the block that kl_ldl / kl_ldl_panels factorise(d): row r into m[] of lane r and into MX; returns 1 / d_r.  FOLLOW:
+// concurrently with the factorisation, in a second wave
+template <int NK, bool FOLLOW>
+__device__ __forceinline__ double kl_inverse_rows(double (&m)[NK], const kl_lds* C, const kl_lds* I, kl_lds* MX, int r, bool act, kl_ldsi* P, int pbase) {
+    if constexpr (kl_panel_path(NK)) {
+        kl_d4 n[KlPanels<NK>::TILES];
+        kl_inverse_panels<NK, FOLLOW>(n, C, r, P, pbase);
+        kl_tiles_to_rows<NK>(n, m, MX, r, r, act);
+        if (FOLLOW) kl_await_opaque(P, pbase + NK + 1);
+        return I[act ? r : 0];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) m[k] = (k == r) ? 1.0 : 0.0;
+        if (FOLLOW)
+            kl_follow_LinvT<NK>(m, C, I, P, pbase);
+        else
+            kl_row_times_LinvT<NK>(m, C, I);
+        if (FOLLOW) kl_await_opaque(P, pbase + NK + 1);  // the LAST reciprocal pivot is written after the last image was announced
+        const double dinv = I[act ? r : 0];  // (read before the chain is told to go on: its next block overwrites I)
+        kl_store_rows<NK>(m, MX, r, act);
+        return dinv;
+    }
 }

@@ -14,7 +14,7 @@
 //     sweep; step into the ping-pong arrays + neighbourhood test + next iteration's weights);
 //   * per-control-point 3x3 accumulators are expanded into the knot blocks (no atomics) by the six waves that would otherwise
 //     idle behind the factorisation chains, block by block just ahead of them (twisted_factor);
-//   * the block-tridiagonal factorisation: nk <= 36 twisted two-wave chains, L D L' with column images broadcast through LDS
+//   * the block-tridiagonal factorisation: nk <= 36 twisted two-wave chains, L D L' with column images broadcast through LDS (36 x 36 blocks: 4-column panels on the FP64 MFMA, knot_lds.inc)
 //     (knot_lds.inc), the explicit inverse factor M = L^-T by a companion wave, MFMA rank-k updates; wider batches an MFMA-tiled path
 //     (LDS-resident for nk <= 72); substitutions as matrix-vector products with the staged M;
 //   * an active-set polish (qp_polish.inc) turns the interior-point answer into the exact optimum, verified by a full
@@ -1418,8 +1418,8 @@ __device__ __forceinline__ bool chol_rows(double (&a)[NK], double& dinv) {  // r
 // ---- one chain of the twisted factorisation (round 3: knot_lds.inc, cross-lane traffic through LDS broadcasts) --------------------
 // Per knot j of the chain (the chain's previous knot jp = j - dir):
 //   S_j = T_j - X_j D_jp^-1 X_j'          X_j = T_{j,jp} L_jp^-T  (rows of block j), the rank-NK update on v_mfma_f64_16x16x4_f64
-//   S_j = L_j D_j L_j'                    kl_ldl: column images in LDS
-//   M_j = L_j^-T                          explicit (kl_row_times_LinvT): the substitutions are matrix-vector products with M_j, and
+//   S_j = L_j D_j L_j'                    kl_ldl: column images in LDS; NK = 36: kl_ldl_panels, 4 columns per step on the FP64 MFMA, panel images in LDS
+//   M_j = L_j^-T                          explicit (kl_inverse_rows): the substitutions are matrix-vector products with M_j, and
 //   X_jn = Cpl M_j                        the coupling factor towards the next knot costs three multiply-adds per entry
 // What a knot leaves in global memory for the substitutions is M_j (row r contiguous, entries k < r are zeros) and 1 / d_j: 5.5 KB of
 // triangle + diagonal instead of the two full blocks (L_j, X_j: 20.7 KB) of the round-2 formulation; X never leaves the LDS.
@@ -1435,7 +1435,8 @@ __device__ __forceinline__ void coupling_coef(const QpWs& w, int j, int dir, int
     e2 = dir > 0 ? E[6 + rr % 3] : E[3 * (rr % 3) + 2];
 }
 
-// the diagonal block of one knot: S = T_j (- U) into registers, factorised (column images in C, 1 / d in I); P / pbase: see kl_ldl.
+// the diagonal block of one knot: S = T_j (- U) into registers, factorised (1 / d in I; in C the column images of kl_ldl or, for the blocks
+// on the panel path -- kl_panel_path(NK), the 36 x 36 blocks --, the panel images of kl_ldl_panels); P / pbase: see kl_ldl / kl_ldl_panels.
 // Timg != nullptr (512-thread build): T_j is read from the assembling wave's LDS image instead of global memory -- the block never leaves
 // the CU, and the chain does not start every knot with a trip to memory --; when the values have arrived *consumed = consumed_value
 // tells the assembling wave that it may overwrite the image.
@@ -1444,6 +1445,17 @@ __device__ __forceinline__ bool knot_ldl(const QpWs& w, int j, bool minus_u, kl_
                                          const kl_lds* Timg = nullptr, kl_ldsi* consumed = nullptr, int consumed_value = 0) {
     using A = KlArea<NK>;
     kl_lds *C = base + A::C, *I = base + A::I, *U = base + A::C;
+    if constexpr (kl_panel_path(NK)) {  // S straight into the MFMA tiles of the panel-blocked factorisation (knot_lds.inc, kl_knot_panels)
+        if (Timg)
+            return kl_knot_panels<NK, true>([&](int mx, int mn) { return (double)Timg[mn * KL_LD + mx]; },  // (the images hold both triangles)
+                                      [&] {
+                                          kl_sync();
+                                          if (consumed) kl_publish(consumed, consumed_value);
+                                      },
+                                      minus_u, C, I, r, P, pbase);
+        const double* Tg = w.Td + (size_t)j * NK * NK;
+        return kl_knot_panels<NK, false>([&](int mx, int mn) { return Tg[mn * NK + mx]; }, [] {}, minus_u, C, I, r, P, pbase);
+    }
     double a[NK];
     if (Timg) {
 #pragma unroll
@@ -1471,22 +1483,15 @@ __device__ __forceinline__ bool knot_ldl(const QpWs& w, int j, bool minus_u, kl_
 }
 
 // M = L^-T of the block just factorised: rows into MX (for the coupling factor) and, with 1 / d, into global memory (for the
-// substitutions).  FOLLOW: run by the chain's companion wave concurrently with knot_ldl of the chain wave (kl_follow_LinvT).
+// substitutions).  FOLLOW: run by the chain's companion wave concurrently with knot_ldl of the chain wave (kl_inverse_rows: kl_follow_LinvT a
+// column or two behind the chain, or kl_inverse_panels one panel behind it).
 template <int NK, bool FOLLOW>
 __device__ __forceinline__ void knot_inverse(const QpWs& w, int j, kl_lds* base, int r, bool act, kl_ldsi* P, int pbase, int& seen, kl_ldsi* Mdone,
                                              int done_value) {
     using A = KlArea<NK>;
     kl_lds *C = base + A::C, *MX = base + A::MX, *I = base + A::I;
     double m[NK];
-#pragma unroll
-    for (int k = 0; k < NK; ++k) m[k] = (k == r) ? 1.0 : 0.0;
-    if (FOLLOW)
-        kl_follow_LinvT<NK>(m, C, I, P, pbase);
-    else
-        kl_row_times_LinvT<NK>(m, C, I);
-    if (FOLLOW) kl_await_opaque(P, pbase + NK + 1);  // the LAST reciprocal pivot is written after the last image was announced
-    const double dinv = I[act ? r : 0];  // (read before the chain is told to go on: its next block overwrites I)
-    kl_store_rows<NK>(m, MX, r, act);
+    const double dinv = kl_inverse_rows<NK, FOLLOW>(m, C, I, MX, r, act, P, pbase);  // (1 / d is read before the chain is told to go on: its next block overwrites I)
     if (FOLLOW) kl_publish(Mdone, done_value);
     __attribute__((address_space(1))) double* Mg = QG(w.Lf + (size_t)j * KF_STRIDE(NK));
     // (256-thread build: the next block's inputs, sent for a block ago by global_load_lds, are counted on this wave's memory counter; they have
@@ -1528,7 +1533,7 @@ __device__ __forceinline__ void knot_inverse(const QpWs& w, int j, kl_lds* base,
 #define ASM_CONSUMED(cnt, h) ((kl_ldsi*)((cnt) + 72 + (h)))
 
 // one chain: blocks j0, j0+dir, ... (count of them).  The chain wave factorises; its companion wave (wave_factor_follow) computes
-// M_j = L_j^-T a column or two behind and stores it.  On return the chain's LDS area holds the coupling factor X towards the middle
+// M_j = L_j^-T a column or two (panel path: one panel of 4 columns) behind and stores it.  On return the chain's LDS area holds the coupling factor X towards the middle
 // block (MX) and the reciprocal pivots of its last block (I): wave_factor_mid reads both chains' areas.
 template <int NK>
 __device__ __forceinline__ bool wave_factor_chain(const QpDims& d, const QpWs& w, int j0, int count, int dir, double* ldsW, int* cnt, int h) {

@@ -1,5 +1,9 @@
-// Developer test + timing of kernels/knot_lds.inc (one wavefront, a chain of knot steps) against a host restatement.
-//   hipcc --offload-arch=gfx950 -O3 -I../../swarm_simulator_amd/csrc/kernels -o knot knot.hip && ./knot
+// Developer test + timing of kernels/knot_lds.inc in the arrangement the product runs (qp.hip, wave_factor_chain / knot_inverse): a chain
+// wave and its companion wave on different SIMDs of ONE workgroup, synchronised by the progress words, over a chain of knot steps,
+// against a host restatement.  NK = 9, 18, 27, 36; diagonal spreads 1e4 and 1e8 (the spread of an interior-point system).
+//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I../../swarm_simulator_amd/csrc/kernels -DKL_PANEL=1 -o knot knot.hip && ./knot
+// -DKL_PANEL=0: the column loop (kl_ldl / kl_follow_LinvT) for every NK; -DKL_PANEL=1: the panel path where kl_panel_path(NK) says so
+// (-DKL_PANEL_MIN_NK=9: for every NK).  One workgroup per launch; run it under a time limit of its own.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -8,79 +12,108 @@
 
 #include "knot_lds.inc"
 
-constexpr int NK = 36;
 constexpr int STEPS = 6;
 
-// T: [STEPS][NK*NK] element (r,k) at k*NK + r (symmetric); E: [STEPS][9]; out M, X: [STEPS][NK*NK] element (r,k) at k*NK + r; dinv [STEPS][NK]
-__global__ __launch_bounds__(512) void chain_kernel(const double* T, const double* E, double* Mo, double* Xo, double* Do, long long* cyc, int* okflag, int waves_active) {
-    extern __shared__ __attribute__((aligned(16))) double lds_raw[];
-    const int wave = threadIdx.x >> 6, r = threadIdx.x & 63;
-    if (wave >= waves_active) return;
+// timers of the chain wave, cycles per knot step: [0] whole step, [1] syrk, [2] load + factorisation, [3] start of the factorisation ->
+// "M rows are in MX" (what the chain waits for), [4] coupling rows; [5] of the companion wave: its whole step
+struct Timers {
+    long long v[8];
+};
+
+// the diagonal block of one knot, as knot_ldl of qp.hip forms it: S = T_j (- U), factorised
+template <int NK>
+__device__ __forceinline__ bool ub_knot_ldl(const double* Tg, bool minus_u, kl_lds* base, int r, bool act, int rr, kl_ldsi* P, int pbase) {
     using A = KlArea<NK>;
-    kl_lds* base = (kl_lds*)(lds_raw + wave * A::SIZE);
-    kl_lds *C = base + A::C, *MX = base + A::MX, *I = base + A::I, *U = base + A::C;
-    for (int i = r; i < A::SIZE; i += 64) base[i] = 0.0;
-    kl_sync();
-    const bool act = r < NK;
-    const int rr = act ? r : 0;
-    bool ok = true;
-    long long t0 = __builtin_readcyclecounter(), tl = 0, tm = 0, tx = 0, ts = 0, tst = 0;
-    for (int i = 0; i < STEPS; ++i) {
-        long long c0 = __builtin_readcyclecounter();
-#ifndef NO_SYRK
-        if (i > 0) kl_syrk<NK>(MX, I, U, r, false);
-#endif
-        long long c1 = __builtin_readcyclecounter();
+    kl_lds *C = base + A::C, *I = base + A::I, *U = base + A::C;
+    (void)U;
+    if constexpr (kl_panel_path(NK)) {
+        return kl_knot_panels<NK, false>([&](int mx, int mn) { return Tg[mn * NK + mx]; }, [] {}, minus_u, C, I, r, P, pbase);
+    } else {
         double a[NK];
-        const double* Tg = T + (size_t)i * NK * NK;
 #pragma unroll
         for (int k = 0; k < NK; ++k) a[k] = Tg[k * NK + rr];
-        if (i > 0) {
+        if (minus_u) {
 #pragma unroll
             for (int k = 0; k < NK; ++k) a[k] -= U[rr * KL_LDU + k];
             kl_sync();
         }
-        double m[NK];
-#pragma unroll
-        for (int k = 0; k < NK; ++k) m[k] = (k == r) ? 1.0 : 0.0;
-        if (!kl_ldl<NK>(a, C, I, r, act)) ok = false;
-        long long c2 = __builtin_readcyclecounter();
-#ifndef NO_M
-        kl_row_times_LinvT<NK>(m, C, I);
-        kl_store_rows<NK>(m, MX, r, act);
-        long long c2b = __builtin_readcyclecounter();
-        if (act && wave == 0) {   // row r of M = L^-T, entries k >= r: pairs, 16 bytes per lane and instruction
-            double* Mr = Mo + (size_t)i * NK * NK + (size_t)r * NK;
-#pragma unroll
-            for (int k = 0; k < NK; k += 2)
-                if (k + 1 >= r) *(kl_d2*)(Mr + k) = kl_d2{m[k], m[k + 1]};
-            Do[i * NK + r] = I[r];
-        }
-        tst += __builtin_readcyclecounter() - c2b;
-#endif
-        long long c3 = __builtin_readcyclecounter();
-        const double* Ei = E + 9 * i;
-        const double e0 = Ei[rr % 3], e1 = Ei[3 + rr % 3], e2 = Ei[6 + rr % 3];  // T_{j+1,j}[r][3g+q] = E[q][r%3]
-#ifndef NO_X
-        double x[NK];
-        kl_coupling_rows<NK>(x, MX, r, act, e0, e1, e2);
-        if (act && wave == 0 && i == STEPS - 1) {  // (the product does not store X: checked here on the last step only)
-#pragma unroll
-            for (int k = 0; k < NK; ++k) Xo[(size_t)i * NK * NK + k * NK + r] = x[k];
-        }
-#endif
-        long long c4 = __builtin_readcyclecounter();
-        ts += c1 - c0, tl += c2 - c1, tm += c3 - c2, tx += c4 - c3;
+        return kl_ldl<NK>(a, C, I, r, act, P, pbase);
     }
-    long long t1 = __builtin_readcyclecounter();
-    if (r == 0) cyc[wave * 8 + 0] = (t1 - t0) / STEPS, cyc[wave * 8 + 1] = ts / STEPS, cyc[wave * 8 + 2] = tl / STEPS, cyc[wave * 8 + 3] = tm / STEPS, cyc[wave * 8 + 4] = tx / STEPS, cyc[wave * 8 + 5] = tst / STEPS;
-    if (!ok && r == 0) *okflag = 1;
 }
 
-int main() {
+// T: [STEPS][NK*NK] element (r,k) at k*NK + r (symmetric); E: [STEPS][9]; out M: [STEPS][NK*NK] row-major, X: element (r,k) at k*NK + r (last step),
+// dinv [STEPS][NK].  256 threads: waves 0, 1 = chains, waves 2, 3 = their companions (only `pairs` of them work; pair 0 is checked)
+template <int NK>
+__global__ __launch_bounds__(256) void pair_kernel(const double* T, const double* E, double* Mo, double* Xo, double* Do, Timers* tm, int* okflag, int pairs) {
+    extern __shared__ __attribute__((aligned(16))) double lds_raw[];
+    using A = KlArea<NK>;
+    const int wave = threadIdx.x >> 6, r = threadIdx.x & 63, h = wave & 1;
+    const bool follower = wave >= 2;
+    kl_ldsi* words = (kl_ldsi*)(lds_raw + 2 * A::SIZE);
+    for (int i = threadIdx.x; i < 2 * A::SIZE + 8; i += 256) lds_raw[i] = 0.0;
+    __syncthreads();
+    if (h >= pairs) return;
+    kl_lds* base = (kl_lds*)(lds_raw + h * A::SIZE);
+    kl_lds *C = base + A::C, *MX = base + A::MX, *I = base + A::I, *U = base + A::C;
+    kl_ldsi *P = words + 2 * h, *Mdone = P + 1;
+    const bool act = r < NK;
+    const int rr = act ? r : 0;
+    long long t_all = 0, t_syrk = 0, t_fac = 0, t_m = 0, t_x = 0;
+    if (!follower) {
+        bool ok = true;
+        int seen = 0;
+        for (int i = 0; i < STEPS; ++i) {
+            const long long c0 = __builtin_readcyclecounter();
+            if (i > 0) kl_syrk<NK>(MX, I, U, r, false);
+            const long long c1 = __builtin_readcyclecounter();
+            const double* Ei = E + 9 * i;
+            const double e0 = Ei[rr % 3], e1 = Ei[3 + rr % 3], e2 = Ei[6 + rr % 3];  // T_{j+1,j}[r][3g+q] = E[q][r%3]
+            if (!ub_knot_ldl<NK>(T + (size_t)i * NK * NK, i > 0, base, r, act, rr, P, i * (NK + 1))) ok = false;
+            const long long c2 = __builtin_readcyclecounter();
+            kl_await(Mdone, i + 1, seen);
+            const long long c3 = __builtin_readcyclecounter();
+            double x[NK];
+            kl_coupling_rows<NK>(x, MX, r, act, e0, e1, e2);
+            if (act && h == 0 && i == STEPS - 1) {  // (the product does not store X: checked here on the last step only)
+#pragma unroll
+                for (int k = 0; k < NK; ++k) Xo[(size_t)i * NK * NK + k * NK + r] = x[k];
+            }
+            const long long c4 = __builtin_readcyclecounter();
+            t_syrk += c1 - c0, t_fac += c2 - c1, t_m += c3 - c1, t_x += c4 - c3, t_all += c4 - c0;
+        }
+        if (r == 0 && h == 0) tm->v[0] = t_all / STEPS, tm->v[1] = t_syrk / STEPS, tm->v[2] = t_fac / STEPS, tm->v[3] = t_m / STEPS, tm->v[4] = t_x / STEPS;
+        if (!ok && r == 0) *okflag = 1;
+    } else {
+        for (int i = 0; i < STEPS; ++i) {  // knot_inverse<NK, true> of qp.hip
+            const long long c0 = __builtin_readcyclecounter();
+            double m[NK];
+            const double dinv = kl_inverse_rows<NK, true>(m, C, I, MX, r, act, P, i * (NK + 1));
+            kl_publish(Mdone, i + 1);
+            if (act && h == 0) {  // row r of M = L^-T, entries k >= r: pairs, 16 bytes per lane and instruction
+                double* Mr = Mo + (size_t)i * NK * NK + (size_t)r * NK;
+                if ((NK & 1) == 0) {
+#pragma unroll
+                    for (int k = 0; k < NK; k += 2)
+                        if (k + 1 >= r) *(kl_d2*)(Mr + k) = kl_d2{m[k], m[k + 1]};
+                } else {
+#pragma unroll
+                    for (int k = 0; k < NK; ++k)
+                        if (k >= r) Mr[k] = m[k];
+                }
+                Do[i * NK + r] = dinv;
+            }
+            t_all += __builtin_readcyclecounter() - c0;
+        }
+        if (r == 0 && h == 0) tm->v[5] = t_all / STEPS;
+    }
+}
+
+static double rnd() { return rand() / (double)RAND_MAX - 0.5; }
+
+template <int NK>
+static bool run(double spread, bool timing) {
     std::vector<double> T(STEPS * NK * NK), E(STEPS * 9);
-    srand(7);
-    auto rnd = [] { return rand() / (double)RAND_MAX - 0.5; };
+    srand(7 + NK);
     for (int i = 0; i < STEPS; ++i) {
         std::vector<double> B(NK * NK);
         for (auto& v : B) v = rnd();
@@ -88,7 +121,7 @@ int main() {
             for (int k = 0; k < NK; ++k) {
                 double s = 0;
                 for (int q = 0; q < NK; ++q) s += B[r * NK + q] * B[k * NK + q];
-                T[(size_t)i * NK * NK + k * NK + r] = s + (r == k ? 30.0 + 1e4 * (r % 5 == 0) : 0.0);  // SPD, some large diagonal entries like IPM weights
+                T[(size_t)i * NK * NK + k * NK + r] = s + (r == k ? 30.0 + spread * (r % 5 == 0) : 0.0);  // SPD, some large diagonal entries like IPM weights
             }
         for (int e = 0; e < 9; ++e) E[9 * i + e] = 3.0 * rnd();
     }
@@ -136,44 +169,66 @@ int main() {
         }
     }
     double *dT, *dE, *dM, *dX, *dD;
-    long long* dc;
+    Timers* dt;
     int* dok;
-    hipMalloc(&dT, T.size() * 8), hipMalloc(&dE, E.size() * 8), hipMalloc(&dM, Mh.size() * 8), hipMalloc(&dX, Xh.size() * 8), hipMalloc(&dD, Dh.size() * 8);
-    hipMalloc(&dc, 8 * 64 * 8), hipMalloc(&dok, 4);
-    hipMemcpy(dT, T.data(), T.size() * 8, hipMemcpyHostToDevice), hipMemcpy(dE, E.data(), E.size() * 8, hipMemcpyHostToDevice);
-    hipMemset(dok, 0, 4);
-    const size_t lds = 5 * KlArea<NK>::SIZE * sizeof(double);  // five areas = 145 KB
-    hipFuncSetAttribute((const void*)chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    printf("LDS per chain wave: %d doubles = %.1f KB\n", KlArea<NK>::SIZE, KlArea<NK>::SIZE * 8 / 1024.0);
-    for (int waves : {1, 2, 4}) {
-        // waves chain waves per workgroup; with 512 threads = 8 waves (2 per SIMD), only `waves` of them work
-        for (int rep = 0; rep < 2; ++rep) hipLaunchKernelGGL(chain_kernel, dim3(1), dim3(512), lds, 0, dT, dE, dM, dX, dD, dc, dok, waves);
-        if (hipDeviceSynchronize() != hipSuccess) printf("launch failed\n");
-        long long h[64];
-        hipMemcpy(h, dc, sizeof(h), hipMemcpyDeviceToHost);
-        printf("chain waves %d: cycles per step %lld  (syrk %lld, load+ldl %lld, Linv^T rows + LDS + global store %lld of which global store %lld, coupling rows %lld)\n", waves, h[0], h[1], h[2], h[3], h[5], h[4]);
+    bool hip_ok = true;
+    auto ck = [&](hipError_t e) { if (e != hipSuccess) hip_ok = false; };
+    ck(hipMalloc(&dT, T.size() * 8)), ck(hipMalloc(&dE, E.size() * 8)), ck(hipMalloc(&dM, Mh.size() * 8)), ck(hipMalloc(&dX, Xh.size() * 8)), ck(hipMalloc(&dD, Dh.size() * 8));
+    ck(hipMalloc(&dt, sizeof(Timers))), ck(hipMalloc(&dok, 4));
+    if (!hip_ok) {
+        printf("NK %d: allocation failed\nFAIL\n", NK);
+        exit(2);  // nothing more is started on a device that failed
     }
-    // 5 waves working: one SIMD carries two chains
-    hipLaunchKernelGGL(chain_kernel, dim3(1), dim3(512), lds, 0, dT, dE, dM, dX, dD, dc, dok, 5);
-    if (hipDeviceSynchronize() != hipSuccess) printf("launch failed\n");
-    {
-        long long h[64];
-        hipMemcpy(h, dc, sizeof(h), hipMemcpyDeviceToHost);
-        printf("chain waves 5 (one SIMD carries two): cycles per step %lld %lld %lld %lld %lld\n", h[0], h[8], h[16], h[24], h[32]);
+    ck(hipMemcpy(dT, T.data(), T.size() * 8, hipMemcpyHostToDevice)), ck(hipMemcpy(dE, E.data(), E.size() * 8, hipMemcpyHostToDevice));
+    ck(hipMemset(dok, 0, 4)), ck(hipMemset(dM, 0, Mh.size() * 8)), ck(hipMemset(dX, 0, Xh.size() * 8)), ck(hipMemset(dD, 0, Dh.size() * 8));
+    const size_t lds = (2 * KlArea<NK>::SIZE + 8) * sizeof(double);
+    ck(hipFuncSetAttribute((const void*)pair_kernel<NK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (int pairs : {1, 2}) {
+        if (!timing && pairs == 2) break;
+        Timers h{};
+        for (int rep = 0; rep < 2 && hip_ok; ++rep) {  // (the second launch is the one reported: warm instruction cache)
+            hipLaunchKernelGGL(pair_kernel<NK>, dim3(1), dim3(256), lds, 0, dT, dE, dM, dX, dD, dt, dok, pairs);
+            ck(hipDeviceSynchronize());
+        }
+        if (!hip_ok) {
+            printf("NK %d: launch failed\nFAIL\n", NK);
+            exit(2);
+        }
+        ck(hipMemcpy(&h, dt, sizeof(h), hipMemcpyDeviceToHost));
+        if (timing)
+            printf("NK %d %s, %d chain + companion pair%s: cycles per knot step %lld  (syrk %lld, load + factorisation %lld, factorisation start -> M rows in MX %lld, "
+                   "coupling rows %lld; companion step %lld)\n",
+                   NK, kl_panel_path(NK) ? "panels" : "columns", pairs, pairs > 1 ? "s" : "", h.v[0], h.v[1], h.v[2], h.v[3], h.v[4], h.v[5]);
     }
     std::vector<double> Mg(Mh.size()), Xg(Xh.size()), Dg(Dh.size());
-    int okf;
-    hipMemcpy(Mg.data(), dM, Mg.size() * 8, hipMemcpyDeviceToHost), hipMemcpy(Xg.data(), dX, Xg.size() * 8, hipMemcpyDeviceToHost);
-    hipMemcpy(Dg.data(), dD, Dg.size() * 8, hipMemcpyDeviceToHost), hipMemcpy(&okf, dok, 4, hipMemcpyDeviceToHost);
+    int okf = 1;
+    ck(hipMemcpy(Mg.data(), dM, Mg.size() * 8, hipMemcpyDeviceToHost)), ck(hipMemcpy(Xg.data(), dX, Xg.size() * 8, hipMemcpyDeviceToHost));
+    ck(hipMemcpy(Dg.data(), dD, Dg.size() * 8, hipMemcpyDeviceToHost)), ck(hipMemcpy(&okf, dok, 4, hipMemcpyDeviceToHost));
+    hipFree(dT), hipFree(dE), hipFree(dM), hipFree(dX), hipFree(dD), hipFree(dt), hipFree(dok);
     double em = 0, ex = 0, ed = 0, sm = 0, sx = 0;
     for (size_t i = 0; i < Mh.size(); ++i) {
         const int rr = (int)(i % (NK * NK)) / NK, kk = (int)(i % NK);
-        if ((kk | 1) >= rr) em = fmax(em, fabs(Mg[i] - Mh[i])), sm = fmax(sm, fabs(Mh[i]));   // only pairs with k + 1 >= r are stored
+        if (((NK & 1) ? kk : (kk | 1)) >= rr) em = fmax(em, fabs(Mg[i] - Mh[i])), sm = fmax(sm, fabs(Mh[i]));  // only entries k >= r (pairs: k + 1 >= r) are stored
         if (i >= (size_t)(STEPS - 1) * NK * NK) ex = fmax(ex, fabs(Xg[i] - Xh[i])), sx = fmax(sx, fabs(Xh[i]));
     }
     for (size_t i = 0; i < Dh.size(); ++i) ed = fmax(ed, fabs(Dg[i] - Dh[i]) / fabs(Dh[i]));
-    printf("pivots positive: %s   max|M err| %.3g (scale %.3g)  max|X err| %.3g (scale %.3g)  max rel 1/d err %.3g\n", okf ? "NO" : "yes", em, sm, ex, sx, ed);
-    const bool pass = !okf && em < 1e-11 * fmax(1.0, sm) && ex < 1e-11 * fmax(1.0, sx) && ed < 1e-12;
+    // (negated comparisons: a NaN fails)
+    const bool pass = hip_ok && !okf && em < 1e-11 * fmax(1.0, sm) && ex < 1e-11 * fmax(1.0, sx) && ed < 1e-12;
+    printf("NK %d spread %.0e: pivots positive: %s   max|M err| %.3g (scale %.3g)  max|X err| %.3g (scale %.3g)  max rel 1/d err %.3g   %s\n", NK, spread,
+           okf ? "NO" : "yes", em, sm, ex, sx, ed, pass ? "ok" : "MISMATCH");
+    return pass;
+}
+
+int main() {
+    printf("KL_PANEL=%d KL_PANEL_MIN_NK=%d; LDS per chain wave (NK 36): %d doubles = %.1f KB\n", KL_PANEL, KL_PANEL_MIN_NK, KlArea<36>::SIZE, KlArea<36>::SIZE * 8 / 1024.0);
+    bool pass = true;
+    for (double spread : {1e4, 1e8}) {
+        const bool timing = spread == 1e4;
+        pass = run<9>(spread, timing) && pass;
+        pass = run<18>(spread, timing) && pass;
+        pass = run<27>(spread, timing) && pass;
+        pass = run<36>(spread, timing) && pass;
+    }
     printf("%s\n", pass ? "PASS" : "FAIL");
     return pass ? 0 : 1;
 }
