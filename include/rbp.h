@@ -45,8 +45,14 @@ typedef struct rbp_world {
     int32_t dim[3];     /* nx, ny, nz */
     int32_t key_min[3]; /* voxel key of cell (0,0,0), relative to the octree centre */
     double res;         /* octree resolution [m] */
-    const float* dist;  /* [nx][ny][nz], metres, z fastest */
+    const float* dist;  /* [nx][ny][nz], metres, z fastest; a host pointer, or a DEVICE pointer (see below) */
 } rbp_world;
+/* rbp_world.dist may point into the HBM of the device the call runs on -- a grid of rbp_dev_worlds (below), or any other device
+ * allocation of that layout, e.g. a caller's torch tensor -- wherever a world is taken: rbp_session_create / rbp_session_create_in,
+ * the one-shot and context calls, rbp_corridor_update_range.  The library asks the HIP runtime what the pointer is (a pointer the
+ * runtime does not know is a host pointer).  A device grid is referenced IN PLACE: nothing is copied, so the caller keeps it alive
+ * and unchanged until the session is destroyed (the one-shot and context calls: until they return).  A grid on another device than
+ * the session's is RBP_ERR_BAD_ARGUMENT.  Missions that hand in the same pointer and shape share one grid, host or device. */
 
 /* ---- mission.hpp:13-15 ---------------------------------------------------------------------- */
 typedef struct rbp_mission {
@@ -350,10 +356,34 @@ const char* rbp_version(void);
  * rbp_world.dist points at, [nx][ny][nz] with z fastest, clamped at ((int)(max_dist / res + 1)) cells like dynamicEDT3D.
  * leaf_keys: [n_leaves][4] = min-corner voxel key minus 32768 (x, y, z) and edge length in voxels of every occupied leaf (what
  * rbp_octomap_load_bt of rbp_host.h returns).  rbp_edt_dims gives the grid shape (dim, key_min as in rbp_world) for a box;
- * rbp_edt_build fills dist (host buffer of dim[0]*dim[1]*dim[2] floats).  Bit-identical to the host library's rbp_world_build. */
+ * rbp_edt_build fills dist (host buffer of dim[0]*dim[1]*dim[2] floats): a set of one world (rbp_dev_worlds, below) copied back.
+ * Bit-identical to the host library's rbp_world_build. */
 int rbp_edt_dims(double res, const double bbx_min[3], const double bbx_max[3], int32_t dim[3], int32_t key_min[3]);
 int rbp_edt_build(const int32_t* leaf_keys, int64_t n_leaves, double res, const double bbx_min[3], const double bbx_max[3],
                   double max_dist, float* dist);
+
+/* ---- worlds that stay on the device -------------------------------------------------------------
+ * One build for a SET of W worlds (the 50 maps of swarm_traj_planner_rbp_test_all.cpp:49-103): the number of kernel launches does not
+ * depend on W, the W float grids lie in one device allocation owned by the set, and nothing returns to the host.  leaf_keys[w] /
+ * n_leaves[w]: the occupied leaves of world w as for rbp_edt_build (leaf_keys[w] may be NULL where n_leaves[w] is 0); res[w]: its
+ * resolution, which with the common box gives every world its own shape by rbp_edt_dims' rule; one max_dist for all.  Every grid is
+ * bit-identical to what rbp_edt_build / rbp_world_build give for that world.  Argument errors (null out, W <= 0, negative n_leaves,
+ * bbx_max < bbx_min, res <= 0, max_dist <= 0) are RBP_ERR_BAD_ARGUMENT before a device is looked for. */
+typedef struct rbp_dev_worlds rbp_dev_worlds;
+/* builds W grids on `device` (< 0: current) and returns when they are complete */
+int  rbp_dev_worlds_create(rbp_dev_worlds** out, int device, int32_t W, const int32_t* const* leaf_keys, const int64_t* n_leaves,
+                           const double* res /* [W] */, const double bbx_min[3], const double bbx_max[3], double max_dist);
+int  rbp_dev_worlds_count(const rbp_dev_worlds* ws);
+/* fills dim / key_min / res; out->dist is a DEVICE pointer, valid until destroy */
+int  rbp_dev_worlds_get(const rbp_dev_worlds* ws, int32_t w, rbp_world* out);
+int  rbp_dev_worlds_download(const rbp_dev_worlds* ws, int32_t w, float* dist_host);
+void rbp_dev_worlds_destroy(rbp_dev_worlds* ws);
+/* The coarse obstacle mask of the ECBS front-end (ECBSPlanner::setObstacles, ecbs_planner.hpp:80-109) from the resident grid of world w:
+ * what rbp_ecbs_obstacles of rbp_host.h computes from a host grid, same arguments and return values (0; 1: a sample of the planning
+ * lattice lies outside the grid; obstacle_host == NULL only fills dim), to be handed to rbp_ecbs_plan_obstacles.  One thread per sample
+ * looks the distance up; dim[0] * dim[1] * dim[2] bytes come back instead of the grid. */
+int  rbp_dev_worlds_ecbs_obstacles(const rbp_dev_worlds* ws, int32_t w, const rbp_mission* mission, const rbp_param* param, int32_t dim[3],
+                                   uint8_t* obstacle_host, size_t capacity);
 
 const char* rbp_last_error(void);
 int rbp_device_count(void);

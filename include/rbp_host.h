@@ -65,6 +65,16 @@ typedef struct rbp_init_traj_buf {
 /* returns 0 ok; 1 start/goal occluded; 2 search failed / node budget exhausted */
 int rbp_ecbs_plan(const rbp_world_buf* world, const rbp_mission* mission, const rbp_param* param,
                   int64_t max_high_level_nodes, rbp_init_traj_buf* out);
+/* rbp_ecbs_plan in its two halves -- the same result as the one call, which is the two composed:
+ * rbp_ecbs_obstacles: ECBSPlanner::setObstacles (ecbs_planner.hpp:80-109), the only reader of the fine grid: the planning lattice's shape in
+ *   dim and, if obstacle != NULL (capacity >= dim[0]*dim[1]*dim[2] bytes), its occupancy mask [dimx][dimy][dimz] of 0 / 1.  Returns 0 ok;
+ *   1 a sample of the lattice lies outside the world's grid (the mask is then incomplete); RBP_ERR_BAD_ARGUMENT.  A world that lives on
+ *   the GPU gives the same mask through rbp_dev_worlds_ecbs_obstacles of rbp.h.
+ * rbp_ecbs_plan_obstacles: the search on such a mask (dim must be the lattice's shape for `param`); returns as rbp_ecbs_plan. */
+int rbp_ecbs_obstacles(const rbp_world_buf* world, const rbp_mission* mission, const rbp_param* param, int32_t dim[3], uint8_t* obstacle,
+                       size_t capacity);
+int rbp_ecbs_plan_obstacles(const int32_t dim[3], const uint8_t* obstacle, const rbp_mission* mission, const rbp_param* param,
+                            int64_t max_high_level_nodes, rbp_init_traj_buf* out);
 void rbp_init_traj_free(rbp_init_traj_buf* t);
 
 /* ---- validation metrics of rbp_publisher.hpp:685-695, 769-798 ------------------

@@ -247,7 +247,21 @@ static int session_create_impl(rbp_session** out, int device, int K, const rbp_w
         s->n_cu = hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 256;
     }
 
-    // missions that share a map (same host grid pointer and shape, e.g. several passes of a map sweep) share one device copy
+    // a grid may already lie in HBM (rbp_dev_worlds, a caller's tensor): such a grid is used where it is.  A pointer the runtime does not
+    // know is reported as an error or as unregistered memory, depending on the runtime: both mean host
+    std::vector<char> on_device(K, 0);
+    for (int k = 0; k < K; ++k) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, worlds[k].dist) != hipSuccess) {
+            (void)hipGetLastError();  // (the error is sticky)
+            continue;
+        }
+        if (at.type != hipMemoryTypeDevice) continue;
+        if (at.device != device) return fail(RBP_ERR_BAD_ARGUMENT, "world.dist of mission " + std::to_string(k) + " lies on device " + std::to_string(at.device) +
+                                                                       ", the session on device " + std::to_string(device));
+        on_device[k] = 1;
+    }
+    // missions that share a map (same grid pointer and shape, e.g. several passes of a map sweep) share one device copy
     auto same_grid = [&](int a, int b) {
         return worlds[a].dist == worlds[b].dist && worlds[a].dim[0] == worlds[b].dim[0] && worlds[a].dim[1] == worlds[b].dim[1] &&
                worlds[a].dim[2] == worlds[b].dim[2];
@@ -263,7 +277,7 @@ static int session_create_impl(rbp_session** out, int device, int K, const rbp_w
     }
     size_t grid_bytes = 0;
     for (int k = 0; k < K; ++k)
-        if (grid_of[k] == k) grid_bytes += al(sizeof(float) * (size_t)worlds[k].dim[0] * worlds[k].dim[1] * worlds[k].dim[2]);
+        if (grid_of[k] == k && !on_device[k]) grid_bytes += al(sizeof(float) * (size_t)worlds[k].dim[0] * worlds[k].dim[1] * worlds[k].dim[2]);
     const size_t total = grid_bytes + al(sizeof(DevWorld) * K) + 2 * al(sizeof(int) * K) + al(sizeof(float) * (size_t)K * N * P * 3) +
                          al(sizeof(double) * K * P) + 2 * al(sizeof(double) * (size_t)K * N * 9) + al(sizeof(double) * K * N) +
                          2 * al(sizeof(double) * (size_t)K * N * 3) + al(sizeof(int) * K * N) + al(sizeof(unsigned) * (size_t)K * SFC_MASK_WORDS) +
@@ -330,7 +344,9 @@ static int session_create_impl(rbp_session** out, int device, int K, const rbp_w
     for (int k = 0; k < K; ++k) {
         size_t n = (size_t)worlds[k].dim[0] * worlds[k].dim[1] * worlds[k].dim[2];
         float* g;
-        if (grid_of[k] == k) {
+        if (on_device[k]) {
+            g = const_cast<float*>(worlds[k].dist);  // referenced in place: the caller keeps it alive (include/rbp.h)
+        } else if (grid_of[k] == k) {
             g = A.take<float>(n);
             UP(g, worlds[k].dist, sizeof(float) * n);
         } else {

@@ -252,31 +252,36 @@ float world_distance(const rbp_world_buf* w, float x, float y, float z) {
     return w->dist[((size_t)kx * w->dim[1] + ky) * w->dim[2] + kz];
 }
 
-}  // namespace
-
-extern "C" int rbp_ecbs_plan(const rbp_world_buf* world, const rbp_mission* mission, const rbp_param* param,
-                             int64_t max_high_level_nodes, rbp_init_traj_buf* out) {
-    if (!world || !mission || !param || !out) return RBP_ERR_BAD_ARGUMENT;
-    memset(out, 0, sizeof(*out));
+// the planning lattice of init_traj_planner.hpp:19-29: false when an axis has no cell
+bool planning_grid(const rbp_param* param, double gmin[3], double gmax[3], double gres[3], int dim[3]) {
     const double eps = 1e-9;  // SP_EPSILON
-    const int N = mission->N;
-    // init_traj_planner.hpp:19-29
-    double gmin[3], gmax[3], gres[3] = {param->grid_xy_res, param->grid_xy_res, param->grid_z_res};
-    int dim[3];
+    gres[0] = gres[1] = param->grid_xy_res, gres[2] = param->grid_z_res;
     for (int a = 0; a < 3; ++a) {
         gmin[a] = std::ceil((param->world_min[a] - eps) / gres[a]) * gres[a];
         gmax[a] = std::floor((param->world_max[a] + eps) / gres[a]) * gres[a];
         dim[a] = (int)std::round((gmax[a] - gmin[a]) / gres[a]) + 1;
-        if (dim[a] <= 0) return RBP_ERR_BAD_ARGUMENT;
+        if (dim[a] <= 0) return false;
     }
-    Grid g;
-    g.dimx = dim[0], g.dimy = dim[1], g.dimz = dim[2];
-    g.grid_size = param->grid_xy_res;
-    g.radius.assign(mission->radius, mission->radius + N);
-    g.obstacle.assign((size_t)dim[0] * dim[1] * dim[2], 0);
-    // ecbs_planner.hpp:80-109
+    return true;
+}
+
+}  // namespace
+
+// ECBSPlanner::setObstacles (ecbs_planner.hpp:80-109): the only reader of the fine distance grid in the front-end
+extern "C" int rbp_ecbs_obstacles(const rbp_world_buf* world, const rbp_mission* mission, const rbp_param* param, int32_t dim_out[3],
+                                  uint8_t* obstacle, size_t capacity) {
+    if (!world || !mission || !param || !dim_out) return RBP_ERR_BAD_ARGUMENT;
+    const double eps = 1e-9;  // SP_EPSILON
+    double gmin[3], gmax[3], gres[3];
+    int dim[3];
+    if (!planning_grid(param, gmin, gmax, gres, dim)) return RBP_ERR_BAD_ARGUMENT;
+    for (int a = 0; a < 3; ++a) dim_out[a] = dim[a];
+    if (!obstacle) return RBP_OK;  // (only the shape was asked for)
+    const size_t ncell = (size_t)dim[0] * dim[1] * dim[2];
+    if (capacity < ncell) return RBP_ERR_BAD_ARGUMENT;
+    memset(obstacle, 0, ncell);
     double r = 0;
-    for (int qi = 0; qi < N; ++qi) r = std::max(r, mission->radius[qi]);
+    for (int qi = 0; qi < mission->N; ++qi) r = std::max(r, mission->radius[qi]);
     for (double k = gmin[2]; k < gmax[2] + eps; k += gres[2])
         for (double i = gmin[0]; i < gmax[0] + eps; i += gres[0])
             for (double j = gmin[1]; j < gmax[1] + eps; j += gres[1]) {
@@ -287,9 +292,40 @@ extern "C" int rbp_ecbs_plan(const rbp_world_buf* world, const rbp_mission* miss
                     int y = (int)std::round((j - gmin[1]) / gres[1]);
                     int z = (int)std::round((k - gmin[2]) / gres[2]);
                     if (x >= 0 && y >= 0 && z >= 0 && x < dim[0] && y < dim[1] && z < dim[2])
-                        g.obstacle[((size_t)x * dim[1] + y) * dim[2] + z] = 1;
+                        obstacle[((size_t)x * dim[1] + y) * dim[2] + z] = 1;
                 }
             }
+    return RBP_OK;
+}
+
+extern "C" int rbp_ecbs_plan(const rbp_world_buf* world, const rbp_mission* mission, const rbp_param* param,
+                             int64_t max_high_level_nodes, rbp_init_traj_buf* out) {
+    if (!world || !mission || !param || !out) return RBP_ERR_BAD_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    int32_t dim[3];
+    int rc = rbp_ecbs_obstacles(world, mission, param, dim, nullptr, 0);
+    if (rc) return rc;
+    std::vector<uint8_t> obstacle((size_t)dim[0] * dim[1] * dim[2]);
+    rc = rbp_ecbs_obstacles(world, mission, param, dim, obstacle.data(), obstacle.size());
+    if (rc) return rc;
+    return rbp_ecbs_plan_obstacles(dim, obstacle.data(), mission, param, max_high_level_nodes, out);
+}
+
+// ECBSPlanner::update on a given obstacle mask ([dimx][dimy][dimz], as Grid::obstacle)
+extern "C" int rbp_ecbs_plan_obstacles(const int32_t dim_in[3], const uint8_t* obstacle, const rbp_mission* mission, const rbp_param* param,
+                                       int64_t max_high_level_nodes, rbp_init_traj_buf* out) {
+    if (!dim_in || !obstacle || !mission || !param || !out) return RBP_ERR_BAD_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    const int N = mission->N;
+    double gmin[3], gmax[3], gres[3];
+    int dim[3];
+    if (!planning_grid(param, gmin, gmax, gres, dim)) return RBP_ERR_BAD_ARGUMENT;
+    if (dim_in[0] != dim[0] || dim_in[1] != dim[1] || dim_in[2] != dim[2]) return RBP_ERR_BAD_ARGUMENT;  // a mask of another lattice
+    Grid g;
+    g.dimx = dim[0], g.dimy = dim[1], g.dimz = dim[2];
+    g.grid_size = param->grid_xy_res;
+    g.radius.assign(mission->radius, mission->radius + N);
+    g.obstacle.assign(obstacle, obstacle + (size_t)dim[0] * dim[1] * dim[2]);
     // ecbs_planner.hpp:112-136
     std::vector<Cell> starts(N), goals(N);
     for (int i = 0; i < N; ++i) {

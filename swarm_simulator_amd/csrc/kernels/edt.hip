@@ -15,6 +15,9 @@
 // both are >= md^2 and clamp to the same value.  11-cell windows on the 101 x 101 x 23 grids of the benchmark: 0.23 M voxels x 63 reads.
 #include "rbp_dev.h"
 
+#include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -22,40 +25,143 @@ namespace {
 
 constexpr int EDT_INF = 0x3f3f3f3f;
 
-__global__ __launch_bounds__(256) void edt_raster_kernel(const int* __restrict__ keys, long long n_leaves, int kx0, int ky0, int kz0, int nx, int ny,
-                                                         int nz, int* __restrict__ g) {
-    // one thread per occupied leaf: a cube of `s` voxels per edge, clipped to the box (DynamicEDTOctomap::initializeOcTree)
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_leaves) return;
-    const int s = keys[4 * i + 3];
-    const int x0 = max(keys[4 * i] - kx0, 0), x1 = min(keys[4 * i] - kx0 + s - 1, nx - 1);
-    const int y0 = max(keys[4 * i + 1] - ky0, 0), y1 = min(keys[4 * i + 1] - ky0 + s - 1, ny - 1);
-    const int z0 = max(keys[4 * i + 2] - kz0, 0), z1 = min(keys[4 * i + 2] - kz0 + s - 1, nz - 1);
+// ---- a SET of W worlds in one build (rbp_dev_worlds of include/rbp.h) ------------------------------------------------------------------
+// The three min-plus passes, with the world index as a grid dimension: the leaf lists of all worlds lie in one buffer, every world has
+// a descriptor (its own res, hence its own dim / key_min / md) and the float grids lie back to back in one allocation.  Per chunk of
+// worlds (the int32 scratch is bounded, whatever W):
+//   1. edt_set_raster_kernel   leaves -> one byte of occupancy per voxel (cleared by a memset before)
+//   2. edt_set_zy_kernel       one workgroup per (world, x) slab of ny * nz cells: the z pass from the occupancy bytes into LDS, the y
+//                              pass from LDS into the only int32 intermediate that reaches global memory (9.3 KB of LDS at 101 x 23)
+//   3. edt_set_x_finish_kernel one thread per voxel: the x pass (2 md - 1 coalesced reads) and the finish: sqrt in double, rounded to float
+//                              (dynamicEDT3D keeps float distances in cells), times the double resolution, rounded to float (getDistance)
+// A slab of more than EDT_SLAB_MAX cells (64 KB of LDS) takes edt_set_z_kernel + edt_set_y_kernel through a second int32 buffer instead
+// of kernel 2.  Integer minima are exact in any order, so both routes give the same floats, bit for bit, and so does a set of one
+// (rbp_edt_build) or of fifty.
+struct EdtWorldDesc {
+    int dim[3];
+    int kmin[3];
+    int md;                // window half-width + 1 in cells: (int)(max_dist / res + 1)
+    int n_leaves;
+    long long leaf_off;    // first leaf of the world in the set's leaf buffer
+    long long cell_off;    // first cell of the world in the set's float allocation
+    long long chunk_off;   // first cell of the world in the chunk's scratch
+    double res;
+};
+
+#ifndef EDT_SLAB_MAX_CELLS
+#define EDT_SLAB_MAX_CELLS 16384  // (A/B builds: -DEDT_SLAB_MAX_CELLS=0 sends every set through the unfused passes, tools/dev_worlds_ab.py)
+#endif
+constexpr int EDT_SLAB_MAX = EDT_SLAB_MAX_CELLS;  // cells of a (world, x) slab the fused z + y kernel keeps in LDS as int32: 64 KB
+constexpr long long EDT_CHUNK_CELLS = 1 << 22;  // scratch of a chunk of worlds: 4 M cells = 16 MB of int32 + 4 MB of occupancy
+constexpr int EDT_CHUNK_WORLDS = 32768;         // (grid dimension y)
+
+__global__ __launch_bounds__(256) void edt_set_raster_kernel(const EdtWorldDesc* __restrict__ desc, const int* __restrict__ keys,
+                                                             unsigned char* __restrict__ occ) {
+    const EdtWorldDesc& w = desc[blockIdx.y];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= w.n_leaves) return;
+    const int* k = keys + 4 * (w.leaf_off + i);
+    const int nx = w.dim[0], ny = w.dim[1], nz = w.dim[2];
+    const int s = k[3];
+    const int x0 = max(k[0] - w.kmin[0], 0), x1 = min(k[0] - w.kmin[0] + s - 1, nx - 1);
+    const int y0 = max(k[1] - w.kmin[1], 0), y1 = min(k[1] - w.kmin[1] + s - 1, ny - 1);
+    const int z0 = max(k[2] - w.kmin[2], 0), z1 = min(k[2] - w.kmin[2] + s - 1, nz - 1);
+    unsigned char* g = occ + w.chunk_off;
     for (int x = x0; x <= x1; ++x)
         for (int y = y0; y <= y1; ++y)
-            for (int z = z0; z <= z1; ++z) g[((size_t)x * ny + y) * nz + z] = 0;
+            for (int z = z0; z <= z1; ++z) g[((size_t)x * ny + y) * nz + z] = 1;
 }
 
-// out(c) = min over |d| < md of d^2 + in(c + d * stride) along one axis (n cells, position p of c along it)
-__global__ __launch_bounds__(256) void edt_pass_kernel(const int* __restrict__ in, int* __restrict__ out, long long ncell, int n, long long stride, int md) {
-    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ncell) return;
-    const int p = (int)((c / stride) % n);
+// z pass of one cell from the occupancy bytes of its row: min over |d| < md of d^2 where occ(z + d) is set
+__device__ __forceinline__ int edt_z_of_row(const unsigned char* __restrict__ row, int z, int nz, int md) {
+    const int lo = max(-(md - 1), -z), hi = min(md - 1, nz - 1 - z);
+    int best = EDT_INF;
+    for (int d = lo; d <= hi; ++d)
+        if (row[z + d]) best = min(best, d * d);
+    return best;
+}
+
+// min over |d| < md of d^2 + in[d * stride] along an axis of n cells, for the cell at position p of it (`in` points at that cell)
+template <class Ptr>
+__device__ __forceinline__ int edt_window(Ptr in, int p, int n, long long stride, int md) {
     const int lo = max(-(md - 1), -p), hi = min(md - 1, n - 1 - p);
     int best = EDT_INF;
     for (int d = lo; d <= hi; ++d) {
-        const int v = in[c + d * stride];
+        const int v = in[d * stride];
         best = min(best, v >= EDT_INF ? EDT_INF : v + d * d);
     }
-    out[c] = best;
+    return best;
 }
 
-__global__ __launch_bounds__(256) void edt_finish_kernel(const int* __restrict__ d2, float* __restrict__ dist, long long ncell, int md2, double res) {
+__global__ __launch_bounds__(256) void edt_set_zy_kernel(const EdtWorldDesc* __restrict__ desc, const unsigned char* __restrict__ occ,
+                                                         int* __restrict__ d2) {
+    extern __shared__ int slab[];  // [ny][nz]: the slab after the z pass
+    const EdtWorldDesc& w = desc[blockIdx.y];
+    const int x = blockIdx.x;
+    if (x >= w.dim[0]) return;  // (uniform over the workgroup: before any barrier)
+    const int ny = w.dim[1], nz = w.dim[2], md = w.md, n = ny * nz;
+    const long long base = w.chunk_off + (long long)x * n;
+    const unsigned char* o = occ + base;
+    for (int c = threadIdx.x; c < n; c += blockDim.x) {
+        const int y = c / nz, z = c - y * nz;
+        slab[c] = edt_z_of_row(o + y * nz, z, nz, md);
+    }
+    __syncthreads();
+    int* out = d2 + base;
+    for (int c = threadIdx.x; c < n; c += blockDim.x) out[c] = edt_window(slab + c, c / nz, ny, (long long)nz, md);
+}
+
+// the same two passes unfused, for slabs that do not fit the LDS: one thread per voxel and pass
+__global__ __launch_bounds__(256) void edt_set_z_kernel(const EdtWorldDesc* __restrict__ desc, const unsigned char* __restrict__ occ,
+                                                        int* __restrict__ out) {
+    const EdtWorldDesc& w = desc[blockIdx.y];
     const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ncell) return;
-    const int sq = d2[c];
+    if (c >= (long long)w.dim[0] * w.dim[1] * w.dim[2]) return;
+    const int nz = w.dim[2], z = (int)(c % nz);
+    out[w.chunk_off + c] = edt_z_of_row(occ + w.chunk_off + (c - z), z, nz, w.md);
+}
+
+__global__ __launch_bounds__(256) void edt_set_y_kernel(const EdtWorldDesc* __restrict__ desc, const int* __restrict__ in, int* __restrict__ out) {
+    const EdtWorldDesc& w = desc[blockIdx.y];
+    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= (long long)w.dim[0] * w.dim[1] * w.dim[2]) return;
+    const int ny = w.dim[1], nz = w.dim[2];
+    out[w.chunk_off + c] = edt_window(in + w.chunk_off + c, (int)((c / nz) % ny), ny, (long long)nz, w.md);
+}
+
+__global__ __launch_bounds__(256) void edt_set_x_finish_kernel(const EdtWorldDesc* __restrict__ desc, const int* __restrict__ d2,
+                                                               float* __restrict__ dist) {
+    const EdtWorldDesc& w = desc[blockIdx.y];
+    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= (long long)w.dim[0] * w.dim[1] * w.dim[2]) return;
+    const long long stride = (long long)w.dim[1] * w.dim[2];
+    const int sq = edt_window(d2 + w.chunk_off + c, (int)(c / stride), w.dim[0], stride, w.md);
+    const int md2 = w.md * w.md;
     const float cells = (float)__dsqrt_rn((double)(sq < md2 ? sq : md2));  // dynamicEDT3D keeps float distances in cells
-    dist[c] = (float)((double)cells * res);                                 // getDistance: float * double treeResolution -> float
+    dist[w.cell_off + c] = (float)((double)cells * w.res);                 // getDistance: float * double treeResolution -> float
+}
+
+// ---- the coarse obstacle mask of the ECBS front-end from a resident grid (ECBSPlanner::setObstacles, ecbs_planner.hpp:80-109) ----------
+// One thread per sample (x, y, z) of the planning lattice: getDistance's lookup and `dist < r + grid_margin` in double.  xs / ys / zs hold the
+// sample coordinates as float (octomap::point3d), cx / cy / cz the mask cell of each sample (-1: none), both made on the host by the
+// reference's own loops.  A sample outside the grid sets *outside.
+__global__ __launch_bounds__(256) void ecbs_obstacle_kernel(DevWorld w, const float* __restrict__ xs, const float* __restrict__ ys,
+                                                            const float* __restrict__ zs, const int* __restrict__ cx, const int* __restrict__ cy,
+                                                            const int* __restrict__ cz, int sx, int sy, int sz, int dimy, int dimz, double limit,
+                                                            unsigned char* __restrict__ mask, unsigned* __restrict__ outside) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= sx * sy * sz) return;
+    const int c = i % sz, b = (i / sz) % sy, a = i / (sz * sy);
+    const double rf = 1.0 / w.res;
+    const int kx = (int)floor(rf * (double)xs[a]) - w.key_min[0];
+    const int ky = (int)floor(rf * (double)ys[b]) - w.key_min[1];
+    const int kz = (int)floor(rf * (double)zs[c]) - w.key_min[2];
+    if (kx < 0 || ky < 0 || kz < 0 || kx >= w.dim[0] || ky >= w.dim[1] || kz >= w.dim[2]) {
+        atomicOr(outside, 1u);
+        return;
+    }
+    const float d = w.dist[((size_t)kx * w.dim[1] + ky) * w.dim[2] + kz];
+    if ((double)d < limit && cx[a] >= 0 && cy[b] >= 0 && cz[c] >= 0) mask[((size_t)cx[a] * dimy + cy[b]) * dimz + cz[c]] = 1;
 }
 
 int dims(double res, const double* bmin, const double* bmax, int* dim, int* kmin) {
@@ -74,27 +180,55 @@ int dims(double res, const double* bmin, const double* bmax, int* dim, int* kmin
 
 }  // namespace
 
-extern "C" int rbp_edt_dims(double res, const double bbx_min[3], const double bbx_max[3], int32_t dim[3], int32_t key_min[3]) {
-    if (!bbx_min || !bbx_max || !dim || !key_min || dims(res, bbx_min, bbx_max, dim, key_min))
-        return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_edt_dims: need res > 0, bbx_min <= bbx_max, at most 4096 voxels per axis");
-    return RBP_OK;
-}
+// W float grids in one allocation on one device, with what rbp_world needs of each
+struct rbp_dev_worlds {
+    int device = 0;
+    float* dist = nullptr;
+    std::vector<EdtWorldDesc> desc;
+};
 
-extern "C" int rbp_edt_build(const int32_t* leaf_keys, int64_t n_leaves, double res, const double bbx_min[3], const double bbx_max[3],
-                             double max_dist, float* dist) {
-    int dim[3], kmin[3];
-    if (!bbx_min || !bbx_max || !dist || n_leaves < 0 || (n_leaves > 0 && !leaf_keys) || !(max_dist > 0) || dims(res, bbx_min, bbx_max, dim, kmin))
-        return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_edt_build: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rbp_set_error(RBP_ERR_NO_DEVICE, "no HIP device: the RBP path has no CPU fallback");
-    const long long ncell = (long long)dim[0] * dim[1] * dim[2];
-    const int md = (int)(max_dist / res + 1);
-    if (md < 1 || md > 4096) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_edt_build: max_dist / res out of range");
-    int *d_keys = nullptr, *d_a = nullptr, *d_b = nullptr;
-    float* d_dist = nullptr;
+namespace {
+
+struct DeviceScope {  // the calling thread's current device is put back when the call returns
+    int prev = -1;
+    explicit DeviceScope(int device) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != device) (void)hipSetDevice(device);
+        else prev = -1;
+    }
+    ~DeviceScope() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// builds the grids of `ws` (desc filled but for chunk_off; ws->dist allocated) on the current device; returns when they are complete
+int build_set(rbp_dev_worlds* ws, const int32_t* const* leaf_keys) {
+    const int W = (int)ws->desc.size();
+    std::vector<int> keys_h;
+    for (int w = 0; w < W; ++w)
+        if (ws->desc[w].n_leaves > 0) keys_h.insert(keys_h.end(), leaf_keys[w], leaf_keys[w] + 4 * (size_t)ws->desc[w].n_leaves);
+    // chunks of consecutive worlds whose cells fit the scratch (a world larger than the scratch is a chunk of its own)
+    std::vector<int> chunk_begin{0};
+    long long in_chunk = 0, scratch_cells = 0;
+    bool any_unfused = false;
+    for (int w = 0; w < W; ++w) {
+        EdtWorldDesc& d = ws->desc[w];
+        const long long nc = (long long)d.dim[0] * d.dim[1] * d.dim[2];
+        if (w > chunk_begin.back() && (in_chunk + nc > EDT_CHUNK_CELLS || w - chunk_begin.back() >= EDT_CHUNK_WORLDS)) chunk_begin.push_back(w), in_chunk = 0;
+        d.chunk_off = in_chunk;
+        in_chunk += nc;
+        scratch_cells = std::max(scratch_cells, in_chunk);
+        any_unfused = any_unfused || d.dim[1] * d.dim[2] > EDT_SLAB_MAX;
+    }
+    chunk_begin.push_back(W);
+
+    int* d_keys = nullptr;
+    EdtWorldDesc* d_desc = nullptr;
+    unsigned char* d_occ = nullptr;
+    int *d_a = nullptr, *d_b = nullptr;
     hipError_t e = hipSuccess;
     auto done = [&](int rc, const std::string& msg) {
-        (void)hipFree(d_keys), (void)hipFree(d_a), (void)hipFree(d_b), (void)hipFree(d_dist);
+        (void)hipFree(d_keys), (void)hipFree(d_desc), (void)hipFree(d_occ), (void)hipFree(d_a), (void)hipFree(d_b);
         return rc == RBP_OK ? RBP_OK : rbp_set_error(rc, msg.c_str());
     };
 #define EDT_TRY(expr)                                                                                  \
@@ -102,23 +236,219 @@ extern "C" int rbp_edt_build(const int32_t* leaf_keys, int64_t n_leaves, double 
         e = (expr);                                                                                    \
         if (e != hipSuccess) return done(RBP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e)); \
     } while (0)
-    EDT_TRY(hipMalloc((void**)&d_a, sizeof(int) * ncell));
-    EDT_TRY(hipMalloc((void**)&d_b, sizeof(int) * ncell));
-    EDT_TRY(hipMalloc((void**)&d_dist, sizeof(float) * ncell));
-    EDT_TRY(hipMemset(d_a, 0x3f, sizeof(int) * ncell));
-    const unsigned nb = (unsigned)((ncell + 255) / 256);
-    if (n_leaves > 0) {
-        EDT_TRY(hipMalloc((void**)&d_keys, sizeof(int) * 4 * n_leaves));
-        EDT_TRY(hipMemcpy(d_keys, leaf_keys, sizeof(int) * 4 * n_leaves, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(edt_raster_kernel, dim3((unsigned)((n_leaves + 255) / 256)), dim3(256), 0, 0, d_keys, (long long)n_leaves, kmin[0], kmin[1],
-                           kmin[2], dim[0], dim[1], dim[2], d_a);
+    if (!keys_h.empty()) {
+        EDT_TRY(hipMalloc((void**)&d_keys, sizeof(int) * keys_h.size()));
+        EDT_TRY(hipMemcpy(d_keys, keys_h.data(), sizeof(int) * keys_h.size(), hipMemcpyHostToDevice));
     }
-    hipLaunchKernelGGL(edt_pass_kernel, dim3(nb), dim3(256), 0, 0, d_a, d_b, ncell, dim[2], 1LL, md);                          // z
-    hipLaunchKernelGGL(edt_pass_kernel, dim3(nb), dim3(256), 0, 0, d_b, d_a, ncell, dim[1], (long long)dim[2], md);             // y
-    hipLaunchKernelGGL(edt_pass_kernel, dim3(nb), dim3(256), 0, 0, d_a, d_b, ncell, dim[0], (long long)dim[1] * dim[2], md);    // x
-    hipLaunchKernelGGL(edt_finish_kernel, dim3(nb), dim3(256), 0, 0, d_b, d_dist, ncell, md * md, res);
-    EDT_TRY(hipGetLastError());
-    EDT_TRY(hipMemcpy(dist, d_dist, sizeof(float) * ncell, hipMemcpyDeviceToHost));
+    EDT_TRY(hipMalloc((void**)&d_desc, sizeof(EdtWorldDesc) * W));
+    EDT_TRY(hipMemcpy(d_desc, ws->desc.data(), sizeof(EdtWorldDesc) * W, hipMemcpyHostToDevice));
+    EDT_TRY(hipMalloc((void**)&d_occ, (size_t)scratch_cells));
+    EDT_TRY(hipMalloc((void**)&d_a, sizeof(int) * (size_t)scratch_cells));
+    if (any_unfused) EDT_TRY(hipMalloc((void**)&d_b, sizeof(int) * (size_t)scratch_cells));
+    for (size_t ci = 0; ci + 1 < chunk_begin.size(); ++ci) {
+        const int w0 = chunk_begin[ci], nw = chunk_begin[ci + 1] - w0;
+        long long cells = 0, max_cells = 0;
+        int max_leaves = 0, max_nx = 0, max_slab = 0;
+        for (int w = w0; w < w0 + nw; ++w) {
+            const EdtWorldDesc& d = ws->desc[w];
+            const long long nc = (long long)d.dim[0] * d.dim[1] * d.dim[2];
+            cells += nc, max_cells = std::max(max_cells, nc);
+            max_leaves = std::max(max_leaves, d.n_leaves), max_nx = std::max(max_nx, d.dim[0]), max_slab = std::max(max_slab, d.dim[1] * d.dim[2]);
+        }
+        const EdtWorldDesc* dd = d_desc + w0;
+        const unsigned nb = (unsigned)((max_cells + 255) / 256);
+        EDT_TRY(hipMemsetAsync(d_occ, 0, (size_t)cells, 0));
+        if (max_leaves > 0)
+            hipLaunchKernelGGL(edt_set_raster_kernel, dim3((unsigned)((max_leaves + 255) / 256), nw), dim3(256), 0, 0, dd, d_keys, d_occ);
+        if (max_slab <= EDT_SLAB_MAX) {
+            hipLaunchKernelGGL(edt_set_zy_kernel, dim3(max_nx, nw), dim3(256), sizeof(int) * (size_t)max_slab, 0, dd, d_occ, d_a);
+            hipLaunchKernelGGL(edt_set_x_finish_kernel, dim3(nb, nw), dim3(256), 0, 0, dd, d_a, ws->dist);
+        } else {
+            hipLaunchKernelGGL(edt_set_z_kernel, dim3(nb, nw), dim3(256), 0, 0, dd, d_occ, d_a);
+            hipLaunchKernelGGL(edt_set_y_kernel, dim3(nb, nw), dim3(256), 0, 0, dd, d_a, d_b);
+            hipLaunchKernelGGL(edt_set_x_finish_kernel, dim3(nb, nw), dim3(256), 0, 0, dd, d_b, ws->dist);
+        }
+        EDT_TRY(hipGetLastError());
+    }
+    EDT_TRY(hipStreamSynchronize(0));
 #undef EDT_TRY
     return done(RBP_OK, "");
+}
+
+// argument checks and descriptors of a set (no device work); nullptr + the error recorded on a bad argument
+rbp_dev_worlds* describe_set(const char* who, int32_t W, const int32_t* const* leaf_keys, const int64_t* n_leaves, const double* res,
+                             const double* bmin, const double* bmax, double max_dist) {
+    auto bad = [&](const char* what) {
+        rbp_set_error(RBP_ERR_BAD_ARGUMENT, (std::string(who) + ": " + what).c_str());
+        return (rbp_dev_worlds*)nullptr;
+    };
+    if (W <= 0 || !n_leaves || !res || !bmin || !bmax) return bad("need W > 0, n_leaves, res and the box");
+    if (!(max_dist > 0)) return bad("need max_dist > 0");
+    auto* ws = new rbp_dev_worlds();
+    ws->desc.resize(W);
+    long long cell_off = 0, leaf_off = 0;
+    for (int w = 0; w < W; ++w) {
+        EdtWorldDesc& d = ws->desc[w];
+        const char* what = nullptr;
+        if (n_leaves[w] < 0 || n_leaves[w] > 0x7fffffff / 4 || (n_leaves[w] > 0 && (!leaf_keys || !leaf_keys[w]))) what = "negative n_leaves, or leaves without keys";
+        else if (dims(res[w], bmin, bmax, d.dim, d.kmin)) what = "need res > 0, bbx_min <= bbx_max, at most 4096 voxels per axis";
+        else if (!(max_dist / res[w] + 1 < 4097.0)) what = "max_dist / res out of range";
+        if (what) {
+            delete ws;
+            return bad(what);
+        }
+        d.md = (int)(max_dist / res[w] + 1);
+        d.n_leaves = (int)n_leaves[w];
+        d.leaf_off = leaf_off, d.cell_off = cell_off, d.chunk_off = 0, d.res = res[w];
+        leaf_off += d.n_leaves, cell_off += (long long)d.dim[0] * d.dim[1] * d.dim[2];
+    }
+    return ws;
+}
+
+int create_set(const char* who, rbp_dev_worlds** out, int device, int32_t W, const int32_t* const* leaf_keys, const int64_t* n_leaves,
+               const double* res, const double* bmin, const double* bmax, double max_dist) {
+    rbp_dev_worlds* ws = describe_set(who, W, leaf_keys, n_leaves, res, bmin, bmax, max_dist);
+    if (!ws) return RBP_ERR_BAD_ARGUMENT;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        delete ws;
+        return rbp_set_error(RBP_ERR_NO_DEVICE, "no HIP device: the RBP path has no CPU fallback");
+    }
+    if (device < 0) (void)hipGetDevice(&device);
+    if (device < 0 || device >= ndev) {
+        delete ws;
+        return rbp_set_error(RBP_ERR_NO_DEVICE, "device index out of range");
+    }
+    ws->device = device;
+    DeviceScope scope(device);
+    const EdtWorldDesc& last = ws->desc.back();
+    const long long total = last.cell_off + (long long)last.dim[0] * last.dim[1] * last.dim[2];
+    hipError_t e = hipMalloc((void**)&ws->dist, sizeof(float) * (size_t)total);
+    int rc = e == hipSuccess ? build_set(ws, leaf_keys) : rbp_set_error(RBP_ERR_HIP, (std::string("hipMalloc: ") + hipGetErrorString(e)).c_str());
+    if (rc) {
+        (void)hipFree(ws->dist);
+        delete ws;
+        return rc;
+    }
+    *out = ws;
+    return RBP_OK;
+}
+
+}  // namespace
+
+extern "C" int rbp_edt_dims(double res, const double bbx_min[3], const double bbx_max[3], int32_t dim[3], int32_t key_min[3]) {
+    if (!bbx_min || !bbx_max || !dim || !key_min || dims(res, bbx_min, bbx_max, dim, key_min))
+        return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_edt_dims: need res > 0, bbx_min <= bbx_max, at most 4096 voxels per axis");
+    return RBP_OK;
+}
+
+// one world, returned to the host: a set of one on the calling thread's current device, and the copy back
+extern "C" int rbp_edt_build(const int32_t* leaf_keys, int64_t n_leaves, double res, const double bbx_min[3], const double bbx_max[3],
+                             double max_dist, float* dist) {
+    if (!dist) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_edt_build: bad argument");
+    rbp_dev_worlds* ws = nullptr;
+    int rc = create_set("rbp_edt_build", &ws, -1, 1, &leaf_keys, &n_leaves, &res, bbx_min, bbx_max, max_dist);
+    if (rc) return rc;
+    rc = rbp_dev_worlds_download(ws, 0, dist);
+    rbp_dev_worlds_destroy(ws);
+    return rc;
+}
+
+extern "C" int rbp_dev_worlds_create(rbp_dev_worlds** out, int device, int32_t W, const int32_t* const* leaf_keys, const int64_t* n_leaves,
+                                     const double* res, const double bbx_min[3], const double bbx_max[3], double max_dist) {
+    if (!out) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_create: null out");
+    *out = nullptr;
+    return create_set("rbp_dev_worlds_create", out, device, W, leaf_keys, n_leaves, res, bbx_min, bbx_max, max_dist);
+}
+
+extern "C" int rbp_dev_worlds_count(const rbp_dev_worlds* ws) { return ws ? (int)ws->desc.size() : 0; }
+
+extern "C" int rbp_dev_worlds_get(const rbp_dev_worlds* ws, int32_t w, rbp_world* out) {
+    if (!ws || !out || w < 0 || w >= (int)ws->desc.size()) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_get: null argument or world index out of range");
+    const EdtWorldDesc& d = ws->desc[w];
+    for (int a = 0; a < 3; ++a) out->dim[a] = d.dim[a], out->key_min[a] = d.kmin[a];
+    out->res = d.res;
+    out->dist = ws->dist + d.cell_off;
+    return RBP_OK;
+}
+
+extern "C" int rbp_dev_worlds_download(const rbp_dev_worlds* ws, int32_t w, float* dist_host) {
+    rbp_world g;
+    if (!dist_host) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_download: null buffer");
+    if (int rc = rbp_dev_worlds_get(ws, w, &g)) return rc;
+    DeviceScope scope(ws->device);
+    const hipError_t e = hipMemcpy(dist_host, g.dist, sizeof(float) * (size_t)g.dim[0] * g.dim[1] * g.dim[2], hipMemcpyDeviceToHost);
+    return e == hipSuccess ? RBP_OK : rbp_set_error(RBP_ERR_HIP, (std::string("hipMemcpy: ") + hipGetErrorString(e)).c_str());
+}
+
+extern "C" void rbp_dev_worlds_destroy(rbp_dev_worlds* ws) {
+    if (!ws) return;
+    if (ws->dist) {
+        DeviceScope scope(ws->device);
+        (void)hipFree(ws->dist);
+    }
+    delete ws;
+}
+
+extern "C" int rbp_dev_worlds_ecbs_obstacles(const rbp_dev_worlds* ws, int32_t w, const rbp_mission* mission, const rbp_param* param, int32_t dim[3],
+                                             uint8_t* obstacle_host, size_t capacity) {
+    rbp_world g;
+    if (!mission || !param || !dim || mission->N <= 0 || !mission->radius) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_ecbs_obstacles: null argument");
+    if (int rc = rbp_dev_worlds_get(ws, w, &g)) return rc;
+    // the planning lattice and its samples, by the reference's own loops (init_traj_planner.hpp:19-29, ecbs_planner.hpp:80-109)
+    const double eps = SP_EPSILON;
+    const double gres[3] = {param->grid_xy_res, param->grid_xy_res, param->grid_z_res};
+    std::vector<float> pos[3];
+    std::vector<int> cell[3];
+    for (int a = 0; a < 3; ++a) {
+        if (!(gres[a] > 0)) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_ecbs_obstacles: grid resolution must be positive");
+        const double gmin = std::ceil((param->world_min[a] - eps) / gres[a]) * gres[a];
+        const double gmax = std::floor((param->world_max[a] + eps) / gres[a]) * gres[a];
+        const double n = std::round((gmax - gmin) / gres[a]) + 1;
+        if (!(n > 0) || n > 4096) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_ecbs_obstacles: planning grid empty or above 4096 cells per axis");
+        dim[a] = (int)n;
+        for (double i = gmin; i < gmax + eps; i += gres[a]) {
+            const int c = (int)std::round((i - gmin) / gres[a]);
+            pos[a].push_back((float)i), cell[a].push_back(c >= 0 && c < dim[a] ? c : -1);
+        }
+    }
+    if (!obstacle_host) return RBP_OK;  // (only the shape was asked for)
+    const size_t ncell = (size_t)dim[0] * dim[1] * dim[2];
+    if (capacity < ncell) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_ecbs_obstacles: obstacle buffer smaller than dim[0] * dim[1] * dim[2]");
+    double r = 0;
+    for (int qi = 0; qi < mission->N; ++qi) r = std::max(r, mission->radius[qi]);
+    const int sx = (int)pos[0].size(), sy = (int)pos[1].size(), sz = (int)pos[2].size(), ns = sx + sy + sz;
+    if ((double)sx * sy * sz > (double)(1 << 30)) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_ecbs_obstacles: more than 2^30 samples");
+    // one upload (sample coordinates, then their mask cells), one buffer back (the mask, then the flag word)
+    std::vector<int> up(2 * (size_t)ns);
+    for (int a = 0, o = 0; a < 3; o += (int)pos[a].size(), ++a) {
+        memcpy(&up[o], pos[a].data(), sizeof(float) * pos[a].size());
+        memcpy(&up[ns + o], cell[a].data(), sizeof(int) * cell[a].size());
+    }
+    const size_t mask_bytes = (ncell + 3) & ~size_t(3);
+    std::vector<unsigned char> back(mask_bytes + 4);
+    DeviceScope scope(ws->device);
+    int* d_up = nullptr;
+    unsigned char* d_mask = nullptr;
+    hipError_t e = hipMalloc((void**)&d_up, sizeof(int) * up.size());
+    if (e == hipSuccess) e = hipMalloc((void**)&d_mask, back.size());
+    if (e == hipSuccess) e = hipMemcpy(d_up, up.data(), sizeof(int) * up.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(d_mask, 0, back.size(), 0);
+    if (e == hipSuccess) {
+        DevWorld dw;
+        for (int a = 0; a < 3; ++a) dw.dim[a] = g.dim[a], dw.key_min[a] = g.key_min[a];
+        dw.res = g.res, dw.dist = g.dist;
+        const float* f = reinterpret_cast<const float*>(d_up);
+        const int* c = d_up + ns;
+        hipLaunchKernelGGL(ecbs_obstacle_kernel, dim3((unsigned)(((size_t)sx * sy * sz + 255) / 256)), dim3(256), 0, 0, dw, f, f + sx, f + sx + sy, c, c + sx,
+                           c + sx + sy, sx, sy, sz, dim[1], dim[2], r + param->grid_margin, d_mask, reinterpret_cast<unsigned*>(d_mask + mask_bytes));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(back.data(), d_mask, back.size(), hipMemcpyDeviceToHost);
+    (void)hipFree(d_up), (void)hipFree(d_mask);
+    if (e != hipSuccess) return rbp_set_error(RBP_ERR_HIP, (std::string("rbp_dev_worlds_ecbs_obstacles: ") + hipGetErrorString(e)).c_str());
+    memcpy(obstacle_host, back.data(), ncell);
+    unsigned outside = 0;
+    memcpy(&outside, back.data() + mask_bytes, 4);
+    return outside ? 1 : RBP_OK;
 }

@@ -35,6 +35,10 @@ def lib():
         L.rbp_world_free.restype = None
         L.rbp_ecbs_plan.argtypes = [C.POINTER(A.rbp_world_buf), C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param),
                                     C.c_int64, C.POINTER(A.rbp_init_traj_buf)]
+        L.rbp_ecbs_obstacles.argtypes = [C.POINTER(A.rbp_world_buf), C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.c_int32 * 3,
+                                         C.POINTER(C.c_uint8), C.c_size_t]
+        L.rbp_ecbs_plan_obstacles.argtypes = [C.c_int32 * 3, C.POINTER(C.c_uint8), C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param),
+                                              C.c_int64, C.POINTER(A.rbp_init_traj_buf)]
         L.rbp_init_traj_free.argtypes = [C.POINTER(A.rbp_init_traj_buf)]
         L.rbp_init_traj_free.restype = None
         L.rbp_validate.argtypes = [C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.c_int32, A.c_double_p,
@@ -111,19 +115,56 @@ def load_world(path, param: Param) -> World:
     return build_world(keys, res, param)
 
 
-def ecbs_plan(world: World, mission: Mission, param: Param, max_nodes=200000) -> PlanResult:
-    """ECBSPlanner::update (ecbs_planner.hpp:21-72): returns a PlanResult holding initTraj and T."""
-    out = A.rbp_init_traj_buf()
-    wb, ms, ps = world.c_buf(), mission.c_struct(), param.c_struct()
-    rc = lib().rbp_ecbs_plan(C.byref(wb), C.byref(ms), C.byref(ps), max_nodes, C.byref(out))
+ECBS_ERROR_TEXT = {1: "ECBSPlanner: start/goal occluded by obstacle", 2: "ECBSPlanner: ECBS Failed!"}
+
+
+def _plan_result(rc, out) -> PlanResult:
     if rc:
-        raise RuntimeError({1: "ECBSPlanner: start/goal occluded by obstacle", 2: "ECBSPlanner: ECBS Failed!"}.get(rc, f"rc={rc}"))
+        raise RuntimeError(ECBS_ERROR_TEXT.get(rc, f"rc={rc}"))
     N, M = out.N, out.M
     pr = PlanResult(_np(out.init_traj, (N, M + 1, 3), np.float32), _np(out.T, (M + 1,), np.float64))
     pr.ecbs_stats = dict(makespan=out.makespan, sum_cost=out.sum_cost, high_level=out.high_level_expanded,
                          low_level=out.low_level_expanded)
     lib().rbp_init_traj_free(C.byref(out))
     return pr
+
+
+def ecbs_plan(world: World, mission: Mission, param: Param, max_nodes=200000) -> PlanResult:
+    """ECBSPlanner::update (ecbs_planner.hpp:21-72): returns a PlanResult holding initTraj and T."""
+    out = A.rbp_init_traj_buf()
+    wb, ms, ps = world.c_buf(), mission.c_struct(), param.c_struct()
+    return _plan_result(lib().rbp_ecbs_plan(C.byref(wb), C.byref(ms), C.byref(ps), max_nodes, C.byref(out)), out)
+
+
+def obstacle_mask(call):
+    """the two-step protocol of rbp_ecbs_obstacles / rbp_dev_worlds_ecbs_obstacles: call(dim, buffer or None, capacity) -> rc; returns
+    (rc, mask [dimx][dimy][dimz] uint8)."""
+    dim = (C.c_int32 * 3)()
+    rc = call(dim, None, 0)
+    if rc:
+        return rc, None
+    mask = np.zeros(tuple(dim), np.uint8)
+    return call(dim, mask.ctypes.data_as(C.POINTER(C.c_uint8)), mask.size), mask
+
+
+def ecbs_obstacles(world: World, mission: Mission, param: Param) -> np.ndarray:
+    """ECBSPlanner::setObstacles (ecbs_planner.hpp:80-109): the occupancy mask [dimx][dimy][dimz] of the planning lattice.  A lattice
+    sample outside the world's grid raises what ecbs_plan raises."""
+    wb, ms, ps = world.c_buf(), mission.c_struct(), param.c_struct()
+    rc, mask = obstacle_mask(lambda dim, buf, cap: lib().rbp_ecbs_obstacles(C.byref(wb), C.byref(ms), C.byref(ps), dim, buf, cap))
+    if rc:
+        raise RuntimeError(ECBS_ERROR_TEXT.get(rc, f"rc={rc}"))
+    return mask
+
+
+def ecbs_plan_obstacles(obstacle, mission: Mission, param: Param, max_nodes=200000) -> PlanResult:
+    """the search of ecbs_plan on a mask from ecbs_obstacles (or planner.ecbs_obstacles): ecbs_plan is the two composed."""
+    mask = np.ascontiguousarray(obstacle, np.uint8)
+    out = A.rbp_init_traj_buf()
+    ms, ps = mission.c_struct(), param.c_struct()
+    rc = lib().rbp_ecbs_plan_obstacles((C.c_int32 * 3)(*mask.shape), mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(ms), C.byref(ps),
+                                       max_nodes, C.byref(out))
+    return _plan_result(rc, out)
 
 
 def validate(mission: Mission, param: Param, plan: PlanResult, dt=0.1):

@@ -11,7 +11,7 @@ import ctypes as C
 import os
 
 from . import _abi as A
-from .types import Mission, Param, PlanResult, World
+from .types import DeviceWorld, Mission, Param, PlanResult, World
 
 _lib = None
 
@@ -112,6 +112,14 @@ def lib():
         try:  # (developer A/B builds of older commits loaded through RBP_HIP_LIB may predate the GPU distance grid)
             L.rbp_edt_dims.argtypes = [C.c_double, C.c_double * 3, C.c_double * 3, C.c_int32 * 3, C.c_int32 * 3]
             L.rbp_edt_build.argtypes = [A.c_int32_p, C.c_int64, C.c_double, C.c_double * 3, C.c_double * 3, C.c_double, A.c_float_p]
+            L.rbp_dev_worlds_create.argtypes = [P(C.c_void_p), C.c_int, C.c_int32, P(A.c_int32_p), P(C.c_int64), A.c_double_p, C.c_double * 3,
+                                                C.c_double * 3, C.c_double]
+            L.rbp_dev_worlds_count.argtypes = [C.c_void_p]
+            L.rbp_dev_worlds_get.argtypes = [C.c_void_p, C.c_int32, P(A.rbp_world)]
+            L.rbp_dev_worlds_download.argtypes = [C.c_void_p, C.c_int32, A.c_float_p]
+            L.rbp_dev_worlds_destroy.argtypes = [C.c_void_p]
+            L.rbp_dev_worlds_destroy.restype = None
+            L.rbp_dev_worlds_ecbs_obstacles.argtypes = [C.c_void_p, C.c_int32, P(A.rbp_mission), P(A.rbp_param), C.c_int32 * 3, P(C.c_uint8), C.c_size_t]
         except AttributeError:
             if not os.environ.get("RBP_HIP_LIB"):
                 raise
@@ -145,6 +153,8 @@ EXPORTED_SYMBOLS = [
     "rbp_session_create_in",
     "rbp_solver_opts_defaults", "rbp_session_set_solver_opts", "rbp_ctx_set_solver_opts", "rbp_session_workspace_bytes", "rbp_session_reserve_workspace",
     "rbp_edt_dims", "rbp_edt_build",
+    "rbp_dev_worlds_create", "rbp_dev_worlds_count", "rbp_dev_worlds_get", "rbp_dev_worlds_download", "rbp_dev_worlds_destroy",
+    "rbp_dev_worlds_ecbs_obstacles",
 ]
 
 
@@ -447,3 +457,92 @@ def build_world(keys, res, param: Param, max_dist=1.0):
     if rc:
         raise RuntimeError(f"rbp_edt_build rc={rc}: {last_error()}")
     return World(dist, tuple(kmin), res)
+
+
+def _box(param: Param):
+    return ((C.c_double * 3)(param.world_x_min, param.world_y_min, param.world_z_min),
+            (C.c_double * 3)(param.world_x_max, param.world_y_max, param.world_z_max))
+
+
+class DeviceWorlds:
+    """rbp_dev_worlds (include/rbp.h): the distance grids of a set of worlds built in one call and kept in HBM.  keys_list / res_list:
+    per world what host.load_octomap returns; the box is param's.  len(), indexing (-> DeviceWorld) and close(); an item keeps the set
+    alive, and a closed set's items must not be used any more.  Every grid equals host.build_world's, bit for bit."""
+
+    def __init__(self, keys_list, res_list, param: Param, max_dist=1.0, device=0):
+        import numpy as np
+        W = len(keys_list)
+        if len(res_list) != W:
+            raise ValueError("keys_list and res_list must have one entry per world")
+        keys = [np.ascontiguousarray(k, np.int32).reshape(-1, 4) for k in keys_list]
+        kp = (A.c_int32_p * max(W, 1))(*[A.ptr(k, A.c_int32_p) for k in keys])
+        nl = (C.c_int64 * max(W, 1))(*[len(k) for k in keys])
+        res = np.ascontiguousarray(res_list, np.float64)
+        lo, hi = _box(param)
+        self._h = C.c_void_p()
+        self.device = int(device)
+        rc = lib().rbp_dev_worlds_create(C.byref(self._h), self.device, W, kp, nl, A.ptr(res, A.c_double_p), lo, hi, max_dist)
+        if rc == A.RBP_ERR_BAD_ARGUMENT:
+            raise ValueError(f"rbp_dev_worlds_create rc={rc}: {last_error()}")
+        if rc:
+            raise RuntimeError(f"rbp_dev_worlds_create rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+        self._items = []
+        for w in range(W):
+            g = A.rbp_world()
+            rc = lib().rbp_dev_worlds_get(self._h, w, C.byref(g))
+            if rc:
+                raise RuntimeError(f"rbp_dev_worlds_get rc={rc}: {last_error()}")
+            self._items.append(DeviceWorld(C.cast(g.dist, C.c_void_p).value, tuple(g.dim), tuple(g.key_min), g.res, self.device, owner=self, index=w))
+
+    def __len__(self):
+        return len(self._items)
+
+    def __getitem__(self, i):
+        if not self._h:
+            raise RuntimeError("DeviceWorlds is closed")
+        return self._items[i]
+
+    def _download(self, w):
+        import numpy as np
+        if not self._h:
+            raise RuntimeError("DeviceWorlds is closed")
+        dist = np.zeros(self._items[w].shape, np.float32)
+        rc = lib().rbp_dev_worlds_download(self._h, w, A.ptr(dist, A.c_float_p))
+        if rc:
+            raise RuntimeError(f"rbp_dev_worlds_download rc={rc}: {last_error()}")
+        return dist
+
+    def close(self):
+        if self._h:
+            lib().rbp_dev_worlds_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ecbs_obstacles(dev_world: DeviceWorld, mission: Mission, param: Param):
+    """host.ecbs_obstacles from a grid that stays on the GPU (rbp_dev_worlds_ecbs_obstacles): one thread per sample of the planning lattice,
+    and the mask [dimx][dimy][dimz] comes back instead of the grid.  `dev_world`: an item of a DeviceWorlds."""
+    from . import host
+    ws = dev_world._owner
+    if not isinstance(ws, DeviceWorlds):
+        raise TypeError("planner.ecbs_obstacles takes an item of a DeviceWorlds (rbp_dev_worlds_ecbs_obstacles addresses a world of a set)")
+    if not ws._h:
+        raise RuntimeError("DeviceWorlds is closed")
+    ms, ps = mission.c_struct(), param.c_struct()
+    rc, mask = host.obstacle_mask(lambda dim, buf, cap: lib().rbp_dev_worlds_ecbs_obstacles(ws._h, dev_world._index, C.byref(ms), C.byref(ps), dim, buf, cap))
+    if rc in host.ECBS_ERROR_TEXT:
+        raise RuntimeError(host.ECBS_ERROR_TEXT[rc])
+    if rc:
+        raise RuntimeError(f"rbp_dev_worlds_ecbs_obstacles rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+    return mask
+
+
+def ecbs_plan(dev_world: DeviceWorld, mission: Mission, param: Param, max_nodes=200000) -> PlanResult:
+    """host.ecbs_plan for a world on the GPU: the obstacle mask from the resident grid, then the host search; same result, same errors."""
+    from . import host
+    return host.ecbs_plan_obstacles(ecbs_obstacles(dev_world, mission, param), mission, param, max_nodes)

@@ -1,0 +1,87 @@
+"""The map sweep of swarm_simulator_amd.test_all (swarm_traj_planner_rbp_test_all.cpp:49-103) on worlds that stay on the device.
+
+With --device-worlds the distance grids of all maps are built on the GPU in one call and stay there (planner.DeviceWorlds): the ECBS
+front-end gets its obstacle mask from the resident grid (planner.ecbs_plan) and both modes plan on it, with the report lines of test_all.
+Without the flag this is test_all itself, argument for argument.
+
+usage: python -m swarm_simulator_amd.sweep_device [--device-worlds] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
+       [--batch-size 4] [--iteration 1] [--joint] [--csv DIR]
+"""
+import argparse
+import time
+
+from . import host, planner, test_all
+from .types import Param
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--device-worlds", action="store_true", help="build all distance grids on the GPU in one call and keep them there")
+    ap.add_argument("--mission", default="mission_64agents_15.json")
+    ap.add_argument("--maps", default="1-50")
+    ap.add_argument("--mode", choices=["serial", "batched"], default="serial")
+    ap.add_argument("--batch-size", type=int, default=4)
+    ap.add_argument("--iteration", type=int, default=1)
+    ap.add_argument("--joint", action="store_true")
+    ap.add_argument("--csv", default=None, help="write coef<qi>.csv per map into DIR/map<i>/ (generateCoefCSV)")
+    args, rest = ap.parse_known_args(argv)
+    if not args.device_worlds:
+        return test_all.main(argv)
+    if rest:
+        ap.error("unrecognized arguments: " + " ".join(rest))
+
+    param = Param.test_sweep(batch_size=args.batch_size, iteration=args.iteration, sequential=not args.joint)
+    mission = host.load_mission(args.mission)
+    maps = test_all.parse_maps(args.maps)
+    t0 = time.perf_counter()
+    octrees = [host.load_octomap(f"map{i}.bt") for i in maps]
+    worlds = planner.DeviceWorlds([o[0] for o in octrees], [o[1] for o in octrees], param)
+    print(f"Euclidean Distmap runtime, {len(maps)} maps in one device build: {time.perf_counter() - t0:.6f}")
+    try:
+        plans = []
+        for n, i in enumerate(maps):
+            print(f"Map: map{i}.bt")
+            w = worlds[n]
+            t0 = time.perf_counter()
+            try:
+                pr = planner.ecbs_plan(w, mission, param)
+            except RuntimeError as e:
+                print(f"[ERROR] {e}")
+                return -1
+            print(f"Initial Trajectory Planner runtime: {time.perf_counter() - t0:.6f}")
+            if args.mode == "serial":
+                t0 = time.perf_counter()
+                cor = planner.Corridor(w, mission, param)
+                if not cor.update(param.log, pr):
+                    print(f"[ERROR] {cor.last_error}")
+                    return -1
+                print(f"BoxGenerator runtime: {time.perf_counter() - t0:.6f}")
+                t0 = time.perf_counter()
+                pl = planner.RBPPlanner(mission, param)
+                if not pl.update(param.log, pr):
+                    print(f"[ERROR] {pl.last_error}")
+                    return -1
+                print(f"SwarmPlanner runtime: {time.perf_counter() - t0:.6f}")
+                test_all.report(i, mission, param, pr, args.csv)
+            plans.append(pr)
+        if args.mode == "batched":
+            sess = planner.Session([worlds[n] for n in range(len(maps))], [mission] * len(plans), param, plans)
+            t0 = time.perf_counter()
+            sess.run()
+            status = sess.download()
+            dt = time.perf_counter() - t0
+            print(f"BoxGenerator + SwarmPlanner runtime, {len(plans)} maps in one session: {dt:.6f} "
+                  f"({len(plans) * mission.qn / dt:.1f} agent-trajectories/s incl. download)")
+            sess.close()
+            for i, p, st in zip(maps, plans, status):
+                if st:
+                    print(f"[ERROR] map{i}: status {st}")
+                    return -1
+                test_all.report(i, mission, param, p, args.csv)
+        return 0
+    finally:
+        worlds.close()
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -3,6 +3,7 @@
 reference: swarm_planner/include/mission.hpp:10-20, param.hpp:7-42, sp_const.hpp:16-28.
 Each object owns numpy buffers and hands out the flat C structs of include/rbp.h.
 """
+import ctypes as C
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -129,6 +130,48 @@ class World:
         w.res = self.res
         w.dist = A.ptr(self.dist, A.c_float_p)
         return w
+
+
+class DeviceWorld:
+    """A distance grid that lives in HBM: rbp_world whose `dist` is a device pointer (include/rbp.h).  Corridor, Context.plan_update and
+    Session take it in place of a World and read the grid where it is.  Items of planner.DeviceWorlds are of this type; from_tensor wraps
+    a caller's own tensor."""
+
+    def __init__(self, ptr, shape, key_min, res, device, owner=None, index=None):
+        self.ptr, self.shape, self.key_min, self.res, self.device = int(ptr), tuple(int(n) for n in shape), tuple(int(k) for k in key_min), float(res), int(device)
+        self._owner, self._index = owner, index   # the DeviceWorlds (or the tensor) that owns the memory: kept alive with this object
+
+    @classmethod
+    def from_tensor(cls, t, key_min, res):
+        """a caller's float32 CUDA tensor [nx][ny][nz] (contiguous) as a world; the tensor is kept alive with the object"""
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.is_contiguous()):
+            raise TypeError("DeviceWorld.from_tensor needs a contiguous float32 CUDA tensor [nx][ny][nz]")
+        return cls(t.data_ptr(), t.shape, key_min, res, t.device.index if t.device.index is not None else torch.cuda.current_device(), owner=t)
+
+    def c_struct(self):
+        w = A.rbp_world()
+        w.dim[:] = list(self.shape)
+        w.key_min[:] = list(self.key_min)
+        w.res = self.res
+        w.dist = C.cast(C.c_void_p(self.ptr), A.c_float_p)
+        return w
+
+    def tensor(self):
+        """zero-copy torch float32 view [nx][ny][nz] of the grid"""
+        import torch
+        if isinstance(self._owner, torch.Tensor):
+            return self._owner
+        holder = type("_View", (), {})()   # __cuda_array_interface__ holder (torch on ROCm reads it like on CUDA)
+        holder.__cuda_array_interface__ = {"shape": self.shape, "typestr": "<f4", "data": (self.ptr, False), "version": 2}
+        holder.keepalive = self
+        return torch.as_tensor(holder, device=torch.device("cuda", self.device))
+
+    def download(self) -> World:
+        """the grid as a host World"""
+        if self._index is not None:
+            return World(self._owner._download(self._index), self.key_min, self.res)
+        return World(self._owner.detach().cpu().numpy(), self.key_min, self.res)
 
 
 class PlanResult:
