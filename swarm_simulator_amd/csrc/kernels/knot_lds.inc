@@ -11,6 +11,8 @@
 //   I  [KL_I]        1 / d_c
 //   MX [NK+1][KL_LD] rows of M = L^-T (row r = column r of L^-1), later overwritten by the rows of the coupling factor X = Cpl M
 //   U  [NK][KL_LDU]  the rank-NK update X D^-1 X' of the next block, MFMA tiles written in the C/D layout; overlays C
+// (Blocks on the fused path -- kl_fused_path(NK), the 36 x 36 blocks --: MX keeps M, X only ever exists as MFMA operands and U not at all, see
+// kl_fused_update; the two lines above describe the column loop and -DKL_FUSED_UPDATE=0.)
 // With M explicit, the coupling factor costs 3 multiply-adds per entry (the coupling block T_{j+1,j} is 3x3-block diagonal) and the
 // substitutions become matrix-vector products instead of 36-step dependent chains.
 //
@@ -19,7 +21,8 @@
 // NK >= KL_PANEL_MIN_NK columns (the 36 x 36 blocks of the flagship missions) take the PANEL path in the second half of this file
 // instead: S and the running inverse live in the accumulators of v_mfma_f64_16x16x4_f64, a step eliminates 4 columns, C holds one
 // small image per panel in place of the column images (knot_panel_layout.h), and I, MX, U and the progress words keep their meaning.
-// tools/ubench/knot.hip times both paths (-DKL_PANEL=0/1) in the product's arrangement; profiles/knot_panel_ubench.txt has the figures.
+// tools/ubench/knot.hip times the paths (-DKL_PANEL=0/1, -DKL_FUSED_UPDATE=0/1) in the product's arrangement; profiles/knot_panel_ubench.txt and
+// profiles/knot_fused_ubench.txt have the figures.
 #pragma once
 #include "knot_panel_layout.h"
 
@@ -385,12 +388,13 @@ __device__ __forceinline__ void kl_panel_row(const KlPivot& f, const kl_d2 s01, 
 }
 
 // S -> upper tiles: entry(mx, mn) returns the element (mx, mn), mx >= mn, of the symmetric NK x NK source (its lower triangle); rows and
-// columns >= NK are the unit diagonal of the padding.  SUB: subtract from the tiles instead.  BOTH: the source holds both triangles
+// columns >= NK are the unit diagonal of the padding.  OP 1: subtract from the tiles instead; OP 2: add to them (the padding is SET all the
+// same: whatever the tiles held there is replaced by the unit diagonal).  BOTH: the source holds both triangles
 // of the diagonal tiles (the LDS images of T_j and U do) -- entry is then called with (column, row) of the tile entry as it stands,
 // which is (mx, mn) above the diagonal and the mirrored, equal element below it: a lane's addresses are one base plus constants,
 // instead of one register per diagonal-tile entry for the lane-dependent choice (the factorisation only consumes entries at and above
 // the diagonal anyway).
-template <int NK, bool SUB, bool BOTH, class F>
+template <int NK, int OP, bool BOTH, class F>
 __device__ __forceinline__ void kl_tiles_load(kl_d4 (&s)[KlPanels<NK>::TILES], int lane, F&& entry) {
     constexpr int NT = KlPanels<NK>::NT;
     const int li = lane & 15, lk = lane >> 4;
@@ -406,8 +410,10 @@ __device__ __forceinline__ void kl_tiles_load(kl_d4 (&s)[KlPanels<NK>::TILES], i
                 const bool pad = !full && (i >= NK || j >= NK);
                 const double v = entry(full || mx < NK ? mx : NK - 1, full || mn < NK ? mn : NK - 1);
                 const int tile = kp_upper(ti, tj, NT);
-                if (SUB)
+                if (OP == 1)
                     s[tile][g] -= pad ? 0.0 : v;
+                else if (OP == 2)
+                    s[tile][g] = pad ? (i == j ? 1.0 : 0.0) : s[tile][g] + v;
                 else
                     s[tile][g] = pad ? (i == j ? 1.0 : 0.0) : v;
             }
@@ -498,10 +504,105 @@ __device__ __forceinline__ bool kl_ldl_panels(kl_d4 (&s)[KlPanels<NK>::TILES], k
 template <int NK, bool T_BOTH, class TF, class LF>
 __device__ __forceinline__ bool kl_knot_panels(TF&& t_entry, LF&& t_loaded, bool minus_u, kl_lds* C, kl_lds* I, int lane, kl_ldsi* P, int pbase) {
     kl_d4 s[KlPanels<NK>::TILES];
-    kl_tiles_load<NK, false, T_BOTH>(s, lane, t_entry);
+    kl_tiles_load<NK, 0, T_BOTH>(s, lane, t_entry);
     t_loaded();
-    if (minus_u) kl_tiles_load<NK, true, true>(s, lane, [&](int mx, int mn) { return (double)C[mx * KL_LDU + mn]; });  // (kl_syrk writes whole diagonal tiles)
+    if (minus_u) kl_tiles_load<NK, 1, true>(s, lane, [&](int mx, int mn) { return (double)C[mx * KL_LDU + mn]; });  // (kl_syrk writes whole diagonal tiles)
     kl_sync();  // (U is read: the panel images overlay it)
+    return kl_ldl_panels<NK>(s, C, I, lane, P, pbase);
+}
+
+// ---- the rank-NK update formed in the tiles (KL_FUSED_UPDATE) --------------------------------------------------------------------------
+// kl_coupling_rows + kl_syrk + the SUB pass above carry the same numbers through the LDS three times: M -> X (rows, over M), X -> U (tiles,
+// stored), U -> S (read back element by element), each hop with its own kl_sync, all of it on the chain.  Here S_next = T - X D^-1 X' is
+// accumulated where the factorisation consumes it: the tiles start at zero, every MFMA operand element X[16 t + li][4 ks + lk] is formed
+// where it is needed from the three rows of M it combines (three ds_read_b64 a row apart: the 16 rows of a tile row fall into 6 groups
+// whose 4 doubles lie on distinct banks -- 3 KL_LD doubles = 36 dwords mod 64 between groups --, the lanes of a group read one address)
+// and the knot's nine coupling coefficients, A = -X and B = X / d go straight into v_mfma_f64_16x16x4_f64, and T is added when its
+// image has arrived (kl_knot_panels_add).  Neither X nor U exists in the LDS, MX keeps M, and the chain wave writes nothing outside the
+// panel images and I: the companion may announce M as soon as its tiles are scattered (kl_inverse_rows).
+#ifndef KL_FUSED_UPDATE
+#define KL_FUSED_UPDATE 1  // 0: the panel path with kl_coupling_rows / kl_syrk, the parent of the A/B in profiles/knot_fused_ubench.txt
+#endif
+__host__ __device__ constexpr bool kl_fused_path(int nk) { return KL_FUSED_UPDATE && kl_panel_path(nk); }
+
+// the coefficients of the rows a lane forms: cf[t][q] multiplies row kp_x_group(16 t + li) + q of M; coef(row, q) returns T_next,this[row][group + q]
+// (coupling_coef of qp.hip).  Rows of the padding get zeros: they contribute nothing, and the tiles' padding stays what kl_tiles_load sets.
+template <int NK, class F>
+__device__ __forceinline__ void kl_fused_coef(double (&cf)[KlPanels<NK>::NT][3], int lane, F&& coef) {
+    const int li = lane & 15;
+#pragma unroll
+    for (int t = 0; t < KlPanels<NK>::NT; ++t) {
+        const int row = KP_T * t + li;
+        const bool in = KP_T * t + KP_T <= NK || row < NK;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const double c = coef(in ? row : 0, q);
+            cf[t][q] = in ? c : 0.0;
+        }
+    }
+}
+
+template <int NK>
+__device__ __forceinline__ void kl_tiles_zero(kl_d4 (&s)[KlPanels<NK>::TILES]) {
+#pragma unroll
+    for (int t = 0; t < KlPanels<NK>::TILES; ++t) s[t] = kl_d4{0, 0, 0, 0};
+}
+
+// s -= X D^-1 X' (upper tiles), X = Cpl M: M rows in MX, 1 / d in I, Cpl in cf (kl_fused_coef).  SKIP: leave out the k-steps in which the
+// B operand is all zeros (27 instead of 54 MFMAs for NK = 36); they multiply exact zeros, so the result has the same bits either way
+template <int NK, bool SKIP = true>
+__device__ __forceinline__ void kl_fused_update(kl_d4 (&s)[KlPanels<NK>::TILES], const kl_lds* MX, const kl_lds* I, int lane, const double (&cf)[KlPanels<NK>::NT][3]) {
+    constexpr int NT = KlPanels<NK>::NT, KS = kp_ksteps(NK);
+    const int li = lane & 15, lk = lane >> 4;
+    const kl_lds* grp[NT];  // M[group of row 16 t + li][lk]: every address below is this plus a constant
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int row = KP_T * t + li;
+        grp[t] = MX + kp_x_group(KP_T * t + KP_T <= NK || row < NK ? row : 0) * KL_LD + lk;
+    }
+    double raw[2][NT][3], dk[2];  // (the loads of a k-step are written one step ahead of their use: see kl_axpy_roll)
+    auto request = [&](int ks) {
+        const bool live = KP_W * ks + KP_W <= NK || KP_W * ks + lk < NK;  // (columns >= NK: the padding of the rows, finite)
+        dk[ks & 1] = I[live ? KP_W * ks + lk : 0];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+            if (!SKIP || ks >= kp_x_first_kstep(t))
+#pragma unroll
+                for (int q = 0; q < 3; ++q) raw[ks & 1][t][q] = grp[t][q * KL_LD + KP_W * ks];
+    };
+    request(0);
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        if (ks + 1 < KS) request(ks + 1);
+        const bool live = KP_W * ks + KP_W <= NK || KP_W * ks + lk < NK;
+        double a[NT], b[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+            if (!SKIP || ks >= kp_x_first_kstep(t)) {
+                const double (&m)[3] = raw[ks & 1][t];
+                const double x = cf[t][0] * m[0] + cf[t][1] * m[1] + cf[t][2] * m[2];  // (the expression of kl_coupling_rows)
+                // entry (i, j) of an upper tile is -sum_k X[i][k] * fl(X[j][k] / d_k): the scaled factor is the one of the LATER row, as in the lower
+                // tiles of kl_syrk that the parent path reads through their mirror image -- the products are exact inside the MFMA, so the tiles
+                // get the bits of T - U
+                a[t] = live ? -x : 0.0;
+                b[t] = live ? x * dk[ks & 1] : 0.0;
+            }
+#pragma unroll
+        for (int tj = 0; tj < NT; ++tj)
+            if (!SKIP || ks >= kp_x_first_kstep(tj))
+#pragma unroll
+                for (int ti = 0; ti <= tj; ++ti)
+                    s[kp_upper(ti, tj, NT)] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ti], b[tj], s[kp_upper(ti, tj, NT)], 0, 0, 0);
+    }
+}
+
+// One knot on the fused path: the tiles hold -X D^-1 X' (kl_tiles_zero, kl_fused_update: before the caller waits for T); T is added,
+// then the factorisation.  t_entry, t_loaded, T_BOTH: see kl_knot_panels.  No kl_sync of its own: the update's reads of MX and I are served
+// before the factorisation's writes to I (one wave, in order), and nothing lies under the panel images.
+template <int NK, bool T_BOTH, class TF, class LF>
+__device__ __forceinline__ bool kl_knot_panels_add(kl_d4 (&s)[KlPanels<NK>::TILES], TF&& t_entry, LF&& t_loaded, kl_lds* C, kl_lds* I, int lane, kl_ldsi* P, int pbase) {
+    kl_tiles_load<NK, 2, T_BOTH>(s, lane, t_entry);
+    t_loaded();
     return kl_ldl_panels<NK>(s, C, I, lane, P, pbase);
 }
 
@@ -561,9 +662,9 @@ __device__ __forceinline__ void kl_inverse_panels(kl_d4 (&n)[KlPanels<NK>::TILES
     }
 }
 
-// N (lower tiles) -> rows of M = N' in MX (zeros below the diagonal are stored; padding lands in row NK), then row r back into m[]
+// N (lower tiles) -> rows of M = N' in MX (zeros below the diagonal are stored; padding lands in row NK)
 template <int NK>
-__device__ __forceinline__ void kl_tiles_to_rows(const kl_d4 (&n)[KlPanels<NK>::TILES], double (&m)[NK], kl_lds* MX, int lane, int r, bool act) {
+__device__ __forceinline__ void kl_tiles_scatter(const kl_d4 (&n)[KlPanels<NK>::TILES], kl_lds* MX, int lane) {
     constexpr int NT = KlPanels<NK>::NT;
     const int li = lane & 15, lk = lane >> 4;
 #pragma unroll
@@ -578,6 +679,10 @@ __device__ __forceinline__ void kl_tiles_to_rows(const kl_d4 (&n)[KlPanels<NK>::
                 MX[in ? row * KL_LD + col : NK * KL_LD + li] = tj <= ti ? n[kp_lower(ti, tj)][g] : 0.0;
             }
     kl_sync();
+}
+// row r of MX back into m[] of lane r
+template <int NK>
+__device__ __forceinline__ void kl_row_load(double (&m)[NK], const kl_lds* MX, int r, bool act) {
     const kl_lds* row = MX + (act ? r : NK) * KL_LD;
 #pragma unroll
     for (int k = 0; k + 1 < NK; k += 2) {
@@ -585,19 +690,37 @@ __device__ __forceinline__ void kl_tiles_to_rows(const kl_d4 (&n)[KlPanels<NK>::
         m[k] = t[0], m[k + 1] = t[1];
     }
     if (NK & 1) m[NK - 1] = row[NK - 1];
-    kl_sync();
 }
 
 // M = L^-T of the block that kl_ldl / kl_ldl_panels factorise(d): row r into m[] of lane r and into MX; returns 1 / d_r.  FOLLOW:
-// concurrently with the factorisation, in a second wave
+// concurrently with the factorisation, in a second wave, which announces *Mdone = done_value once the chain may go on to its next block:
+// MX holds M, and 1 / d has been read (the chain's next block overwrites I).
+// Fused path: the announcement leaves right after the scatter, its kl_sync and the read of 1 / d; the read-back of the row, which only
+// serves the caller's store to global memory, follows it.  That is safe because the chain no longer writes into MX: the next write to
+// MX is THIS wave's scatter of the next block, in program order after the read-back, and the chain's update of the next block reads MX and I
+// before its own factorisation writes I and the panel images that this wave's next scatter waits for.
+// Otherwise the chain overwrites M with X as soon as it is told: the read-back comes first.
 template <int NK, bool FOLLOW>
-__device__ __forceinline__ double kl_inverse_rows(double (&m)[NK], const kl_lds* C, const kl_lds* I, kl_lds* MX, int r, bool act, kl_ldsi* P, int pbase) {
+__device__ __forceinline__ double kl_inverse_rows(double (&m)[NK], const kl_lds* C, const kl_lds* I, kl_lds* MX, int r, bool act, kl_ldsi* P, int pbase,
+                                                  kl_ldsi* Mdone = nullptr, int done_value = 0) {
     if constexpr (kl_panel_path(NK)) {
         kl_d4 n[KlPanels<NK>::TILES];
         kl_inverse_panels<NK, FOLLOW>(n, C, r, P, pbase);
-        kl_tiles_to_rows<NK>(n, m, MX, r, r, act);
+        kl_tiles_scatter<NK>(n, MX, r);
+        if (kl_fused_path(NK)) {
+            if (FOLLOW) kl_await_opaque(P, pbase + NK + 1);
+            const double dinv = I[act ? r : 0];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (keeps the compiler from moving the read below the store; the LDS serves a wave in order)
+            if (FOLLOW) kl_publish(Mdone, done_value);
+            kl_row_load<NK>(m, MX, r, act);
+            return dinv;
+        }
+        kl_row_load<NK>(m, MX, r, act);
+        kl_sync();
         if (FOLLOW) kl_await_opaque(P, pbase + NK + 1);
-        return I[act ? r : 0];
+        const double dinv = I[act ? r : 0];
+        if (FOLLOW) kl_publish(Mdone, done_value);
+        return dinv;
     } else {
 #pragma unroll
         for (int k = 0; k < NK; ++k) m[k] = (k == r) ? 1.0 : 0.0;
@@ -608,6 +731,7 @@ __device__ __forceinline__ double kl_inverse_rows(double (&m)[NK], const kl_lds*
         if (FOLLOW) kl_await_opaque(P, pbase + NK + 1);  // the LAST reciprocal pivot is written after the last image was announced
         const double dinv = I[act ? r : 0];  // (read before the chain is told to go on: its next block overwrites I)
         kl_store_rows<NK>(m, MX, r, act);
+        if (FOLLOW) kl_publish(Mdone, done_value);
         return dinv;
     }
 }

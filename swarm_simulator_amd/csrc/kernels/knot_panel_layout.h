@@ -41,6 +41,13 @@ KP_FN constexpr int kp_panel_reg(int p) { return p % (KP_T / KP_W); }
 // first tile row of S that still changes when panel p is eliminated (the panel's own tile row is finished with its last panel)
 KP_FN constexpr int kp_first_live_tile(int p) { return kp_panel_tile(p + 1); }
 
+// Rank-NK update of the next block formed in the tiles (kl_fused_update): S -= X D^-1 X' with X = Cpl M, Cpl 3x3-block diagonal and
+// M = L^-T upper triangular.  Row r of X combines the three rows kp_x_group(r) .. + 2 of M, so X[r][k] = 0 for k < kp_x_group(r): the rows
+// of tile row t only see the k-steps (4 columns each) from kp_x_first_kstep(t) on, and the upper tile (ti, tj) those of its LATER tile row tj.
+KP_FN constexpr int kp_x_group(int row) { return 3 * (row / 3); }
+KP_FN constexpr int kp_x_first_kstep(int t) { return kp_x_group(KP_T * t) / KP_W; }
+KP_FN constexpr int kp_ksteps(int nk) { return (nk + KP_W - 1) / KP_W; }
+
 // LDS image of the panels (doubles, relative to KlArea::C): panel p holds the padded rows j of S's columns 4p .. 4p+3 as they are when
 // the panels before p have been eliminated, entry (j, k) = S[j][4p + k] -- 32 bytes per row, one ds_read_b128 pair
 KP_FN constexpr int kp_img_doubles(int nk) { return kp_rows(nk) * KP_W; }

@@ -1423,6 +1423,8 @@ __device__ __forceinline__ bool chol_rows(double (&a)[NK], double& dinv) {  // r
 //   X_jn = Cpl M_j                        the coupling factor towards the next knot costs three multiply-adds per entry
 // What a knot leaves in global memory for the substitutions is M_j (row r contiguous, entries k < r are zeros) and 1 / d_j: 5.5 KB of
 // triangle + diagonal instead of the two full blocks (L_j, X_j: 20.7 KB) of the round-2 formulation; X never leaves the LDS.
+// The 36 x 36 blocks (kl_fused_path(NK)) do not store X at all: the chain forms S_j in the MFMA tiles straight from M_jp (kl_fused_update), each
+// operand element of X_j from three rows of M_jp and the knot's nine coupling coefficients, and the companion announces M_j before its read-back.
 #define KF_STRIDE(NK) ((NK) * (NK) + KL_I)  // doubles per knot in QpWs::Lf: M_j [NK][NK], then 1 / d_j
 
 // coefficients of row rr of the coupling block between knot j and the next knot of the chain: T_{j+dir,j}[rr][3g + q], g = rr / 3
@@ -1482,6 +1484,30 @@ __device__ __forceinline__ bool knot_ldl(const QpWs& w, int j, bool minus_u, kl_
     return kl_ldl<NK>(a, C, I, r, act, P, pbase);
 }
 
+// The fused path (kl_fused_path(NK), knot_lds.inc): the caller has accumulated -X_j D_jp^-1 X_j' in the tiles s (kl_fused_update, straight from
+// M_jp in MX: neither X nor U is stored); T_j is added to them and the block factorised.  Timg, consumed: as above.
+template <int NK>
+__device__ __forceinline__ bool knot_ldl_add(const QpWs& w, int j, kl_d4 (&s)[KlPanels<NK>::TILES], kl_lds* base, int r, kl_ldsi* P, int pbase,
+                                             const kl_lds* Timg = nullptr, kl_ldsi* consumed = nullptr, int consumed_value = 0) {
+    using A = KlArea<NK>;
+    kl_lds *C = base + A::C, *I = base + A::I;
+    if (Timg)
+        return kl_knot_panels_add<NK, true>(s, [&](int mx, int mn) { return (double)Timg[mn * KL_LD + mx]; },  // (the images hold both triangles)
+                                            [&] {
+                                                kl_sync();
+                                                if (consumed) kl_publish(consumed, consumed_value);
+                                            },
+                                            C, I, r, P, pbase);
+    const double* Tg = w.Td + (size_t)j * NK * NK;
+    return kl_knot_panels_add<NK, false>(s, [&](int mx, int mn) { return Tg[mn * NK + mx]; }, [] {}, C, I, r, P, pbase);
+}
+// the coupling coefficients of the rows a lane forms in kl_fused_update, towards the knot after j: coupling_coef for the rows 16 t + (lane & 15)
+template <int NK>
+__device__ __forceinline__ void fused_coupling_coef(const QpWs& w, int j, int dir, int lane, double (&cf)[KlPanels<NK>::NT][3]) {
+    const __attribute__((address_space(1))) double* E = QGC(w.Ek) + 9 * (dir > 0 ? j + 1 : j);  // (global loads, see coupling_coef)
+    kl_fused_coef<NK>(cf, lane, [&](int row, int q) { return dir > 0 ? E[3 * q + row % 3] : E[3 * (row % 3) + q]; });
+}
+
 // M = L^-T of the block just factorised: rows into MX (for the coupling factor) and, with 1 / d, into global memory (for the
 // substitutions).  FOLLOW: run by the chain's companion wave concurrently with knot_ldl of the chain wave (kl_inverse_rows: kl_follow_LinvT a
 // column or two behind the chain, or kl_inverse_panels one panel behind it).
@@ -1491,8 +1517,9 @@ __device__ __forceinline__ void knot_inverse(const QpWs& w, int j, kl_lds* base,
     using A = KlArea<NK>;
     kl_lds *C = base + A::C, *MX = base + A::MX, *I = base + A::I;
     double m[NK];
-    const double dinv = kl_inverse_rows<NK, FOLLOW>(m, C, I, MX, r, act, P, pbase);  // (1 / d is read before the chain is told to go on: its next block overwrites I)
-    if (FOLLOW) kl_publish(Mdone, done_value);
+    // (kl_inverse_rows announces *Mdone = done_value as soon as the chain may go on: after the read of 1 / d -- its next block overwrites I --, and on
+    // the fused path BEFORE the read-back of the row that the stores below need)
+    const double dinv = kl_inverse_rows<NK, FOLLOW>(m, C, I, MX, r, act, P, pbase, Mdone, done_value);
     __attribute__((address_space(1))) double* Mg = QG(w.Lf + (size_t)j * KF_STRIDE(NK));
     // (256-thread build: the next block's inputs, sent for a block ago by global_load_lds, are counted on this wave's memory counter; they have
     // long landed -- drain the counter HERE, so that the tiles' wait for them does not have to wait for the row stores below as well)
@@ -1512,18 +1539,30 @@ __device__ __forceinline__ void knot_inverse(const QpWs& w, int j, kl_lds* base,
     }
 }
 
-#if defined(QP_PROFILE) && !defined(QP_LHSTATS) && !defined(QP_SOLVE_TIMERS)  // chain-side timers of the left chain (100 MHz clock, like the phase timers): SC 25 = MFMA update, 26 = waiting for the
-                   // block assembly, 27 = the knot itself (load, factorisation, waiting for M, coupling rows)
+// chain-side timers of the left chain (-DQP_PROFILE; 100 MHz clock, like the phase timers): SC 25 = the rank-NK update, 26 = waiting for the block
+// assembly, 27 = the knot itself (T into the tiles, factorisation, waiting for M; without the fused update also the coupling rows).
+// They must not change what they measure: the time stamp is wave-uniform and stays in scalar registers, a step adds its difference to a
+// 64-bit LDS word behind the progress words (cleared with them at the start of a factorisation; every lane adds, all but lane 0 of the left
+// chain add zero: no branch inside the step), and the three sums go to global memory once per factorisation (CHAIN_FLUSH).
+#if defined(QP_PROFILE) && !defined(QP_LHSTATS) && !defined(QP_SOLVE_TIMERS)
+#define CHAIN_TW(cnt, slot) ((__attribute__((address_space(3))) unsigned long long*)((cnt) + 96) + ((slot) - 25))
 #define CHAIN_T0 long long ct_ = wall_clock64()
-#define CHAIN_T(slot)                                                          \
-    do {                                                                       \
-        const long long t_ = wall_clock64();                                   \
-        if (w.prof && dir > 0 && r == 0) w.prof[slot] += (double)(t_ - ct_);   \
-        ct_ = t_;                                                              \
+#define CHAIN_T(slot)                                                                                                                              \
+    do {                                                                                                                                           \
+        const long long t_ = wall_clock64();                                                                                                       \
+        __hip_atomic_fetch_add(CHAIN_TW(cnt, slot), (dir > 0 && r == 0) ? (unsigned long long)(t_ - ct_) : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
+        ct_ = t_;                                                                                                                                  \
+    } while (0)
+#define CHAIN_FLUSH()                                                                                   \
+    do {                                                                                                \
+        kl_sync();                                                                                      \
+        if (w.prof && dir > 0 && r == 0)                                                                \
+            for (int k_ = 25; k_ < 28; ++k_) w.prof[k_] += (double)(long long)*CHAIN_TW(cnt, k_);       \
     } while (0)
 #else
 #define CHAIN_T0
 #define CHAIN_T(slot)
+#define CHAIN_FLUSH()
 #endif
 // progress words of chain h (LDS ints behind the assembly counters): [2h] = images / pivots published by the chain wave (monotone over
 // the whole factorisation: block i publishes i * (NK + 1) + 1 ...), [2h + 1] = blocks whose M rows the companion wave has put into MX
@@ -1534,7 +1573,8 @@ __device__ __forceinline__ void knot_inverse(const QpWs& w, int j, kl_lds* base,
 
 // one chain: blocks j0, j0+dir, ... (count of them).  The chain wave factorises; its companion wave (wave_factor_follow) computes
 // M_j = L_j^-T a column or two (panel path: one panel of 4 columns) behind and stores it.  On return the chain's LDS area holds the coupling factor X towards the middle
-// block (MX) and the reciprocal pivots of its last block (I): wave_factor_mid reads both chains' areas.
+// block (MX; on the fused path M of the chain's last block instead, once the companion is done) and the reciprocal pivots of its last block (I): wave_factor_mid
+// reads both chains' areas.
 template <int NK>
 __device__ __forceinline__ bool wave_factor_chain(const QpDims& d, const QpWs& w, int j0, int count, int dir, double* ldsW, int* cnt, int h) {
     using A = KlArea<NK>;
@@ -1546,6 +1586,35 @@ __device__ __forceinline__ bool wave_factor_chain(const QpDims& d, const QpWs& w
     const int rr = act ? r : 0;
     bool ok = true;
     int seen = 0, seen_img = 0;
+    if constexpr (kl_fused_path(NK)) {
+        // S_j is formed in the tiles: -X_j D_jp^-1 X_j' from M_jp (MX: the companion's rows, which this wave no longer overwrites) as soon as the
+        // companion has announced them, still in front of the wait for T_j's image; then T_j, then the factorisation.  No coupling rows.
+        double cf[KlPanels<NK>::NT][3];
+        for (int i = 0, j = j0; i < count; ++i, j += dir) {
+            CHAIN_T0;
+            kl_d4 s[KlPanels<NK>::TILES];
+            kl_tiles_zero<NK>(s);
+            if (i > 0) {
+                kl_await(Mdone, i, seen);
+                CHAIN_T(27);
+                kl_fused_update<NK>(s, MX, I, r, cf);
+            }
+            CHAIN_T(25);
+            if (QP_FOLLOW_ASM)
+                kl_await(ASMF_READY(cnt, h), i + 1, seen_img);
+            else
+                wait_blocks(cnt, i);
+            CHAIN_T(26);
+            fused_coupling_coef<NK>(w, j, dir, r, cf);  // (issued here: nine loads from the L2, needed by the NEXT block's update)
+            const kl_lds* Timg = ASM_HELPERS > 0 ? (const kl_lds*)(ldsW - (size_t)h * A::SIZE + 2 * A::SIZE + 128 + (size_t)(h + 2 * (i & 1)) * ASML_DOUBLES(NK, (NK / 9)))
+                                 : QP_FOLLOW_ASM ? (const kl_lds*)(ldsW - (size_t)h * A::SIZE + 2 * A::SIZE + 128 + (size_t)h * ASML_DOUBLES(NK, (NK / 9)))
+                                                 : nullptr;
+            if (!knot_ldl_add<NK>(w, j, s, base, r, P, i * (NK + 1), Timg, ASM_CONSUMED(cnt, h), i + 1)) ok = false;
+            CHAIN_T(27);
+        }
+        CHAIN_FLUSH();
+        return ok;  // (the last block's M is waited for by the workgroup barrier in front of wave_factor_mid)
+    }
     for (int i = 0, j = j0; i < count; ++i, j += dir) {
         CHAIN_T0;
         if (i > 0) kl_syrk<NK>(MX, I, U, r, false);
@@ -1567,6 +1636,7 @@ __device__ __forceinline__ bool wave_factor_chain(const QpDims& d, const QpWs& w
         kl_coupling_rows<NK>(x, MX, r, act, e0, e1, e2);
         CHAIN_T(27);
     }
+    CHAIN_FLUSH();
     return ok;
 }
 
@@ -1579,8 +1649,28 @@ __device__ __forceinline__ bool wave_factor_mid(const QpDims& d, const QpWs& w, 
     const bool act = r < NK;
     const int rr = act ? r : 0;
     int nsy = 0;
-    if (mid > 0) kl_syrk<NK>(bl + A::MX, bl + A::I, bl + A::C, r, false), nsy++;
-    if (mid + 1 < d.nj) kl_syrk<NK>(br + A::MX, br + A::I, bl + A::C, r, nsy > 0), nsy++;
+    [[maybe_unused]] kl_d4 s[kl_fused_path(NK) ? KlPanels<NK>::TILES : 1];
+    if constexpr (kl_fused_path(NK)) {  // both chains' updates into the one set of tiles: the left chain's M with the coefficients towards mid from below, the right chain's from above
+        double cl[KlPanels<NK>::NT][3], cr[KlPanels<NK>::NT][3];
+        if (mid > 0) fused_coupling_coef<NK>(w, mid - 1, +1, r, cl);
+        if (mid + 1 < d.nj) fused_coupling_coef<NK>(w, mid + 1, -1, r, cr);
+        kl_tiles_zero<NK>(s);
+        if (mid > 0) kl_fused_update<NK>(s, bl + A::MX, bl + A::I, r, cl);
+        if (mid + 1 < d.nj) {
+            if (mid > 0) {  // each side summed on its own, then the two sums added: the roundings of U_left + U_right (once per factorisation)
+                kl_d4 s2[KlPanels<NK>::TILES];
+                kl_tiles_zero<NK>(s2);
+                kl_fused_update<NK>(s2, br + A::MX, br + A::I, r, cr);
+#pragma unroll
+                for (int t = 0; t < KlPanels<NK>::TILES; ++t) s[t] += s2[t];
+            } else {
+                kl_fused_update<NK>(s, br + A::MX, br + A::I, r, cr);
+            }
+        }
+    } else {
+        if (mid > 0) kl_syrk<NK>(bl + A::MX, bl + A::I, bl + A::C, r, false), nsy++;
+        if (mid + 1 < d.nj) kl_syrk<NK>(br + A::MX, br + A::I, bl + A::C, r, nsy > 0), nsy++;
+    }
     if (QP_FOLLOW_ASM) {
         int seen_img = 0;
         kl_await(ASMF_READY(cnt, 0), mid + 1, seen_img);  // the left chain's companion makes the middle block after the chain's mid blocks
@@ -1594,7 +1684,11 @@ __device__ __forceinline__ bool wave_factor_mid(const QpDims& d, const QpWs& w, 
     kl_ldsi* scratch = CHAIN_SYNC(cnt, 2);
     const kl_lds* Timg = ASM_HELPERS > 0 ? (const kl_lds*)(ldsL + 2 * A::SIZE + 128 + (size_t)(2 * (cnt_idx & 1)) * ASML_DOUBLES(NK, (NK / 9)))
                          : QP_FOLLOW_ASM ? (const kl_lds*)(ldsL + 2 * A::SIZE + 128) : nullptr;
-    const bool ok = knot_ldl<NK>(w, mid, nsy > 0, bl, r, act, rr, scratch, 0, Timg);
+    bool ok;
+    if constexpr (kl_fused_path(NK))
+        ok = knot_ldl_add<NK>(w, mid, s, bl, r, scratch, 0, Timg);
+    else
+        ok = knot_ldl<NK>(w, mid, nsy > 0, bl, r, act, rr, scratch, 0, Timg);
     if (!QP_MID_FOLLOW) {
         int seen = 0;
         knot_inverse<NK, false>(w, mid, bl, r, act, scratch, 0, seen, scratch, 0);

@@ -3,7 +3,12 @@
 // against a host restatement.  NK = 9, 18, 27, 36; diagonal spreads 1e4 and 1e8 (the spread of an interior-point system).
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I../../swarm_simulator_amd/csrc/kernels -DKL_PANEL=1 -o knot knot.hip && ./knot
 // -DKL_PANEL=0: the column loop (kl_ldl / kl_follow_LinvT) for every NK; -DKL_PANEL=1: the panel path where kl_panel_path(NK) says so
-// (-DKL_PANEL_MIN_NK=9: for every NK).  One workgroup per launch; run it under a time limit of its own.
+// (-DKL_PANEL_MIN_NK=9: for every NK).  On the panel path the rank-NK update of the next block is formed in the MFMA tiles straight from M
+// (kl_fused_update: no coupling rows, no stored X or U, M announced early); -DKL_FUSED_UPDATE=0 is the path with kl_coupling_rows / kl_syrk.
+// Where X is not materialised the check is on the NEXT block's Schur complement T - X D^-1 X' instead (the tiles after the last step's
+// update, with the first step's T standing in for the next block's).  -DUB_T_FIRST=1 (fused path, this tool only): T into the tiles first and
+// the update on top, instead of the update from zero and T added afterwards (what the product does: its update runs before T's image is there).
+// One workgroup per launch; run it under a time limit of its own.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -12,10 +17,15 @@
 
 #include "knot_lds.inc"
 
+#ifndef UB_T_FIRST
+#define UB_T_FIRST 0
+#endif
 constexpr int STEPS = 6;
 
 // timers of the chain wave, cycles per knot step: [0] whole step, [1] syrk, [2] load + factorisation, [3] start of the factorisation ->
 // "M rows are in MX" (what the chain waits for), [4] coupling rows; [5] of the companion wave: its whole step
+// fused path: [1] the update in the tiles, [2] T into the tiles + factorisation, [3] as above, [4] what is left of the chain's wait for M
+// once the factorisation is over (the gap between [2] and [3]); [0] is the sum of [1], [2] and [4]
 struct Timers {
     long long v[8];
 };
@@ -59,6 +69,62 @@ __global__ __launch_bounds__(256) void pair_kernel(const double* T, const double
     const bool act = r < NK;
     const int rr = act ? r : 0;
     long long t_all = 0, t_syrk = 0, t_fac = 0, t_m = 0, t_x = 0;
+    if constexpr (kl_fused_path(NK)) {
+        if (!follower) {  // wave_factor_chain of qp.hip, fused path
+            using KP = KlPanels<NK>;
+            bool ok = true;
+            int seen = 0;
+            double cf[KP::NT][3];
+            kl_d4 s[KP::TILES];
+            const int li = r & 15, lk = r >> 4;
+            // S_i = T_i - X D^-1 X' from block i - 1's M, in two halves around the point where the product waits for T_i's image
+            auto update = [&](int i, bool prev) {
+                const double* Tg = T + (size_t)i * NK * NK;
+                if (UB_T_FIRST)
+                    kl_tiles_load<NK, 0, false>(s, r, [&](int mx, int mn) { return Tg[mn * NK + mx]; });
+                else
+                    kl_tiles_zero<NK>(s);
+                if (prev) kl_fused_update<NK>(s, MX, I, r, cf);
+            };
+            auto add_t = [&](int i) {
+                const double* Tg = T + (size_t)i * NK * NK;
+                if (!UB_T_FIRST) kl_tiles_load<NK, 2, false>(s, r, [&](int mx, int mn) { return Tg[mn * NK + mx]; });
+            };
+            long long c_fac0 = 0;
+            for (int i = 0; i <= STEPS; ++i) {
+                const long long c0 = __builtin_readcyclecounter();
+                if (i > 0) kl_await(Mdone, i, seen);
+                const long long c1 = __builtin_readcyclecounter();
+                if (i > 0) t_m += c1 - c_fac0, t_x += c1 - c0, t_all += c1 - c0;
+                if (i == STEPS) break;  // (the last block's M: in the product the workgroup barrier in front of the middle block waits for it)
+                update(i, i > 0);
+                const long long c2 = __builtin_readcyclecounter();
+                const double* Ei = E + 9 * i;
+                kl_fused_coef<NK>(cf, r, [&](int row, int q) { return Ei[3 * q + row % 3]; });  // T_{j+1,j}[r][3g+q] = E[q][r%3]
+                add_t(i);
+                if (!kl_ldl_panels<NK>(s, C, I, r, P, i * (NK + 1))) ok = false;
+                const long long c3 = __builtin_readcyclecounter();
+                c_fac0 = c2;
+                t_syrk += c2 - c1, t_fac += c3 - c2, t_all += c3 - c1;
+            }
+            // the check: the tiles the NEXT block would factorise, with the first step's T standing in for its T (upper triangle, row-major)
+            update(0, true), add_t(0);
+            if (h == 0) {
+#pragma unroll
+                for (int ti = 0; ti < KP::NT; ++ti)
+#pragma unroll
+                    for (int tj = ti; tj < KP::NT; ++tj)
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            const int row = KP_T * ti + lk + 4 * g, col = KP_T * tj + li;
+                            if (row < NK && col < NK && row <= col) Xo[(size_t)(STEPS - 1) * NK * NK + row * NK + col] = s[kp_upper(ti, tj, KP::NT)][g];
+                        }
+            }
+            if (r == 0 && h == 0) tm->v[0] = t_all / STEPS, tm->v[1] = t_syrk / STEPS, tm->v[2] = t_fac / STEPS, tm->v[3] = t_m / STEPS, tm->v[4] = t_x / STEPS;
+            if (!ok && r == 0) *okflag = 1;
+            return;
+        }
+    }
     if (!follower) {
         bool ok = true;
         int seen = 0;
@@ -87,8 +153,7 @@ __global__ __launch_bounds__(256) void pair_kernel(const double* T, const double
         for (int i = 0; i < STEPS; ++i) {  // knot_inverse<NK, true> of qp.hip
             const long long c0 = __builtin_readcyclecounter();
             double m[NK];
-            const double dinv = kl_inverse_rows<NK, true>(m, C, I, MX, r, act, P, i * (NK + 1));
-            kl_publish(Mdone, i + 1);
+            const double dinv = kl_inverse_rows<NK, true>(m, C, I, MX, r, act, P, i * (NK + 1), Mdone, i + 1);  // (announces M)
             if (act && h == 0) {  // row r of M = L^-T, entries k >= r: pairs, 16 bytes per lane and instruction
                 double* Mr = Mo + (size_t)i * NK * NK + (size_t)r * NK;
                 if ((NK & 1) == 0) {
@@ -126,7 +191,7 @@ static bool run(double spread, bool timing) {
         for (int e = 0; e < 9; ++e) E[9 * i + e] = 3.0 * rnd();
     }
     // host restatement
-    std::vector<double> Mh(STEPS * NK * NK), Xh(STEPS * NK * NK), Dh(STEPS * NK);
+    std::vector<double> Mh(STEPS * NK * NK), Xh(STEPS * NK * NK), Dh(STEPS * NK), Ulast;
     {
         std::vector<double> U(NK * NK, 0.0);
         for (int i = 0; i < STEPS; ++i) {
@@ -167,6 +232,7 @@ static bool run(double spread, bool timing) {
                     U[r * NK + k] = s;
                 }
         }
+        Ulast = U;
     }
     double *dT, *dE, *dM, *dX, *dD;
     Timers* dt;
@@ -195,10 +261,19 @@ static bool run(double spread, bool timing) {
             exit(2);
         }
         ck(hipMemcpy(&h, dt, sizeof(h), hipMemcpyDeviceToHost));
-        if (timing)
+        if (timing && kl_fused_path(NK))
+            printf("NK %d panels, %d chain + companion pair%s: cycles per knot step %lld  (fused update %lld, T + factorisation %lld, factorisation start -> M announced %lld, "
+                   "chain waits for M %lld; companion step %lld)\n",
+                   NK, pairs, pairs > 1 ? "s" : "", h.v[0], h.v[1], h.v[2], h.v[3], h.v[4], h.v[5]);
+        else if (timing)
             printf("NK %d %s, %d chain + companion pair%s: cycles per knot step %lld  (syrk %lld, load + factorisation %lld, factorisation start -> M rows in MX %lld, "
                    "coupling rows %lld; companion step %lld)\n",
                    NK, kl_panel_path(NK) ? "panels" : "columns", pairs, pairs > 1 ? "s" : "", h.v[0], h.v[1], h.v[2], h.v[3], h.v[4], h.v[5]);
+    }
+    if (kl_fused_path(NK)) {  // X is not materialised: the last NK * NK slots hold the next block's Schur complement instead (upper triangle, row-major)
+        const size_t o = (size_t)(STEPS - 1) * NK * NK;
+        for (int r = 0; r < NK; ++r)
+            for (int k = 0; k < NK; ++k) Xh[o + r * NK + k] = k >= r ? T[k * NK + r] - Ulast[r * NK + k] : 0.0;
     }
     std::vector<double> Mg(Mh.size()), Xg(Xh.size()), Dg(Dh.size());
     int okf = 1;
@@ -214,13 +289,13 @@ static bool run(double spread, bool timing) {
     for (size_t i = 0; i < Dh.size(); ++i) ed = fmax(ed, fabs(Dg[i] - Dh[i]) / fabs(Dh[i]));
     // (negated comparisons: a NaN fails)
     const bool pass = hip_ok && !okf && em < 1e-11 * fmax(1.0, sm) && ex < 1e-11 * fmax(1.0, sx) && ed < 1e-12;
-    printf("NK %d spread %.0e: pivots positive: %s   max|M err| %.3g (scale %.3g)  max|X err| %.3g (scale %.3g)  max rel 1/d err %.3g   %s\n", NK, spread,
-           okf ? "NO" : "yes", em, sm, ex, sx, ed, pass ? "ok" : "MISMATCH");
+    printf("NK %d spread %.0e: pivots positive: %s   max|M err| %.3g (scale %.3g)  max|%s err| %.3g (scale %.3g)  max rel 1/d err %.3g   %s\n", NK, spread,
+           okf ? "NO" : "yes", em, sm, kl_fused_path(NK) ? "next S" : "X", ex, sx, ed, pass ? "ok" : "MISMATCH");
     return pass;
 }
 
 int main() {
-    printf("KL_PANEL=%d KL_PANEL_MIN_NK=%d; LDS per chain wave (NK 36): %d doubles = %.1f KB\n", KL_PANEL, KL_PANEL_MIN_NK, KlArea<36>::SIZE, KlArea<36>::SIZE * 8 / 1024.0);
+    printf("KL_PANEL=%d KL_PANEL_MIN_NK=%d KL_FUSED_UPDATE=%d UB_T_FIRST=%d; LDS per chain wave (NK 36): %d doubles = %.1f KB\n", KL_PANEL, KL_PANEL_MIN_NK, KL_FUSED_UPDATE, UB_T_FIRST, KlArea<36>::SIZE, KlArea<36>::SIZE * 8 / 1024.0);
     bool pass = true;
     for (double spread : {1e4, 1e8}) {
         const bool timing = spread == 1e4;
