@@ -87,7 +87,7 @@ struct rbp_session {
     size_t qp_ws_per_mission = 0;
     char* ws_own = nullptr;
     bool ws_joint = false;    // what the workspace was laid out for
-    int bs = 1, biter = 0;    // batch schedule of the plan (setBatch, rbp_planner.hpp:849-872)
+    int bs = 1, biter = 0;    // batch schedule of the plan (batch_schedule, kernels/rbp_dev.h)
     std::vector<int> Mk, MBk;         // per-mission segments / box capacity (host copy of DevSession::Mk, MBk)
     std::vector<DevWorld> worlds_h;
     // planner-stage inputs as uploaded, in device layout (so that a run which overwrote them can be reset)
@@ -182,17 +182,6 @@ static int check_solver_opts(const rbp_solver_opts* o) {
 
 static size_t al(size_t n) { return ((n + 255) & ~size_t(255)) + 256; }
 
-// effective batch size and number of batches solved per pass (setBatch, rbp_planner.hpp:849-872; the loop of :142)
-static void batch_schedule(const rbp_param& p, int N, int* bs_out, int* biter_out) {
-    int bs = p.sequential ? p.batch_size : N;
-    if (bs <= 0) bs = 1;
-    if (bs > N) bs = N;
-    const int bmax = (N + bs - 1) / bs;
-    int biter = p.sequential ? p.batch_iter : 1;
-    if (p.sequential && (biter < 0 || biter > bmax)) biter = bmax;
-    *bs_out = bs, *biter_out = biter;
-}
-
 static int session_create_impl(rbp_session** out, int device, int K, const rbp_world* worlds, const rbp_mission* missions,
                                const rbp_param* param, const rbp_plan* plans, rbp_ctx* ctx) {
     if (!out || K <= 0 || !worlds || !missions || !param || !plans) return fail(RBP_ERR_BAD_ARGUMENT, "null argument");
@@ -225,8 +214,8 @@ static int session_create_impl(rbp_session** out, int device, int K, const rbp_w
         if (!(ext >= 0) || std::ceil(ext / res) + 3 > SFC_MAXS)
             return fail(RBP_ERR_BAD_ARGUMENT, "world extent / box resolution exceeds the SFC sample cache (" + std::to_string(SFC_MAXS - 3) + " steps per axis)");
     }
-    int bs = 1, biter = 0;
-    batch_schedule(*param, N, &bs, &biter);
+    const BatchSchedule sched = batch_schedule(param->sequential, param->batch_size, param->batch_iter, N);
+    const int bs = sched.bs, biter = sched.biter;
 
     struct Guard {  // every error path below releases the session (and with it the arena)
         rbp_session* s;
@@ -693,8 +682,8 @@ int rbp_session_download(rbp_session* s, rbp_plan* plans, int32_t* status, void*
     DN(stat.data(), d.status, sizeof(int) * K);
     DN(sc.data(), d.scalars, sizeof(double) * K * SC_N);
     int first = 0;
-    int bs = 1, biter = 0;
-    batch_schedule(s->param, N, &bs, &biter);
+    const BatchSchedule sched = batch_schedule(s->param.sequential, s->param.batch_size, s->param.batch_iter, N);
+    const int bs = sched.bs, biter = sched.biter;
     for (int k = 0; k < K; ++k) {
         rbp_plan& p = plans[k];
         const int Mq = s->Mk[k], Pq = Mq + 1, oqq = 6 * Mq, MBq = s->MBk[k];

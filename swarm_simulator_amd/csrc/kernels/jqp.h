@@ -73,7 +73,5 @@ struct JointOpts {  // what rbp_solver_opts says about the grid-wide joint solve
 
 JLayout jq_layout(int N, int MS);
 size_t joint_workspace_bytes(int N, int MS);
-// dummy_kernel .. timescale_kernel around it are launched by the caller (launch_planner_prologue / _epilogue in qp.hip)
+// dummy_kernel .. timescale_kernel around it are launched by the caller (launch_planner_prologue / _epilogue, kernels/traj.hip)
 int launch_planner_joint(const DevSession& s, void* ws, hipStream_t st, JointStats* stats, const JointOpts& opts);
-void launch_planner_prologue(const DevSession& s, hipStream_t st);
-void launch_planner_epilogue(const DevSession& s, hipStream_t st);

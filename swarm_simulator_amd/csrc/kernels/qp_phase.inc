@@ -231,8 +231,8 @@ __global__ __launch_bounds__(QP_THREADS, QP_WAVES_PER_EU) void ph_advance(DevSes
             if ((pres < 1e-9 && dres < 1e-9 && mu < 1e-10) || (pres < 1e-6 && dres < 1e-9 && mu < 1e-13) || (pres < 1e-9 && dres < 1e-7 && mu < 1e-14)) {
                 finished = true;  // (the three exits of qp_batch_body)
             } else {
-                const bool polish_first = QP_POLISH_FIRST && st.pass > 0 && st.iter == 0;
-                const bool early = QP_EARLY_POLISH && st.early_tries < QP_EARLY_TRIES && pres < QP_EARLY_TOL && dres < QP_EARLY_TOL &&
+                const bool polish_first = st.pass > 0 && st.iter == 0;
+                const bool early = st.early_tries < QP_EARLY_TRIES && pres < QP_EARLY_TOL && dres < QP_EARLY_TOL &&
                                    mu < (st.early_tries == 0 ? QP_EARLY_TOL : 1e-2 * QP_EARLY_TOL);
                 if (S.p.polish && (polish_first || early)) {
                     if (!polish_first) st.early_tries++;

@@ -47,23 +47,12 @@ __device__ __forceinline__ double red_op(double a, double b, int op) { return op
 __device__ __forceinline__ double rl_const(double v, int lane) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
 }
-#ifndef LH_NEW_RED
-#define LH_NEW_RED 1
-#endif
-#ifndef LH_NEW_GRAD
-#define LH_NEW_GRAD 1
-#endif
 __device__ __forceinline__ double wave_red(double v, int op /*0 sum,1 max,2 min*/) {
-#if LH_NEW_RED
     v = red_op(v, dpp_f64<0xB1>(v), op);   // quad_perm [1,0,3,2]
     v = red_op(v, dpp_f64<0x4E>(v), op);   // quad_perm [2,3,0,1]
     v = red_op(v, dpp_f64<0x141>(v), op);  // row_half_mirror
     v = red_op(v, dpp_f64<0x140>(v), op);  // row_mirror: every lane of a row holds the row's result
     return red_op(red_op(rl_const(v, 0), rl_const(v, 16), op), red_op(rl_const(v, 32), rl_const(v, 48), op), op);
-#else
-    for (int o = 32; o > 0; o >>= 1) v = red_op(v, __shfl_xor(v, o), op);
-    return v;
-#endif
 }
 __device__ __forceinline__ int wave_min_int(int v) {
     v = min(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false));
@@ -75,17 +64,9 @@ __device__ __forceinline__ int wave_min_int(int v) {
 }
 // the largest `best` of the wave and, among the lanes that hold it, the smallest index (-1: no lane has a candidate)
 __device__ __forceinline__ void wave_argmax(double& best, int& bidx) {
-#if LH_NEW_RED
     const double top = wave_red(bidx >= 0 ? best : -1e300, 1);
     const int idx = wave_min_int(bidx >= 0 && best == top ? bidx : 0x7fffffff);
     best = top, bidx = idx == 0x7fffffff ? -1 : idx;
-#else
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bidx, o);
-        if (oi >= 0 && (bidx < 0 || ob > best || (ob == best && oi < bidx))) best = ob, bidx = oi;
-    }
-#endif
 }
 
 __device__ __forceinline__ void knot_of(const QpDims& d, const QpWs& w, int j6, int& knot, double t[3]) {
@@ -191,9 +172,7 @@ __device__ void k0_factor3(const QpDims& d, const QpWs& w, double* f3, int* flag
 // per knot, every one of the 2 nj steps paid a trip to memory (the next knot's load may not pass this knot's store), 70 trips of 3-5 us under
 // load for a few dozen multiply-adds each.  Now the knots travel in BLOCKS of K0_BLK: the next block is requested before the current one is
 // worked on (second register set, first touched after the block), results leave per block -- a dozen trips.  Same arithmetic, same order.
-#ifndef K0_BLK
-#define K0_BLK 6
-#endif
+constexpr int K0_BLK = 6;
 __device__ __forceinline__ void k0_solve3(const double* f3g, int nj, int nk, double* col, int sub) {
     typedef __attribute__((address_space(1))) double gdb;
     const kl_lds* f3 = (const kl_lds*)f3g;  // (the factor is in LDS)
@@ -313,7 +292,7 @@ __device__ __forceinline__ double rl_dyn(double v, int lane) {
 #include "lh_inverse.inc"  // the dual solve's linear algebra: products with the inverse factor W = L^-1 of S_PP
 
 // Lawson-Hanson on  min 1/2 z'Sz - d'z, z >= 0  (n <= PL_NC candidates).  Wave 0 only.  returns nP, or -1 on failure.
-// resume_nP >= 0 (round 6, LH_RESUME): the candidate set has GROWN since the previous call (rows outside it came out violated) -- the old
+// resume_nP >= 0 (round 6): the candidate set has GROWN since the previous call (rows outside it came out violated) -- the old
 // candidates keep their indices, their S entries and their d, so the factor W, the active set P and W d_P the previous call ended with are
 // still what they were: the iteration goes on from there (n_prev: candidates of the previous call) instead of appending the ~60 active rows
 // again one by one, which was half of all the appends of a mission.  shared_int[1] carries "W d_P is valid" from one call to the next.
@@ -374,7 +353,6 @@ __device__ int lh_wave(int n, const double* Sg, int ldS, const double* dv, doubl
                 if (nP == 0) continue;
             }
         } else {
-#if LH_NEW_GRAD
             // g = d - S[:, P] z_P for every candidate.  Lane l owns candidates l, l + 64, ... (an accumulator each); the active
             // rows are walked together: their index and multiplier travel by readlane from per-lane copies, so the S loads of four
             // rows x four candidates are in flight at once and nothing but the multiply-adds is dependent.  (One candidate at a time
@@ -409,24 +387,6 @@ __device__ int lh_wave(int n, const double* Sg, int ldS, const double* dv, doubl
                     if (!inP[a] && !banned[a] && s > best) best = s, bidx = a;
                 }
             }
-#else
-            for (int a = lane; a < n; a += 64) {
-                double s = dv[a], q0 = 0, q1 = 0, q2 = 0, q3 = 0;  // four partial sums: a single one is a chain of nP dependent
-                for (int b0 = 0; b0 < nP; b0 += 8) {                // operations; eight loads in flight
-                    double sv[8], zv[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int pb = b0 + u < nP ? P[b0 + u] : -1;
-                        sv[u] = pb >= 0 ? Sg[(size_t)pb * ldS + a] : 0.0;
-                        zv[u] = pb >= 0 ? zc[pb] : 0.0;
-                    }
-                    q0 += sv[0] * zv[0], q1 += sv[1] * zv[1], q2 += sv[2] * zv[2], q3 += sv[3] * zv[3];
-                    q0 += sv[4] * zv[4], q1 += sv[5] * zv[5], q2 += sv[6] * zv[6], q3 += sv[7] * zv[7];
-                }
-                s -= (q0 + q1) + (q2 + q3);
-                if (!inP[a] && !banned[a] && s > best) best = s, bidx = a;
-            }
-#endif
             wave_argmax(best, bidx);
             if (stats && lane == 0) { const long long t_ = wall_clock64(); stats[0] += (double)(t_ - lt0); lt0 = t_; stats[4] += 1.0; }
             if (bidx < 0) break;
@@ -714,11 +674,8 @@ __device__ __forceinline__ int polish_qp(RowCtx& c, PassIO& io, const PolishWs& 
         // (rows outside the candidate set came out violated and joined it) starts from the active set the previous round ended with --
         // zc still holds it (multiplier > 0) -- instead of from nothing: without it every such round repeated the whole build-up, one gradient pass
         // and one solve per row
-#ifndef LH_REWARM
-#define LH_REWARM 1
-#endif
         for (int ci = tid; ci < n; ci += QP_THREADS)
-            str[ci] = outer == 0 ? pw.cand[ci].strength : (LH_REWARM && ci < n_prev && zc[ci] > 0 ? 1e3 + zc[ci] : 0.0);
+            str[ci] = outer == 0 ? pw.cand[ci].strength : (ci < n_prev && zc[ci] > 0 ? 1e3 + zc[ci] : 0.0);
         __threadfence_block();
         __syncthreads();
         // the dual solve reads S a few thousand times with a dependent access pattern: keep it in LDS when it fits
@@ -736,14 +693,11 @@ __device__ __forceinline__ int polish_qp(RowCtx& c, PassIO& io, const PolishWs& 
         // ---- dual active-set solve (wave 0)
         if (tid < 64) {
             __builtin_amdgcn_s_setprio(QP_CHAIN_PRIO);  // one wave, one dependent chain (see twisted_factor in qp.hip)
-#ifndef LH_RESUME
-#define LH_RESUME 1
-#endif
-            const int res_nP = (LH_RESUME && outer > 0 && nP > 0) ? nP : -1;
+            const int res_nP = (outer > 0 && nP > 0) ? nP : -1;
 #ifdef QP_LHSTATS
-            const int r = lh_wave(n, Suse, ldS, dv, zc, tv, yv, wv, P, inP, banned, Lc, sint + 2, pmax, outer == 0 || LH_REWARM ? str : nullptr, big, c.scal + 20, res_nP, n_prev);
+            const int r = lh_wave(n, Suse, ldS, dv, zc, tv, yv, wv, P, inP, banned, Lc, sint + 2, pmax, str, big, c.scal + 20, res_nP, n_prev);
 #else
-            const int r = lh_wave(n, Suse, ldS, dv, zc, tv, yv, wv, P, inP, banned, Lc, sint + 2, pmax, outer == 0 || LH_REWARM ? str : nullptr, big, nullptr, res_nP, n_prev);
+            const int r = lh_wave(n, Suse, ldS, dv, zc, tv, yv, wv, P, inP, banned, Lc, sint + 2, pmax, str, big, nullptr, res_nP, n_prev);
 #endif
             __builtin_amdgcn_s_setprio(0);
             if (tid == 0) sint[1] = r;
@@ -898,16 +852,9 @@ __device__ __forceinline__ T uni_words(const T& v) {
 }
 __device__ __noinline__ int polish_entry(RowCtx c_in, PolishWs pw_in, double* lds, double* red, int* flag, int mode) {
     PassIO io = {};
-#if QP_UNI_POLISH
     RowCtx c = uni_words(c_in);
     PolishWs pw = uni_words(pw_in);
     c.pw = &pw;
     return polish_qp(c, io, pw, uni(lds), uni(red), uni(flag), uni(mode));
-#else
-    RowCtx c = c_in;
-    PolishWs pw = pw_in;
-    c.pw = &pw;
-    return polish_qp(c, io, pw, lds, red, flag, mode);
-#endif
 }
 #endif

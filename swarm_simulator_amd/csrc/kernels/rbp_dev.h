@@ -86,11 +86,38 @@ enum { SC_TIME_SCALE = 0, SC_TOTAL_COST = 1, SC_IPM_ITERS = 2, SC_QP_SOLVED = 3,
        SC_N = 36 };
 enum { CT_SFC_SAMPLES = 0, CT_N = 4 };
 
+// effective batch size and number of batches solved per pass (setBatch, rbp_planner.hpp:849-872; the loop of :142)
+struct BatchSchedule {
+    int bs, biter;
+};
+inline BatchSchedule batch_schedule(int sequential, int batch_size, int batch_iter, int N) {
+    int bs = sequential ? batch_size : N;
+    if (bs <= 0) bs = 1;
+    if (bs > N) bs = N;
+    const int bmax = (N + bs - 1) / bs;
+    int biter = sequential ? batch_iter : 1;
+    if (sequential && (biter < 0 || biter > bmax)) biter = bmax;
+    return {bs, biter};
+}
+
+// build_dummy (rbp_planner.hpp:513-549): control point j of segment m of the waypoint-constant trajectory, dimension k, from one agent's
+// waypoints tr[M + 1][3] -- the first three of a segment sit on its first waypoint, the last three on its second.
+// (idx runs with m, one waypoint pair per segment; the `idx >= size-1` branch is unreachable for M+1 waypoints)
+__device__ __forceinline__ double dummy_ctrl_point(const float* tr, int m, int j, int k) {
+#pragma clang fp contract(fast)  // as in its callers' files (the Makefile's -ffp-contract=off is for corridor.hip): one fused multiply-add
+    const int a = (j < 3) ? 0 : 1;
+    return (1 - a) * (double)tr[3 * m + k] + a * (double)tr[3 * (m + 1) + k];
+}
+
 int rbp_set_error(int code, const char* msg);  // abi/session.hip: records the message rbp_last_error() returns, returns code
 
 // launchers (defined in the .hip files)
 int launch_corridor(const DevSession& s, hipStream_t st);
 size_t corridor_lds_bytes(const DevSession& s);  // dynamic LDS of sfc_kernel for this session's shapes
+// kernels/traj.hip: build_dummy in front of a QP solve of either kind (batch: kernels/qp.hip, joint: kernels/jqp.hip), Bernstein -> monomial
+// + timeScale behind it
+void launch_planner_prologue(const DevSession& s, hipStream_t st);
+void launch_planner_epilogue(const DevSession& s, hipStream_t st);
 // kernels/qp.hip is built twice: _w2 = 256 VGPRs, one workgroup per CU; _w4 = 128 VGPRs, two workgroups per CU
 void launch_planner_w2(const DevSession& s, void* qp_ws, size_t qp_ws_bytes_per_mission, hipStream_t st);
 void launch_planner_w4(const DevSession& s, void* qp_ws, size_t qp_ws_bytes_per_mission, hipStream_t st);

@@ -3,7 +3,7 @@
 roots_derivative (rbp_planner.hpp:727-754) inspects the first i = 2 of the three eigenvalues of the companion matrix of the velocity's
 derivative, in the order Eigen's EigenSolver returns them (:746-751).  Rule 0 (default) takes ALL real roots; rule 1 takes the first two
 eigenvalues in the order of Eigen 3.3's real Schur decomposition, restated from the published algorithm in oracle/planner.c (C, element-wise)
-and -- independently, with whole-matrix reflections -- in tests/golden/make_kkt_reference.py (numpy), and in kernels/qp.hip (the product).
+and -- independently, with whole-matrix reflections -- in tests/golden/make_kkt_reference.py (numpy), and in kernels/traj.hip (the product).
 
 CPU: the two restatements agree on random polynomials and on the 50-map sweep (64 agents, batch 4) with max_vel / max_acc scaled by
 1, 0.5 and 0.25; how often the rules differ is recorded.  GPU (-m gpu): the product's timescale_kernel gives the oracle's factor under BOTH

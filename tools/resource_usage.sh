@@ -20,6 +20,7 @@ one() {  # name, source, extra flags
   one "build _w2 (-DQP_WAVES_PER_EU=2 -DQP_ROW_PF=4 -DQP_SUFFIX=_w2)" kernels/qp.hip "-DQP_WAVES_PER_EU=2 -DQP_ROW_PF=4 -DQP_SUFFIX=_w2"
   one "build _w4 (-DQP_THREADS=256 -DQP_WAVES_PER_EU=2 -DQP_SUFFIX=_w4)" kernels/qp.hip "-DQP_THREADS=256 -DQP_WAVES_PER_EU=2 -DQP_SUFFIX=_w4"
   one "(every jq_* / jp_* kernel of the grid-wide joint solver)" kernels/jqp.hip ""
+  one "(build_dummy, Bernstein -> monomial, timeScale)" kernels/traj.hip ""
   one "" kernels/corridor.hip ""
   one "" kernels/edt.hip ""
 } > $OUT
