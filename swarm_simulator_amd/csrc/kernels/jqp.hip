@@ -25,7 +25,9 @@
 //     middle knot): half the dependent depth, the two chains share every launch;
 //   * SUBSTITUTIONS are matrix-vector products with the stored inverses (16-row slabs, one launch per knot step and direction).
 //   * two SCHEDULES of that sweep: look-ahead as described (few missions: the dependent chain is what counts) and bulk (eight or more
-//     resident missions: jq_update_bulk without LDS at three workgroups per CU, the pivot inverse in a launch of its own);
+//     resident missions: jq_update_bulk without LDS at three workgroups per CU, the pivot inverse in a launch of its own).  The sweep -- its
+//     context, the pivot inverse, the kernels of every schedule -- is jqp_tile.inc, with ONE copy of each tile operation for all schedules
+//     (tri_tile, sym_tile, panel_rows, quad_load / quad_mac / quad_store, edge_copy, pivot_thresholds; sweep_open opens every kernel);
 //   * on top of Mehrotra's direction ONE centrality corrector per iteration (Gondzio) on the factorisation already paid for, and a
 //     SAFEGUARD that takes back a step which loses the dual residual after an acceptable iterate (explicit inverses at Newton weights
 //     of 1e9: see jq_ctrl(1));
@@ -870,28 +872,9 @@ __device__ __forceinline__ Chain chain_step(const JDims& d, int chain, int s, bo
     }
     return c;
 }
-// ping-pong buffers of the sweep: X[0] = the knot's slot in `inv`, X[1] = the chain's scratch; pass t reads X[(t + p0) & 1] and writes
-// the other; p0 = (number of passes) & 1 makes the last pass land in X[0]
-__device__ __forceinline__ int sweep_parity0(const JArgs& A, int nblk) { return (A.sweep2 ? (nblk + 1) / 2 : nblk) & 1; }
-__device__ __forceinline__ double* sweep_buf(const Ws& w, const JDims& d, const JLayout& L, int chain, int jj, int which) {
-    return which == 0 ? w.inv + (size_t)jj * L.nkpS * L.nkpS : w.scr + (size_t)chain * L.nkpS * L.nkpS;
-}
 
-// what a sweep kernel works on: kind 0 = the Schur complement of a knot (step s of a chain / the middle knot), kind 1 = the polish's
-// S_AA (jqp_polish.inc; order and buffers from the mission's polish record)
-struct SweepCtx {
-    bool active;
-    int nblk;
-    const double* src;  // X[(k + p0) & 1]
-    double* dst;        // X[(k + p0 + 1) & 1]
-    double* Pk;         // pivot inverse of step k
-    double* Pn;         // ... of step k + 1 (look-ahead)
-    double* P2;         // double step (k, k + 1): the three tiles P00, P10, P11 of the pivot block's inverse
-    double* Y;          // panel (double step: two tiles per block row)
-    double* bad;        // counter of non-positive pivots
-    const double* G;    // polish (kind 1): the matrix before the sweep (tile-major): its diagonal scales the deletion threshold; else nullptr
-};
-__device__ __forceinline__ SweepCtx sweep_ctx(const JArgs& A, const Ws& w, const JDims& d, int kind, int s, int mid, int k, int chain);
+// the blocked symmetric sweep: SweepCtx, the pivot tile's inverse, the shared tile operations and the sweep kernels of all three schedules
+#include "jqp_tile.inc"
 
 // T_jj + Schur updates, written into the first sweep buffer (tiles I >= J).  One thread per 3x3 block (Ai, Bi) = ((a, k), (b, l)).
 __global__ __launch_bounds__(256) void jq_prep(JArgs A, int s, int mid) {
@@ -986,709 +969,6 @@ __global__ __launch_bounds__(256) void jq_prep(JArgs A, int s, int mid) {
             const int r = 3 * Ai + e, cc = 3 * Bi + f;
             if ((r >> 6) >= (cc >> 6)) X[telem(nblk, r, cc)] = out[3 * e + f];
         }
-}
-
-// ---- 64 x 64 SPD inverse in LDS (256 threads): the same blocked sweep one level down, 16 x 16 sub-tiles on the MFMA, the diagonal
-// sub-tile by Gauss-Jordan with the rows in lanes (v_readlane broadcasts).  In: Am = the SPD tile, leading dimension LDA.
-// Out: Am = -(tile)^-1.  *bad is set when a pivot is not positive.
-constexpr int LDA = 66;  // (ds_read_b64 of lane (i, g) at row i, column 4 kk + g: conflict free with 66)
-__device__ __forceinline__ double rl(double v, int lane) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-constexpr size_t JQ_UPDATE_LDS_EXTRA = 64 * sizeof(double) + 16;  // thr[JT] + the bad-pivot flag behind Am and the scratch
-struct InvScratch {
-    double Pi[4][16 * 18];  // per wave: its copy of the diagonal sub-tile, inverted in place
-    double Yb[4][16 * 18];
-    // (Z of wave w lives in Pi[w]: a wave is done with its copy of the pivot sub-tile when it stores Z, only wave kk's copy is needed
-    // afterwards and wave kk stores no Z -- 9 KB less, which lets a third workgroup of jq_update onto a CU)
-};
-#define JQ_WSYNC()                                             \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                       \
-    } while (0)
-// 16 x 16 Gauss-Jordan inverse in LDS by ONE wave, in place (leading dimension 18): lane (r = l & 15, g = l >> 4) owns the entries
-// D[r][4g .. 4g+3] in registers and publishes them after every column step; what a step needs from other lanes -- the pivot, the
-// pivot row's segment, the row's entry in the pivot column -- are same-address LDS reads (broadcasts: ~7 cycles per 8 bytes, no
-// v_readlane chains).  LDS serves a wave's operations in order, so a step's reads see the previous step's writes.
-// thr (or nullptr): per column, the pivot size at or below which the row is DELETED from the solve instead of eliminated: row and column
-// become zero, i.e. the result is the inverse of the matrix without that row, with a zero row and column in its place.  The polish uses it
-// for active rows that are linear combinations of the rows before them (five control points around a knot are functions of three
-// variables: a trajectory that runs along a box face makes four or five bound rows of one agent and axis active at once); everything
-// downstream of a zero column of the pivot inverse -- panel, update, the other sub-tiles -- stays zero by the sweep's own algebra.
-__device__ __forceinline__ bool gj16_lds(double* D, int lane, const double* thr = nullptr) {
-    const int r = lane & 15, g = lane >> 4;
-    double v[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = D[r * 18 + 4 * g + q];
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const double p = D[c * 18 + c], f = D[r * 18 + c];
-        double pr[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) pr[q] = D[c * 18 + 4 * g + q];
-        if (thr && p <= thr[c]) {  // (wave-uniform)
-            if (r == c) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = 0.0;
-            }
-            if (g == c / 4) v[c % 4] = 0.0;
-        } else {
-            ok = ok && (p > 0.0);
-            const double ip = fast_rcp(p), fi = f * ip;
-            if (r == c) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = pr[q] * ip;
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] -= fi * pr[q];
-            }
-            if (g == c / 4) v[c % 4] = r == c ? ip : -fi;
-        }
-        JQ_WSYNC();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) D[r * 18 + 4 * g + q] = v[q];
-        JQ_WSYNC();
-    }
-    return ok;
-}
-__device__ __forceinline__ void inv64_lds_inl(double* Am, InvScratch* sc, int* bad, const double* thr = nullptr) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lg = lane >> 4;
-    for (int kk = 0; kk < 4; ++kk) {
-        // every wave inverts its own copy of the diagonal sub-tile (no barrier between the inversion and the wave's panel product)
-        double* Pi = sc->Pi[wave];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) Pi[li * 18 + 4 * lg + q] = Am[(16 * kk + li) * LDA + 16 * kk + 4 * lg + q];
-        JQ_WSYNC();
-        const bool okp = gj16_lds(Pi, lane, thr ? thr + 16 * kk : nullptr);
-        if (!okp && tid == 0) *bad = 1;
-        // panel: row block i = wave: Z = A[i][kk] (old), Y = Z Pi'
-        if (wave != kk) {
-            d4 acc = d4{0, 0, 0, 0};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const double av = Am[(16 * wave + li) * LDA + 16 * kk + 4 * q + lg];
-                const double bv = Pi[li * 18 + 4 * q + lg];
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                sc->Yb[wave][(lg + 4 * r) * 18 + li] = acc[r];
-                sc->Pi[wave][(lg + 4 * r) * 18 + li] = Am[(16 * wave + lg + 4 * r) * LDA + 16 * kk + li];
-            }
-        }
-        __syncthreads();
-        // update: row block i = wave, all four column blocks
-        for (int jb = 0; jb < 4; ++jb) {
-            double* At = Am + (16 * wave) * LDA + 16 * jb;
-            if (wave == kk && jb == kk) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) At[(lg + 4 * r) * LDA + li] = -Pi[(lg + 4 * r) * 18 + li];
-            } else if (jb == kk) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) At[(lg + 4 * r) * LDA + li] = sc->Yb[wave][(lg + 4 * r) * 18 + li];
-            } else if (wave == kk) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) At[(lg + 4 * r) * LDA + li] = sc->Yb[jb][li * 18 + lg + 4 * r];
-            } else {
-                d4 acc = d4{0, 0, 0, 0};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const double av = sc->Yb[wave][li * 18 + 4 * q + lg];
-                    const double bv = sc->Pi[jb][li * 18 + 4 * q + lg];
-                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) At[(lg + 4 * r) * LDA + li] -= acc[r];
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// (out of line for the pivot kernels, which have a CU to themselves; jq_update inlines it so that ITS register budget applies)
-__device__ void inv64_lds(double* Am, InvScratch* sc, int* bad, const double* thr = nullptr) { inv64_lds_inl(Am, sc, bad, thr); }
-
-// Pbuf[chain][parity] <- symmetrised inverse of the SPD tile held (as its NEGATED inverse after inv64_lds) in Am
-__device__ __forceinline__ void store_pivot_inverse(const double* Am, double* Pg) {
-    for (int i = threadIdx.x; i < JTT; i += 256) {
-        const int r = i >> 6, c = i & 63;
-        Pg[i] = -0.5 * (Am[r * LDA + c] + Am[c * LDA + r]);
-    }
-}
-
-// pivot tile of step k.  k = 0: first pivot of a knot; k > 0: only in the bulk schedule (many workgroups per launch), where the update
-// kernel has no look-ahead (jq_update_bulk)
-__global__ __launch_bounds__(256) void jq_pivot0(JArgs A, int kind, int s, int mid, int k) {
-    const DevSession& S = A.S;
-    const int mission = blockIdx.z, chain = blockIdx.y + A.chain0;
-    const Ws w = carve(A, mission);
-    const JDims d = jdims(S.N, S.Mk[mission]);
-    const SweepCtx c = sweep_ctx(A, w, d, kind, s, mid, k, chain);
-    if (!c.active || k >= c.nblk) return;
-    __shared__ double Am[JT * LDA];
-    __shared__ InvScratch sc;
-    __shared__ int bad;
-    if (threadIdx.x == 0) bad = 0;
-    const double* tkk = c.src + ((size_t)k * c.nblk + k) * JTT;  // pivot tile (k, k) as the steps before k left it
-    for (int i = threadIdx.x; i < JTT; i += 256) Am[(i >> 6) * LDA + (i & 63)] = tkk[i];
-    __shared__ double thr[JT];
-    if (c.G && threadIdx.x < JT) thr[threadIdx.x] = A.pol_tau * w.st[ST_PTAU] * c.G[((size_t)k * c.nblk + k) * JTT + (size_t)threadIdx.x * (JT + 1)];
-    __syncthreads();
-    inv64_lds(Am, &sc, &bad, c.G ? thr : nullptr);
-    store_pivot_inverse(Am, c.Pk);
-    // a non-positive pivot (the matrix is SPD in exact arithmetic) is counted, not fatal: the sweep needs no square roots, and with
-    // Newton weights of 1e9 the last interior-point iterations work at the edge of double precision
-    if (bad && threadIdx.x == 0) *c.bad = 1.0;  // (a flag: the two chains' workgroups may both set it, never a read-modify-write)
-}
-
-// operand fragments of a 16-row block for v_mfma_f64_16x16x4_f64 over K = 64: lane (i, g) holds rows[i][16 ch + 4 g + q], ch, q = 0..3
-// (the four MFMA steps of a 16-chunk use k = 4 g + q on both operands: a permutation of the summation index, see tile_nt in qp.hip).
-// TR: the operand is the TRANSPOSE of the stored tile (rows of the operand are columns of the tile).
-__device__ __forceinline__ void load_frag(const double* tile, int row0, bool tr, int li, int lg, d4 (&f)[4]) {
-    if (!tr) {
-        const double* p = tile + (size_t)(row0 + li) * JT + 4 * lg;
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch) f[ch] = *reinterpret_cast<const d4*>(p + 16 * ch);
-    } else {
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) f[ch][q] = tile[(size_t)(16 * ch + 4 * lg + q) * JT + row0 + li];
-    }
-}
-
-// panel of step k: Y_J = B_Jk P for every J != k  (B_Jk = tile (J, k) below the pivot, tile (k, J)' left of it)
-__global__ __launch_bounds__(256) void jq_panel(JArgs A, int kind, int s, int mid, int k) {
-    const DevSession& S = A.S;
-    const int mission = blockIdx.z, chain = blockIdx.y + A.chain0, J = blockIdx.x;
-    const Ws w = carve(A, mission);
-    const JDims d = jdims(S.N, S.Mk[mission]);
-    const SweepCtx c = sweep_ctx(A, w, d, kind, s, mid, k, chain);
-    if (!c.active || J >= c.nblk || J == k) return;
-    const int nblk = c.nblk;
-    const double* X = c.src;
-    const double* P = c.Pk;
-    const bool tr = J < k;
-    const double* Z = X + (tr ? (size_t)k * nblk + J : (size_t)J * nblk + k) * JTT;
-    double* Y = c.Y + (size_t)J * JTT;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, lg = lane >> 4;
-    d4 zf[4];
-    load_frag(Z, 16 * wave, tr, li, lg, zf);  // rows 16 wave .. of Z_J
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj) {
-        d4 pf[4];
-        load_frag(P, 16 * tj, false, li, lg, pf);  // P symmetric: Z P = Z P'
-        d4 acc = d4{0, 0, 0, 0};
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(zf[ch][q], pf[ch][q], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Y[(size_t)(16 * wave + lg + 4 * r) * JT + 16 * tj + li] = acc[r];
-    }
-}
-
-
-// Y_T = B_Tk P of step k (what jq_panel computes for row block T, the same instructions in the same order), written to LDS instead of
-// memory: when JArgs::fuse_panel is set every workgroup of jq_update forms the panel rows it needs itself and the panel launch -- a dependent
-// kernel boundary per 64 columns -- disappears from the look-ahead schedule (one extra 64^3 product per tile, P and B_Tk come from the L2).
-// Decided per launch (JArgs::fuse_panel): it pays while a launch is a round or so of workgroups (64 agents 0.267 -> 0.245 s; one chain of a
-// 256-agent mission, 666 tiles, 3.84 -> 3.75 s) and costs 5 % when both chains of that mission share the launches (1332 tiles).
-__device__ __forceinline__ void panel_rows_to_lds(const double* X, const double* P, int nblk, int k, int T, double* Am, int wave, int li, int lg) {
-    const bool tr = T < k;
-    const double* Z = X + (tr ? (size_t)k * nblk + T : (size_t)T * nblk + k) * JTT;
-    d4 zf[4];
-    load_frag(Z, 16 * wave, tr, li, lg, zf);
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj) {
-        d4 pf[4];
-        load_frag(P, 16 * tj, false, li, lg, pf);
-        d4 acc = d4{0, 0, 0, 0};
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(zf[ch][q], pf[ch][q], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Am[(16 * wave + lg + 4 * r) * LDA + 16 * tj + li] = acc[r];
-    }
-}
-
-// update of step k: every tile (I, J), I >= J, of the lower triangle
-//   (k, k) <- -P        (I, k) <- Y_I        (k, J) <- Y_J'        else  B_IJ - Y_I B_Jk'
-// The last step writes -(...) = the inverse itself, with both triangles.  Look-ahead: the workgroup of tile (k+1, k+1) inverts it.
-__global__ __launch_bounds__(256, 3) void jq_update(JArgs A, int kind, int s, int mid, int k) {
-    const DevSession& S = A.S;
-    // Which tile this workgroup takes.  Workgroups start in the order x, then y: the chains of a launch are interleaved (so that both
-    // chains' first tiles start in the first round), and the tile that carries the look-ahead inversion -- 20 us of dependent work
-    // on top of its update, the longest job of the launch -- is taken by the FIRST workgroup of its chain instead of one in the middle of
-    // the triangle (with hundreds of tiles per chain, a 256-agent mission, it used to start in the second or third round and the
-    // launch ended with that inversion alone on the chip).  The arithmetic of a tile does not depend on who computes it.
-    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x), nchl = (int)gridDim.y;
-    const int mission = blockIdx.z, chain = lin % nchl + A.chain0;
-    int b = lin / nchl;
-    const Ws w = carve(A, mission);
-    const JDims d = jdims(S.N, S.Mk[mission]);
-    const SweepCtx c = sweep_ctx(A, w, d, kind, s, mid, k, chain);
-    const int nblk = c.nblk;
-    if (!c.active || b >= nblk * (nblk + 1) / 2) return;
-    if (k + 1 < nblk) {
-        const int lookb = (k + 1) * (k + 2) / 2 + (k + 1);
-        b = b == 0 ? lookb : (b == lookb ? 0 : b);
-    }
-    int I = (int)((sqrtf(8.0f * b + 1.0f) - 1.0f) * 0.5f);
-    if (I * (I + 1) / 2 > b) I--;
-    if ((I + 1) * (I + 2) / 2 <= b) I++;
-    const int J = b - I * (I + 1) / 2;
-    const double* X = c.src;
-    double* Xn = c.dst;
-    const double* P = c.Pk;
-    const double* Yb = c.Y;
-    const bool last = k == nblk - 1, look = !last && I == k + 1 && J == k + 1, fuse = A.fuse_panel != 0;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lg = lane >> 4;
-    const int wr = wave >> 1, wc = wave & 1;  // this wave's 32 x 32 quadrant
-    // LDS is DYNAMIC here (JQ_UPDATE_LDS bytes per launch): with a static size the compiler derives the occupancy from a 64 KB LDS and then
-    // spends 248 registers; the CU has 160 KB, three workgroups of 52.7 KB fit, and the register budget has to follow (launch bounds)
-    extern __shared__ double jq_update_lds[];
-    double* Am = jq_update_lds;                                        // [JT * LDA]
-    InvScratch& sc = *reinterpret_cast<InvScratch*>(Am + JT * LDA);
-    double* thr = reinterpret_cast<double*>(&sc + 1);                  // [JT]
-    int& bad = *reinterpret_cast<int*>(thr + JT);
-    double* out = Xn + ((size_t)I * nblk + J) * JTT;
-    double* outT = Xn + ((size_t)J * nblk + I) * JTT;
-    const double sgn = last ? -1.0 : 1.0;
-    if (I == k || J == k) {  // copies (through LDS for the transposed ones)
-        const double* src = (I == k && J == k) ? P : (J == k ? Yb + (size_t)I * JTT : Yb + (size_t)J * JTT);
-        const bool tr = (I == k && J != k);
-        const double f = (I == k && J == k) ? -sgn : sgn;
-        if (fuse && !(I == k && J == k))
-            panel_rows_to_lds(X, P, nblk, k, J == k ? I : J, Am, wave, li, lg);
-        else
-            for (int i = tid; i < JTT; i += 256) Am[(i >> 6) * LDA + (i & 63)] = src[i];
-        __syncthreads();
-        for (int i = tid; i < JTT; i += 256) {
-            const int r = i >> 6, cc = i & 63;
-            const double v = f * (tr ? Am[cc * LDA + r] : Am[r * LDA + cc]);
-            out[i] = v;
-            if (last && I != J) outT[(size_t)cc * JT + r] = v;
-        }
-        return;
-    }
-    const bool trJ = J < k;
-    const double* Zt = X + (trJ ? (size_t)k * nblk + J : (size_t)J * nblk + k) * JTT;
-    const double* Yt = Yb + (size_t)I * JTT;
-    const double* Ct = X + ((size_t)I * nblk + J) * JTT;
-    double cv[2][2][4];
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) cv[ti][tj][r] = Ct[(size_t)(32 * wr + 16 * ti + lg + 4 * r) * JT + 32 * wc + 16 * tj + li];
-    if (fuse) {
-        panel_rows_to_lds(X, P, nblk, k, I, Am, wave, li, lg);
-        __syncthreads();
-    }
-    {
-        // operands of ONE 16-column chunk at a time (as jq_update_bulk): the register budget of three workgroups per CU
-        d4 acc[2][2];
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = d4{0, 0, 0, 0};
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch) {
-            d4 yf[2], zf[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                if (fuse) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) yf[t][q] = Am[(32 * wr + 16 * t + li) * LDA + 16 * ch + 4 * lg + q];
-                } else {
-                    yf[t] = *reinterpret_cast<const d4*>(Yt + (size_t)(32 * wr + 16 * t + li) * JT + 16 * ch + 4 * lg);
-                }
-                if (!trJ) {
-                    zf[t] = *reinterpret_cast<const d4*>(Zt + (size_t)(32 * wc + 16 * t + li) * JT + 16 * ch + 4 * lg);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) zf[t][q] = Zt[(size_t)(16 * ch + 4 * lg + q) * JT + 32 * wc + 16 * t + li];
-                }
-            }
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(yf[ti][q], zf[tj][q], acc[ti][tj], 0, 0, 0);
-        }
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) cv[ti][tj][r] = sgn * (cv[ti][tj][r] - acc[ti][tj][r]);
-    }
-    if (!(last && I != J) && !look) {
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) out[(size_t)(32 * wr + 16 * ti + lg + 4 * r) * JT + 32 * wc + 16 * tj + li] = cv[ti][tj][r];
-        return;
-    }
-    // through LDS: mirrored store of the last step / look-ahead inversion of the next pivot
-    if (fuse) __syncthreads();  // (Y_I is still being read from Am by the other waves)
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Am[(32 * wr + 16 * ti + lg + 4 * r) * LDA + 32 * wc + 16 * tj + li] = cv[ti][tj][r];
-    if (tid == 0) bad = 0;
-    __syncthreads();
-    for (int i = tid; i < JTT; i += 256) {
-        const int r = i >> 6, cc = i & 63;
-        out[i] = Am[r * LDA + cc];
-        if (last) outT[i] = Am[cc * LDA + r];
-    }
-    if (look) {
-        if (c.G && tid < JT) thr[tid] = A.pol_tau * w.st[ST_PTAU] * c.G[((size_t)(k + 1) * nblk + (k + 1)) * JTT + (size_t)tid * (JT + 1)];
-        __syncthreads();
-        inv64_lds_inl(Am, &sc, &bad, c.G ? thr : nullptr);
-        store_pivot_inverse(Am, c.Pn);
-        if (bad && tid == 0) *c.bad = 1.0;
-    }
-}
-
-
-// The same update for launches with thousands of tiles (many resident missions, or one 256-agent mission): no look-ahead -- the next pivot
-// is inverted by jq_pivot0(k + 1) in a launch of its own --, hence no LDS (the look-ahead scratch costs every workgroup of jq_update 61 KB),
-// operands of ONE 16-column chunk at a time and a register budget for three workgroups per CU.
-__global__ __launch_bounds__(256, 3) void jq_update_bulk(JArgs A, int kind, int s, int mid, int k) {
-    const DevSession& S = A.S;
-    const int mission = blockIdx.z, chain = blockIdx.y + A.chain0;
-    const Ws w = carve(A, mission);
-    const JDims d = jdims(S.N, S.Mk[mission]);
-    const SweepCtx c = sweep_ctx(A, w, d, kind, s, mid, k, chain);
-    const int nblk = c.nblk;
-    if (!c.active || (int)blockIdx.x >= nblk * (nblk + 1) / 2) return;
-    int I = (int)((sqrtf(8.0f * blockIdx.x + 1.0f) - 1.0f) * 0.5f);
-    if (I * (I + 1) / 2 > (int)blockIdx.x) I--;
-    if ((I + 1) * (I + 2) / 2 <= (int)blockIdx.x) I++;
-    const int J = blockIdx.x - I * (I + 1) / 2;
-    const bool last = k == nblk - 1;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lg = lane >> 4;
-    const int wr = wave >> 1, wc = wave & 1;
-    double* out = c.dst + ((size_t)I * nblk + J) * JTT;
-    double* outT = c.dst + ((size_t)J * nblk + I) * JTT;
-    const double sgn = last ? -1.0 : 1.0;
-    if (I == k || J == k) {
-        const double* src = (I == k && J == k) ? c.Pk : (J == k ? c.Y + (size_t)I * JTT : c.Y + (size_t)J * JTT);
-        const bool tr = (I == k && J != k);
-        const double f = (I == k && J == k) ? -sgn : sgn;
-        for (int i = tid; i < JTT; i += 256) {
-            const int r = i >> 6, cc = i & 63;
-            const double v = f * (tr ? src[(size_t)cc * JT + r] : src[i]);
-            out[i] = v;
-            if (last && I != J) outT[(size_t)cc * JT + r] = v;
-        }
-        return;
-    }
-    const bool trJ = J < k;
-    const double* Zt = c.src + (trJ ? (size_t)k * nblk + J : (size_t)J * nblk + k) * JTT;
-    const double* Yt = c.Y + (size_t)I * JTT;
-    const double* Ct = c.src + ((size_t)I * nblk + J) * JTT;
-    double cv[2][2][4];
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) cv[ti][tj][r] = Ct[(size_t)(32 * wr + 16 * ti + lg + 4 * r) * JT + 32 * wc + 16 * tj + li];
-    d4 acc[2][2];
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = d4{0, 0, 0, 0};
-#pragma unroll
-    for (int ch = 0; ch < 4; ++ch) {
-        d4 yf[2], zf[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            yf[t] = *reinterpret_cast<const d4*>(Yt + (size_t)(32 * wr + 16 * t + li) * JT + 16 * ch + 4 * lg);
-            if (!trJ) {
-                zf[t] = *reinterpret_cast<const d4*>(Zt + (size_t)(32 * wc + 16 * t + li) * JT + 16 * ch + 4 * lg);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) zf[t][q] = Zt[(size_t)(16 * ch + 4 * lg + q) * JT + 32 * wc + 16 * t + li];
-            }
-        }
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(yf[ti][q], zf[tj][q], acc[ti][tj], 0, 0, 0);
-    }
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double v = sgn * (cv[ti][tj][r] - acc[ti][tj][r]);
-                const int rr = 32 * wr + 16 * ti + lg + 4 * r, cc = 32 * wc + 16 * tj + li;
-                out[(size_t)rr * JT + cc] = v;
-                if (last && I != J) outT[(size_t)cc * JT + rr] = v;
-            }
-}
-
-// ------------------------------------------------------------------------------------------------------------------------
-// Double steps of the bulk schedule: the pivots (k, k + 1) in ONE pass over the matrix.  jq_update_bulk is bound by HBM, not by the MFMA
-// (profiles/r05_joint_pmc.txt: 1.6 GB of reads and writes per 286 us launch = 5.6 TB/s at 200 resident missions): every pass reads and
-// writes the knot's whole lower triangle for a rank-64 update.  Sweeping on the 128 x 128 pivot block [B_kk B_k+1,k'; B_k+1,k B_k+1,k+1]
-// is the same two sweep steps composed -- P2 = block^-1, Y2_J = [B_Jk B_J,k+1] P2, (I, J) <- B_IJ - Y2_I [B_Jk B_J,k+1]' -- with half the
-// passes over the matrix per unit of arithmetic.
-// ------------------------------------------------------------------------------------------------------------------------
-// P2 by block elimination in one workgroup: Pa = B_kk^-1, W = B_k+1,k Pa, Ps = (B_k+1,k+1 - W B_k+1,k')^-1,
-// P11 = Ps, P10 = -Ps W, P00 = Pa + W' Ps W.  The four 64^3 products run on plain FMAs out of LDS (a few microseconds per knot and pass).
-__global__ __launch_bounds__(256) void jq_pivot2(JArgs A, int s, int mid, int k) {
-    const DevSession& S = A.S;
-    const int mission = blockIdx.z, chain = blockIdx.y + A.chain0, tid = threadIdx.x;
-    const Ws w = carve(A, mission);
-    const JDims d = jdims(S.N, S.Mk[mission]);
-    const SweepCtx c = sweep_ctx(A, w, d, 0, s, mid, k, chain);
-    if (!c.active || k + 1 >= c.nblk) return;
-    extern __shared__ double lds2[];  // Am, Bm, Wm: 3 x JT x LDA doubles
-    __shared__ InvScratch sc;
-    __shared__ int bad;
-    double *Am = lds2, *Bm = lds2 + JT * LDA, *Wm = lds2 + 2 * JT * LDA;
-    const int nblk = c.nblk;
-    const double* t00 = c.src + ((size_t)k * nblk + k) * JTT;
-    const double* t10 = c.src + ((size_t)(k + 1) * nblk + k) * JTT;
-    const double* t11 = c.src + ((size_t)(k + 1) * nblk + k + 1) * JTT;
-    double *P00 = c.P2, *P10 = c.P2 + JTT, *P11 = c.P2 + 2 * JTT;
-    if (tid == 0) bad = 0;
-    for (int i = tid; i < JTT; i += 256) Am[(i >> 6) * LDA + (i & 63)] = t00[i], Bm[(i >> 6) * LDA + (i & 63)] = t10[i];
-    __syncthreads();
-    inv64_lds(Am, &sc, &bad);  // Am = -Pa
-    double pa[16];
-#pragma unroll
-    for (int n = 0; n < 16; ++n) {
-        const int i = tid + 256 * n, r = i >> 6, cc = i & 63;
-        pa[n] = -0.5 * (Am[r * LDA + cc] + Am[cc * LDA + r]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < 16; ++n) {
-        const int i = tid + 256 * n;
-        Am[(i >> 6) * LDA + (i & 63)] = pa[n];
-    }
-    __syncthreads();
-    const int r0 = 4 * (tid >> 4), c0 = 4 * (tid & 15);
-    double acc[4][4];
-    // MODE 0: X[r][m] Yv[m][c]   1: X[r][m] Yv[c][m]   2: X[m][r] Yv[m][c]
-#define JQ_MM(MODE, X, Yv)                                                                            \
-    do {                                                                                              \
-        _Pragma("unroll") for (int x = 0; x < 4; ++x) _Pragma("unroll") for (int y = 0; y < 4; ++y) acc[x][y] = 0.0; \
-        for (int m = 0; m < JT; ++m) {                                                                \
-            double a[4], b[4];                                                                        \
-            _Pragma("unroll") for (int x = 0; x < 4; ++x) a[x] = (MODE) == 2 ? (X)[m * LDA + r0 + x] : (X)[(r0 + x) * LDA + m]; \
-            _Pragma("unroll") for (int y = 0; y < 4; ++y) b[y] = (MODE) == 1 ? (Yv)[(c0 + y) * LDA + m] : (Yv)[m * LDA + c0 + y]; \
-            _Pragma("unroll") for (int x = 0; x < 4; ++x) _Pragma("unroll") for (int y = 0; y < 4; ++y) acc[x][y] = fma(a[x], b[y], acc[x][y]); \
-        }                                                                                             \
-    } while (0)
-    JQ_MM(0, Bm, Am);  // W = B10 Pa
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) Wm[(r0 + x) * LDA + c0 + y] = acc[x][y];
-    __syncthreads();
-    JQ_MM(1, Wm, Bm);  // W B10'
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) Am[(r0 + x) * LDA + c0 + y] = t11[(size_t)(r0 + x) * JT + c0 + y] - acc[x][y];
-    __syncthreads();
-    inv64_lds(Am, &sc, &bad);  // Am = -Ps
-    double ps[16];
-#pragma unroll
-    for (int n = 0; n < 16; ++n) {
-        const int i = tid + 256 * n, r = i >> 6, cc = i & 63;
-        ps[n] = -0.5 * (Am[r * LDA + cc] + Am[cc * LDA + r]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < 16; ++n) {
-        const int i = tid + 256 * n;
-        Am[(i >> 6) * LDA + (i & 63)] = ps[n];
-        P11[i] = ps[n];
-    }
-    __syncthreads();
-    JQ_MM(0, Am, Wm);  // V = Ps W
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) Bm[(r0 + x) * LDA + c0 + y] = acc[x][y], P10[(size_t)(r0 + x) * JT + c0 + y] = -acc[x][y];
-    __syncthreads();
-    JQ_MM(2, Wm, Bm);  // W' V
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) Am[(r0 + x) * LDA + c0 + y] = acc[x][y];
-    __syncthreads();
-#undef JQ_MM
-#pragma unroll
-    for (int n = 0; n < 16; ++n) {
-        const int i = tid + 256 * n, r = i >> 6, cc = i & 63;
-        P00[i] = pa[n] + 0.5 * (Am[r * LDA + cc] + Am[cc * LDA + r]);
-    }
-    if (bad && tid == 0) *c.bad = 1.0;
-}
-
-// panel of the double step: Y2_J = [B_Jk B_J,k+1] P2 for every block row J outside the pivot block (two tiles per J)
-__global__ __launch_bounds__(256) void jq_panel2(JArgs A, int s, int mid, int k) {
-    const DevSession& S = A.S;
-    const int mission = blockIdx.z, chain = blockIdx.y + A.chain0, J = blockIdx.x;
-    const Ws w = carve(A, mission);
-    const JDims d = jdims(S.N, S.Mk[mission]);
-    const SweepCtx c = sweep_ctx(A, w, d, 0, s, mid, k, chain);
-    const int nblk = c.nblk;
-    if (!c.active || J >= nblk || J == k || J == k + 1 || k + 1 >= nblk) return;
-    const bool tr = J < k;
-    const double* Z0 = c.src + (tr ? (size_t)k * nblk + J : (size_t)J * nblk + k) * JTT;
-    const double* Z1 = c.src + (tr ? (size_t)(k + 1) * nblk + J : (size_t)J * nblk + k + 1) * JTT;
-    const double *P00 = c.P2, *P10 = c.P2 + JTT, *P11 = c.P2 + 2 * JTT;
-    double* Y0 = c.Y + (size_t)J * 2 * JTT;
-    double* Y1 = Y0 + JTT;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, lg = lane >> 4;
-    d4 z0[4], z1[4];
-    load_frag(Z0, 16 * wave, tr, li, lg, z0);
-    load_frag(Z1, 16 * wave, tr, li, lg, z1);
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj) {
-        d4 pf[4];
-        d4 a0 = d4{0, 0, 0, 0}, a1 = d4{0, 0, 0, 0};
-        load_frag(P00, 16 * tj, false, li, lg, pf);  // Z0 P00 (symmetric)
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a0 = __builtin_amdgcn_mfma_f64_16x16x4f64(z0[ch][q], pf[ch][q], a0, 0, 0, 0);
-        load_frag(P10, 16 * tj, true, li, lg, pf);  // Z1 P10: the operand's rows are P10's columns
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a0 = __builtin_amdgcn_mfma_f64_16x16x4f64(z1[ch][q], pf[ch][q], a0, 0, 0, 0);
-        load_frag(P10, 16 * tj, false, li, lg, pf);  // Z0 P01 = Z0 P10'
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(z0[ch][q], pf[ch][q], a1, 0, 0, 0);
-        load_frag(P11, 16 * tj, false, li, lg, pf);  // Z1 P11 (symmetric)
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(z1[ch][q], pf[ch][q], a1, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            Y0[(size_t)(16 * wave + lg + 4 * r) * JT + 16 * tj + li] = a0[r];
-            Y1[(size_t)(16 * wave + lg + 4 * r) * JT + 16 * tj + li] = a1[r];
-        }
-    }
-}
-
-// update of the double step: every tile (I, J), I >= J, of the lower triangle
-//   pivot block <- -P2      (I, k + h) <- Y2_I[h]      (k + h, J) <- Y2_J[h]'      else  B_IJ - Y2_I[0] B_Jk' - Y2_I[1] B_J,k+1'
-// (the last pass writes -(...) = the inverse itself, with both triangles)
-__global__ __launch_bounds__(256, 3) void jq_update2_bulk(JArgs A, int s, int mid, int k) {
-    const DevSession& S = A.S;
-    const int mission = blockIdx.z, chain = blockIdx.y + A.chain0;
-    const Ws w = carve(A, mission);
-    const JDims d = jdims(S.N, S.Mk[mission]);
-    const SweepCtx c = sweep_ctx(A, w, d, 0, s, mid, k, chain);
-    const int nblk = c.nblk;
-    if (!c.active || k + 1 >= nblk || (int)blockIdx.x >= nblk * (nblk + 1) / 2) return;
-    int I = (int)((sqrtf(8.0f * blockIdx.x + 1.0f) - 1.0f) * 0.5f);
-    if (I * (I + 1) / 2 > (int)blockIdx.x) I--;
-    if ((I + 1) * (I + 2) / 2 <= (int)blockIdx.x) I++;
-    const int J = blockIdx.x - I * (I + 1) / 2;
-    const bool last = k + 1 == nblk - 1;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lg = lane >> 4;
-    const int wr = wave >> 1, wc = wave & 1;
-    double* out = c.dst + ((size_t)I * nblk + J) * JTT;
-    double* outT = c.dst + ((size_t)J * nblk + I) * JTT;
-    const double sgn = last ? -1.0 : 1.0;
-    const bool Ik = I == k || I == k + 1, Jk = J == k || J == k + 1;
-    if (Ik || Jk) {
-        const double* src;
-        bool tr = false;
-        double f = sgn;
-        if (Ik && Jk)
-            src = c.P2 + (size_t)(I == k ? 0 : (J == k ? 1 : 2)) * JTT, f = -sgn;
-        else if (Jk)
-            src = c.Y + ((size_t)I * 2 + (J - k)) * JTT;
-        else
-            src = c.Y + ((size_t)J * 2 + (I - k)) * JTT, tr = true;
-        for (int i = tid; i < JTT; i += 256) {
-            const int r = i >> 6, cc = i & 63;
-            const double v = f * (tr ? src[(size_t)cc * JT + r] : src[i]);
-            out[i] = v;
-            if (last && I != J) outT[(size_t)cc * JT + r] = v;
-        }
-        return;
-    }
-    const bool trJ = J < k;
-    const double* Ct = c.src + ((size_t)I * nblk + J) * JTT;
-    double cv[2][2][4];
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) cv[ti][tj][r] = Ct[(size_t)(32 * wr + 16 * ti + lg + 4 * r) * JT + 32 * wc + 16 * tj + li];
-    d4 acc[2][2];
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = d4{0, 0, 0, 0};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const double* Zt = c.src + (trJ ? (size_t)(k + h) * nblk + J : (size_t)J * nblk + k + h) * JTT;
-        const double* Yt = c.Y + ((size_t)I * 2 + h) * JTT;
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch) {
-            d4 yf[2], zf[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                yf[t] = *reinterpret_cast<const d4*>(Yt + (size_t)(32 * wr + 16 * t + li) * JT + 16 * ch + 4 * lg);
-                if (!trJ) {
-                    zf[t] = *reinterpret_cast<const d4*>(Zt + (size_t)(32 * wc + 16 * t + li) * JT + 16 * ch + 4 * lg);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) zf[t][q] = Zt[(size_t)(16 * ch + 4 * lg + q) * JT + 32 * wc + 16 * t + li];
-                }
-            }
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(yf[ti][q], zf[tj][q], acc[ti][tj], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double v = sgn * (cv[ti][tj][r] - acc[ti][tj][r]);
-                const int rr = 32 * wr + 16 * ti + lg + 4 * r, cc = 32 * wc + 16 * tj + li;
-                out[(size_t)rr * JT + cc] = v;
-                if (last && I != J) outT[(size_t)cc * JT + rr] = v;
-            }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -1845,36 +1125,6 @@ __global__ __launch_bounds__(256) void jq_xfer(JArgs A, int what, int dir, int c
 #define JQ_POLISH_PART 2
 #include "jqp_polish.inc"
 #undef JQ_POLISH_PART
-
-__device__ __forceinline__ SweepCtx sweep_ctx(const JArgs& A, const Ws& w, const JDims& d, int kind, int s, int mid, int k, int chain) {
-    SweepCtx c;
-    c.bad = w.st + ST_BADPIV;
-    c.G = nullptr;
-    if (kind == 0) {
-        const Chain ch = chain_step(d, chain, s, mid != 0);
-        c.active = ch.active && w.st[ST_STATE] == 0.0 && w.st[ST_RETRY] == 0.0 && w.st[ST_GO] == 0.0;
-        c.nblk = d.nblk;
-        // pass t of np: a double step takes the pivots (2 t, 2 t + 1), an odd order ends with a single step
-        const int t = A.sweep2 ? (k >> 1) : k, p0 = sweep_parity0(A, d.nblk);
-        c.src = sweep_buf(w, d, A.L, chain, ch.jj, (t + p0) & 1);
-        c.dst = sweep_buf(w, d, A.L, chain, ch.jj, (t + p0 + 1) & 1);
-        c.Pk = w.P + ((size_t)chain * 2 + (k & 1)) * JTT, c.Pn = w.P + ((size_t)chain * 2 + ((k + 1) & 1)) * JTT;
-        c.P2 = w.P + (size_t)(4 + 3 * chain) * JTT;
-        c.Y = w.Y + (size_t)chain * 2 * A.L.nblkS * JTT;
-    } else {
-        const Pol p = pol_carve(A, blockIdx.z);
-        c.nblk = p.cnt[PC_NBLK];
-        c.active = chain == 0 && w.st[ST_STATE] == 0.0 && w.st[ST_GO] != 0.0 && w.st[ST_PSTATE] == (double)PS_SOLVE && !p.cnt[PC_BPPDONE] && k < c.nblk;
-        const int p0 = c.nblk & 1;
-        c.src = ((k + p0) & 1) ? p.W1 : p.W0;
-        c.dst = ((k + p0 + 1) & 1) ? p.W1 : p.W0;
-        c.Pk = p.P + (size_t)(k & 1) * JTT, c.Pn = p.P + (size_t)((k + 1) & 1) * JTT;
-        c.Y = p.Y;
-        c.P2 = nullptr;
-        c.G = p.G;
-    }
-    return c;
-}
 
 // ------------------------------------------------------------------------------------------------------------------------
 // end of a solve: objective sum x' Q_p x (cplex.getObjValue, rbp_planner.hpp:164), diagnostics, status
@@ -2146,7 +1396,7 @@ int launch_planner_joint(const DevSession& s, void* ws, hipStream_t st, JointSta
         xseq += 1;
         JQ_LAUNCH(jq_xfer, grid, 0, A, what, 1, 1 - my_chain, sh->recv + JQ_XHDR, (const double*)nullptr);
     };
-    auto substitute = [&](int which_out) {
+    auto substitute = [&]() {
         A.chain0 = my_chain;
         for (int sidx = 0; sidx < steps; ++sidx) JQ_LAUNCH(jq_mv, dim3(dm.nkp / 16, ychains, K), dm.nkp * sizeof(double), A, 0, sidx);
         A.chain0 = 0;
@@ -2160,7 +1410,7 @@ int launch_planner_joint(const DevSession& s, void* ws, hipStream_t st, JointSta
     };
     auto solve = [&](int which_out) {
         if (nref_round > 0) JQ_LAUNCH(jq_refine, dim3(npost, K), 0, A, 0, which_out);
-        substitute(which_out);
+        substitute();
         JQ_LAUNCH(jq_apply_F, dim3(npost, K), 0, A, which_out);
         for (int rs = 0; rs < nref_round; ++rs) {
             A.ref_step = rs;
@@ -2172,7 +1422,7 @@ int launch_planner_joint(const DevSession& s, void* ws, hipStream_t st, JointSta
                 JQ_LAUNCH(jq_sweep<PASS_KMUL_G>, dim3(nsw, K), 0, A);
             JQ_LAUNCH(jq_refine, dim3(npost, K), 0, A, 1, which_out);
             A.ref_gate = rs + 1;
-            substitute(which_out);
+            substitute();
             A.ref_gate = 0;
             JQ_LAUNCH(jq_refine, dim3(npost, K), 0, A, 2, which_out);
             JQ_LAUNCH(jq_apply_F, dim3(npost, K), 0, A, which_out);
@@ -2196,11 +1446,22 @@ int launch_planner_joint(const DevSession& s, void* ws, hipStream_t st, JointSta
     // as long as the workgroup that carries the look-ahead inversion) run better with TWO workgroups per CU -- asked for by padding the
     // request (measured, 256 agents: one chain per launch 3.76 s against 4.00 s; two chains, 1332 tiles, 4.40 against 4.27 the other way)
     const size_t lds_update_min = (size_t)JT * LDA * sizeof(double) + sizeof(InvScratch) + JQ_UPDATE_LDS_EXTRA;
-    auto few_tiles = [&](int nchain) { return (size_t)K * nchain * ntri < 1024; };  // (about a round of workgroups per launch)
-    auto lds_update_for = [&](int nchain) { return few_tiles(nchain) ? (size_t)72 * 1024 : lds_update_min; };
+    auto few_tiles = [&](int tiles) { return (size_t)K * tiles < 1024; };  // (tiles per mission and launch: about a round of workgroups per launch)
+    auto lds_update_for = [&](int nchain) { return few_tiles(nchain * ntri) ? (size_t)72 * 1024 : lds_update_min; };
     const size_t lds_update = lds_update_min;  // (the polish's S_AA sweeps: one chain, usually few tiles -- but several missions at once)
     if (hipFuncSetAttribute((const void*)jq_update, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(72 * 1024)) != hipSuccess) return RBP_ERR_HIP;
     if (A.sweep2 && hipFuncSetAttribute((const void*)jq_pivot2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pivot2) != hipSuccess) return RBP_ERR_HIP;
+    // the look-ahead sweep of one matrix per chain and mission, order nb tiles: a knot's Schur complement (kind 0) or the polish's S_AA (kind 1).
+    // While a launch is few tiles jq_update forms its panel rows itself (JArgs::fuse_panel) and jq_panel is not launched.
+    auto sweep_lookahead = [&](int kind, int sidx, int mid, int nb, int nchain, size_t lds) {
+        const int tri = nb * (nb + 1) / 2;
+        A.fuse_panel = few_tiles(nchain * tri) ? 1 : 0;
+        JQ_LAUNCH(jq_pivot0, dim3(1, nchain, K), 0, A, kind, sidx, mid, 0);
+        for (int k = 0; k < nb; ++k) {
+            if (nb > 1 && !A.fuse_panel) JQ_LAUNCH(jq_panel, dim3(nb, nchain, K), 0, A, kind, sidx, mid, k);
+            JQ_LAUNCH(jq_update, dim3(tri, nchain, K), lds, A, kind, sidx, mid, k);
+        }
+    };
     auto factor_knot = [&](int sidx, int mid) {
         const int nchain = mid ? 1 : ychains;
         A.chain0 = mid ? 0 : my_chain;
@@ -2223,15 +1484,14 @@ int launch_planner_joint(const DevSession& s, void* ws, hipStream_t st, JointSta
             }
             return;
         }
-        JQ_LAUNCH(jq_pivot0, dim3(1, nchain, K), 0, A, 0, sidx, mid, 0);
+        if (!bulk) {
+            sweep_lookahead(0, sidx, mid, nblk, nchain, lds_update_for(nchain));
+            return;
+        }
         for (int k = 0; k < nblk; ++k) {
-            if (bulk && k > 0) JQ_LAUNCH(jq_pivot0, dim3(1, nchain, K), 0, A, 0, sidx, mid, k);
-            A.fuse_panel = !bulk && few_tiles(nchain) ? 1 : 0;
-            if (nblk > 1 && !A.fuse_panel) JQ_LAUNCH(jq_panel, dim3(nblk, nchain, K), 0, A, 0, sidx, mid, k);
-            if (bulk)
-                JQ_LAUNCH(jq_update_bulk, dim3(ntri, nchain, K), 0, A, 0, sidx, mid, k);
-            else
-                JQ_LAUNCH(jq_update, dim3(ntri, nchain, K), lds_update_for(nchain), A, 0, sidx, mid, k);
+            JQ_LAUNCH(jq_pivot0, dim3(1, nchain, K), 0, A, 0, sidx, mid, k);
+            if (nblk > 1) JQ_LAUNCH(jq_panel, dim3(nblk, nchain, K), 0, A, 0, sidx, mid, k);
+            JQ_LAUNCH(jq_update_bulk, dim3(ntri, nchain, K), 0, A, 0, sidx, mid, k);
         }
     };
     A.trace = trace ? 1 : 0;
@@ -2287,12 +1547,7 @@ int launch_planner_joint(const DevSession& s, void* ws, hipStream_t st, JointSta
             } else if (any_bpp) {
                 if (nblk_max > 0) {
                     JQ_LAUNCH(jp_gather, dim3(nblk_max * nblk_max, K), 0, A);
-                    JQ_LAUNCH(jq_pivot0, dim3(1, 1, K), 0, A, 1, 0, 0, 0);
-                    for (int k = 0; k < nblk_max; ++k) {
-                        A.fuse_panel = (size_t)K * nblk_max * (nblk_max + 1) / 2 < 1024 ? 1 : 0;
-                        if (nblk_max > 1 && !A.fuse_panel) JQ_LAUNCH(jq_panel, dim3(nblk_max, 1, K), 0, A, 1, 0, 0, k);
-                        JQ_LAUNCH(jq_update, dim3(nblk_max * (nblk_max + 1) / 2, 1, K), lds_update, A, 1, 0, 0, k);
-                    }
+                    sweep_lookahead(1, 0, 0, nblk_max, 1, lds_update);
                     JQ_LAUNCH(jp_z, dim3(nblk_max * 4, K), nblk_max * JT * sizeof(double), A, 0);
                     for (int rr = 0; rr < 2; ++rr) {  // two refinement steps: the multipliers' signs drive the exchange
                         JQ_LAUNCH(jp_z, dim3(nblk_max * 4, K), nblk_max * JT * sizeof(double), A, 1);

@@ -11,6 +11,7 @@ Needs an MI355X.
   oracle's certified optimum (tests/golden/joint64_sweep.npz, joint32_sweep.npz, joint_heldout.npz);
 * 256 agents (BASELINE config C4's mission, joint): solved, every constraint set of the reference satisfied;
 * sessions: several joint missions in one session == the one-mission calls bit for bit; a second run of a session repeats the first.
+* the look-ahead sweep with the panel in a launch of its own (sessions of 1024 tiles or more per launch) == with the panel fused into the update, bit for bit.
 """
 import hashlib
 import os
@@ -284,6 +285,31 @@ def test_joint_session_matches_one_mission_calls_and_repeats():
     for a, b, s in zip(runs[0], runs[1], singles):
         assert np.array_equal(a.view(np.uint64), b.view(np.uint64))
         assert np.array_equal(a.view(np.uint64), s.ctrl.view(np.uint64))
+
+
+@pytest.mark.parametrize("n,map_id,copies", [(16, 3, 88), (32, 7, 36)])
+def test_joint_unfused_panel_gives_the_bits_of_the_fused_one(n, map_id, copies):
+    """The look-ahead sweep forms the panel Y = B P in one of two places: inside jq_update while a launch is fewer than 1024 tiles (a lone
+    mission), by a jq_panel launch before it otherwise.  Both are one function (panel_rows in kernels/jqp_tile.inc), so a session of `copies`
+    copies of one mission -- whose two-chain knot launches are 2 x 6 x 88 = 1056 / 2 x 15 x 36 = 1080 tiles (3 / 5 tiles per side: the
+    smallest odd orders above one) -- must give every copy the control points of the mission solved alone, bit for bit, in the same
+    number of iterations."""
+    tri = (9 * n + 63) // 64 * ((9 * n + 63) // 64 + 1) // 2
+    assert 2 * tri < 1024 <= copies * 2 * tri
+    p, m, w, init = _inputs(n, map_id)
+    opts = planner.solver_opts(joint_wide_min_agents=2, joint_schedule=1)
+    runs = {}
+    for K in (1, copies):
+        runs[K] = [init.clone_inputs() for _ in range(K)]
+        sess = planner.Session([w] * K, [m] * K, p, runs[K], opts=opts)
+        sess.run(A.RBP_STAGE_ALL)
+        assert sess.download() == [0] * K
+        sess.close()
+    alone = runs[1][0]
+    assert alone.qp_solves == 1 and alone.qp_unpolished == 0
+    for g in runs[copies]:
+        assert g.qp_unpolished == 0 and g.qp_iterations == alone.qp_iterations
+        assert np.array_equal(g.ctrl.view(np.uint64), alone.ctrl.view(np.uint64))
 
 
 def test_joint_run_async_returns_at_once_and_gives_the_same_answer():

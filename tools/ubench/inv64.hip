@@ -1,4 +1,4 @@
-// Developer micro-benchmark (not product): the 64 x 64 pivot-tile inverse of the joint solver's sweep (kernels/jqp.hip inv64_lds), the
+// Developer micro-benchmark (not product): the 64 x 64 pivot-tile inverse of the joint solver's sweep (kernels/jqp_tile.inc inv64_lds), the
 // dependent chain of a lone joint mission.  One workgroup, 256 threads; times from the 100 MHz wall clock.
 // MI355X, round 4: inv64_lds 19.9 us, of which the four 16 x 16 Gauss-Jordan leaves 4 x 2.0 us (300 cycles per column step: the chain
 // pivot -> reciprocal (v_rcp_f64 + two Newton steps) -> multiplier -> update).  A leaf that keeps the matrix in registers (pivot row by DPP
