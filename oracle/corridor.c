@@ -281,6 +281,15 @@ int oracle_is_obstacle_in_box(const rbp_world* world, const rbp_param* param, co
     return is_obstacle_in_box(&c, box, margin);
 }
 
+/* the same test, also reporting how many getDistance calls it made before it returned (early exit at the first obstacle) */
+int oracle_is_obstacle_in_box_n(const rbp_world* world, const rbp_param* param, const double box[6], double margin,
+                                int64_t* n_samples) {
+    ctx_t c = {world, param, 0};
+    int hit = is_obstacle_in_box(&c, box, margin);
+    if (n_samples) *n_samples = c.samples;
+    return hit;
+}
+
 void oracle_expand_box(const rbp_world* world, const rbp_param* param, double box[6], double margin) {
     ctx_t c = {world, param, 0};
     expand_box(&c, box, margin);

@@ -24,6 +24,8 @@ int oracle_corridor_update(const rbp_world* world, const rbp_mission* mission, c
 
 /* single pieces, for unit tests */
 int oracle_is_obstacle_in_box(const rbp_world* world, const rbp_param* param, const double box[6], double margin);
+int oracle_is_obstacle_in_box_n(const rbp_world* world, const rbp_param* param, const double box[6], double margin,
+                                int64_t* n_samples); /* + the number of getDistance calls made */
 void oracle_expand_box(const rbp_world* world, const rbp_param* param, double box[6], double margin);
 int oracle_rsfc_normal(const float pi0[3], const float pi1[3], const float pj0[3], const float pj1[3], double downwash,
                        float out[3]);

@@ -47,6 +47,7 @@ def lib():
         L.oracle_planner_update.argtypes = [P(A.rbp_mission), P(A.rbp_param), P(A.rbp_plan), P(oracle_qp_options),
                                             P(oracle_qp_report)]
         L.oracle_is_obstacle_in_box.argtypes = [P(A.rbp_world), P(A.rbp_param), C.c_double * 6, C.c_double]
+        L.oracle_is_obstacle_in_box_n.argtypes = [P(A.rbp_world), P(A.rbp_param), C.c_double * 6, C.c_double, P(C.c_int64)]
         L.oracle_expand_box.argtypes = [P(A.rbp_world), P(A.rbp_param), C.c_double * 6, C.c_double]
         L.oracle_expand_box.restype = None
         L.oracle_rsfc_normal.argtypes = [A.c_float_p] * 4 + [C.c_double, A.c_float_p]
@@ -77,6 +78,22 @@ def corridor_update(world: World, mission: Mission, param: Param, plan: PlanResu
     ns = C.c_int64(0)
     rc = lib().oracle_corridor_update(C.byref(w), C.byref(m), C.byref(p), C.byref(pl), C.byref(ns))
     return rc, ns.value
+
+
+def is_obstacle_in_box(world: World, param: Param, box, margin):
+    """isObstacleInBox (rbp_corridor.hpp:44-78) of one box: returns (hit, n_getDistance_samples up to and including the first hit)"""
+    w, p = world.c_struct(), param.c_struct()
+    ns = C.c_int64(0)
+    hit = lib().oracle_is_obstacle_in_box_n(C.byref(w), C.byref(p), (C.c_double * 6)(*[float(v) for v in box]), float(margin), C.byref(ns))
+    return bool(hit), ns.value
+
+
+def expand_box(world: World, param: Param, box, margin):
+    """expand_box (rbp_corridor.hpp:99-147): returns the grown box [6]"""
+    w, p = world.c_struct(), param.c_struct()
+    b = (C.c_double * 6)(*[float(v) for v in box])
+    lib().oracle_expand_box(C.byref(w), C.byref(p), b, float(margin))
+    return np.array(b[:], np.float64)
 
 
 def planner_update(mission: Mission, param: Param, plan: PlanResult, linear_solver=0, verbose=0, tol_feas=None,
