@@ -346,7 +346,7 @@ void rbp_release_thread_context(void);
                               4: rbp_solver_opts (the library no longer reads environment variables); 5: rbp_session_shard_joint, RBP_ERR_EXCHANGE;
                               6: rbp_param.timescale_rule, rbp_plan.time_scale_alt */
 enum { RBP_SIZEOF_WORLD = 0, RBP_SIZEOF_MISSION = 1, RBP_SIZEOF_PARAM = 2, RBP_SIZEOF_PLAN = 3, RBP_SIZEOF_COUNTERS = 4, RBP_SIZEOF_DEVICE_ARRAYS = 5,
-       RBP_SIZEOF_SOLVER_OPTS = 6 };
+       RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7 };
 int rbp_abi_version(void);
 size_t rbp_sizeof(int which);
 const char* rbp_version(void);
@@ -384,6 +384,41 @@ void rbp_dev_worlds_destroy(rbp_dev_worlds* ws);
  * looks the distance up; dim[0] * dim[1] * dim[2] bytes come back instead of the grid. */
 int  rbp_dev_worlds_ecbs_obstacles(const rbp_dev_worlds* ws, int32_t w, const rbp_mission* mission, const rbp_param* param, int32_t dim[3],
                                    uint8_t* obstacle_host, size_t capacity);
+
+/* ---- the ECBS front-end search on the device --------------------------------
+ * The search of rbp_ecbs_plan_obstacles (rbp_host.h; csrc/host/ecbs.cpp) for K missions in one call, one wavefront per mission
+ * (kernels/ecbs.hip).  It is the host library's own deterministic search, so for a mission that ends with status 0, 1 or 2 every output
+ * equals what rbp_ecbs_plan_obstacles / rbp_ecbs_plan return for the same mask, mission, param and budget: init_traj and T bit for bit,
+ * M, makespan, sum_cost and both expansion counters.  Missions with a status other than 0 get zeros in their outputs.
+ * Status 3 (RBP_ECBS_CAPACITY) has no host counterpart: the mission exceeded a capacity of the device search -- a path longer than
+ * max_M - 2 steps in any high-level node, 32768 nodes of one low-level search -- and the library does NOT fall back to the CPU; the
+ * caller decides (rbp_ecbs_plan_obstacles, or a larger max_M).
+ * The return value is RBP_OK when the call itself worked; per-mission outcomes are in `status`.  Argument errors are
+ * RBP_ERR_BAD_ARGUMENT before a device is looked for: a null pointer, K <= 0, missions of differing N, N outside 1..256, a planning
+ * lattice with more than 1024 cells on an axis (or whose seen bitmap, cells x (8 (dimx + dimy + dimz) + 64 + max_M) bits, exceeds
+ * 16 MB), max_M outside 2..4096, max_high_level_nodes outside 1..RBP_ECBS_MAX_HIGH_LEVEL_NODES (B budgeted expansions need 2 B + 1
+ * node slots), a dim that is not param's lattice, a world index outside the set.  ecbs_w < 1 leaves the focal sets empty: status 2. */
+enum { RBP_ECBS_CAPACITY = 3, RBP_ECBS_MAX_HIGH_LEVEL_NODES = 512 };
+typedef struct rbp_ecbs_out {       /* caller-owned; all missions of a call share N */
+    int32_t  max_M;                 /* capacity in segments (makespan + 2 must fit) */
+    int32_t* status;                /* [K] 0 ok; 1 start/goal occluded or lattice sample outside the grid;
+                                       2 search failed / high-level budget exhausted (the host's codes);
+                                       3 RBP_ECBS_CAPACITY: a device capacity (max_M, node pool) was exceeded */
+    int32_t* M; int32_t* makespan; int32_t* sum_cost;         /* [K] */
+    int64_t* high_level_expanded; int64_t* low_level_expanded; /* [K] */
+    double*  T;                     /* [K][max_M+1] */
+    float*   init_traj;             /* [K][N][max_M+1][3] */
+} rbp_ecbs_out;
+
+/* the search on K obstacle masks of one lattice shape (host pointers, [dimx][dimy][dimz] of 0/1); device < 0: the current one */
+int rbp_dev_ecbs_plan_masks(int device, int32_t K, const int32_t dim[3], const uint8_t* const* obstacle,
+                            const rbp_mission* missions, const rbp_param* param,
+                            int64_t max_high_level_nodes, rbp_ecbs_out* out);
+/* the same for missions on resident worlds (mission k on world world_index[k] of the set): masks are made on the device
+   (the kernel behind rbp_dev_worlds_ecbs_obstacles, for all K in one launch) and never leave it */
+int rbp_dev_worlds_ecbs_plan(const rbp_dev_worlds* ws, int32_t K, const int32_t* world_index,
+                             const rbp_mission* missions, const rbp_param* param,
+                             int64_t max_high_level_nodes, rbp_ecbs_out* out);
 
 const char* rbp_last_error(void);
 int rbp_device_count(void);

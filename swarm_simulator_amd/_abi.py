@@ -34,6 +34,9 @@ RBP_ABI_VERSION = 6  # include/rbp.h
 RBP_TIMESCALE_ALL_REAL_ROOTS = 0     # rbp_param.timescale_rule (include/rbp.h)
 RBP_TIMESCALE_FIRST_EIGENVALUES = 1
 
+RBP_ECBS_CAPACITY = 3                # rbp_ecbs_out.status: a capacity of the device search was exceeded (include/rbp.h)
+RBP_ECBS_MAX_HIGH_LEVEL_NODES = 512
+
 RBP_STAGE_CORRIDOR = 1
 RBP_STAGE_PLANNER = 2
 RBP_STAGE_ALL = 3
@@ -85,6 +88,12 @@ class rbp_solver_opts(C.Structure):
     _fields_ = [("size", C.c_int32), ("polish", C.c_int32), ("joint_wide_min_agents", C.c_int32), ("joint_corrector", C.c_int32),
                 ("joint_schedule", C.c_int32), ("qp_schedule", C.c_int32), ("qp_variant", C.c_int32), ("qp_block_order", C.c_int32),
                 ("qp_groups", C.c_int32), ("qp_rounds", C.c_int32), ("qp_far_slack", C.c_double)]
+
+
+class rbp_ecbs_out(C.Structure):
+    _fields_ = [("max_M", C.c_int32), ("status", c_int32_p), ("M", c_int32_p), ("makespan", c_int32_p), ("sum_cost", c_int32_p),
+                ("high_level_expanded", C.POINTER(C.c_int64)), ("low_level_expanded", C.POINTER(C.c_int64)),
+                ("T", c_double_p), ("init_traj", c_float_p)]
 
 
 class rbp_mission_buf(C.Structure):

@@ -138,6 +138,7 @@ size_t rbp_sizeof(int which) {
         case RBP_SIZEOF_COUNTERS: return sizeof(rbp_counters);
         case RBP_SIZEOF_DEVICE_ARRAYS: return sizeof(rbp_device_arrays);
         case RBP_SIZEOF_SOLVER_OPTS: return sizeof(rbp_solver_opts);
+        case RBP_SIZEOF_ECBS_OUT: return sizeof(rbp_ecbs_out);
         default: return 0;
     }
 }

@@ -145,10 +145,10 @@ __global__ __launch_bounds__(256) void edt_set_x_finish_kernel(const EdtWorldDes
 // One thread per sample (x, y, z) of the planning lattice: getDistance's lookup and `dist < r + grid_margin` in double.  xs / ys / zs hold the
 // sample coordinates as float (octomap::point3d), cx / cy / cz the mask cell of each sample (-1: none), both made on the host by the
 // reference's own loops.  A sample outside the grid sets *outside.
-__global__ __launch_bounds__(256) void ecbs_obstacle_kernel(DevWorld w, const float* __restrict__ xs, const float* __restrict__ ys,
-                                                            const float* __restrict__ zs, const int* __restrict__ cx, const int* __restrict__ cy,
-                                                            const int* __restrict__ cz, int sx, int sy, int sz, int dimy, int dimz, double limit,
-                                                            unsigned char* __restrict__ mask, unsigned* __restrict__ outside) {
+__device__ __forceinline__ void ecbs_obstacle_sample(const DevWorld& w, const float* __restrict__ xs, const float* __restrict__ ys,
+                                                     const float* __restrict__ zs, const int* __restrict__ cx, const int* __restrict__ cy,
+                                                     const int* __restrict__ cz, int sx, int sy, int sz, int dimy, int dimz, double limit,
+                                                     unsigned char* __restrict__ mask, unsigned* __restrict__ outside) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= sx * sy * sz) return;
     const int c = i % sz, b = (i / sz) % sy, a = i / (sz * sy);
@@ -162,6 +162,23 @@ __global__ __launch_bounds__(256) void ecbs_obstacle_kernel(DevWorld w, const fl
     }
     const float d = w.dist[((size_t)kx * w.dim[1] + ky) * w.dim[2] + kz];
     if ((double)d < limit && cx[a] >= 0 && cy[b] >= 0 && cz[c] >= 0) mask[((size_t)cx[a] * dimy + cy[b]) * dimz + cz[c]] = 1;
+}
+
+__global__ __launch_bounds__(256) void ecbs_obstacle_kernel(DevWorld w, const float* __restrict__ xs, const float* __restrict__ ys,
+                                                            const float* __restrict__ zs, const int* __restrict__ cx, const int* __restrict__ cy,
+                                                            const int* __restrict__ cz, int sx, int sy, int sz, int dimy, int dimz, double limit,
+                                                            unsigned char* __restrict__ mask, unsigned* __restrict__ outside) {
+    ecbs_obstacle_sample(w, xs, ys, zs, cx, cy, cz, sx, sy, sz, dimy, dimz, limit, mask, outside);
+}
+
+// the same for K missions in one launch (blockIdx.y): mission k reads worlds[k] against limits[k] and writes masks[k][ncell], outside[k]
+__global__ __launch_bounds__(256) void ecbs_obstacle_set_kernel(const DevWorld* __restrict__ worlds, const double* __restrict__ limits,
+                                                                const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                                const int* __restrict__ cx, const int* __restrict__ cy, const int* __restrict__ cz, int sx,
+                                                                int sy, int sz, int dimx, int dimy, int dimz, unsigned char* __restrict__ masks,
+                                                                unsigned* __restrict__ outside) {
+    const int k = blockIdx.y;
+    ecbs_obstacle_sample(worlds[k], xs, ys, zs, cx, cy, cz, sx, sy, sz, dimy, dimz, limits[k], masks + (size_t)k * dimx * dimy * dimz, outside + k);
 }
 
 int dims(double res, const double* bmin, const double* bmax, int* dim, int* kmin) {
@@ -189,17 +206,19 @@ struct rbp_dev_worlds {
 
 namespace {
 
-struct DeviceScope {  // the calling thread's current device is put back when the call returns
-    int prev = -1;
-    explicit DeviceScope(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) (void)hipSetDevice(device);
-        else prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+// the planning lattice and its samples, by the reference's own loops (init_traj_planner.hpp:19-29, ecbs_planner.hpp:80-109): per axis the
+// sample coordinates as float (octomap::point3d) and the mask cell of each sample (-1: none); an error text on a bad lattice
+const char* lattice_samples(const rbp_param* param, int32_t dim[3], std::vector<float> pos[3], std::vector<int> cell[3]) {
+    const double eps = SP_EPSILON;
+    double gmin[3], gmax[3], gres[3];
+    if (!planning_lattice(param, 4096, gmin, gmax, gres, dim)) return "grid resolution must be positive, planning grid of 1..4096 cells per axis";
+    for (int a = 0; a < 3; ++a)
+        for (double i = gmin[a]; i < gmax[a] + eps; i += gres[a]) {
+            const int c = (int)std::round((i - gmin[a]) / gres[a]);
+            pos[a].push_back((float)i), cell[a].push_back(c >= 0 && c < dim[a] ? c : -1);
+        }
+    return nullptr;
+}
 
 // builds the grids of `ws` (desc filled but for chunk_off; ws->dist allocated) on the current device; returns when they are complete
 int build_set(rbp_dev_worlds* ws, const int32_t* const* leaf_keys) {
@@ -395,23 +414,9 @@ extern "C" int rbp_dev_worlds_ecbs_obstacles(const rbp_dev_worlds* ws, int32_t w
     rbp_world g;
     if (!mission || !param || !dim || mission->N <= 0 || !mission->radius) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_ecbs_obstacles: null argument");
     if (int rc = rbp_dev_worlds_get(ws, w, &g)) return rc;
-    // the planning lattice and its samples, by the reference's own loops (init_traj_planner.hpp:19-29, ecbs_planner.hpp:80-109)
-    const double eps = SP_EPSILON;
-    const double gres[3] = {param->grid_xy_res, param->grid_xy_res, param->grid_z_res};
     std::vector<float> pos[3];
     std::vector<int> cell[3];
-    for (int a = 0; a < 3; ++a) {
-        if (!(gres[a] > 0)) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_ecbs_obstacles: grid resolution must be positive");
-        const double gmin = std::ceil((param->world_min[a] - eps) / gres[a]) * gres[a];
-        const double gmax = std::floor((param->world_max[a] + eps) / gres[a]) * gres[a];
-        const double n = std::round((gmax - gmin) / gres[a]) + 1;
-        if (!(n > 0) || n > 4096) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_ecbs_obstacles: planning grid empty or above 4096 cells per axis");
-        dim[a] = (int)n;
-        for (double i = gmin; i < gmax + eps; i += gres[a]) {
-            const int c = (int)std::round((i - gmin) / gres[a]);
-            pos[a].push_back((float)i), cell[a].push_back(c >= 0 && c < dim[a] ? c : -1);
-        }
-    }
+    if (const char* what = lattice_samples(param, dim, pos, cell)) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, (std::string("rbp_dev_worlds_ecbs_obstacles: ") + what).c_str());
     if (!obstacle_host) return RBP_OK;  // (only the shape was asked for)
     const size_t ncell = (size_t)dim[0] * dim[1] * dim[2];
     if (capacity < ncell) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_ecbs_obstacles: obstacle buffer smaller than dim[0] * dim[1] * dim[2]");
@@ -451,4 +456,66 @@ extern "C" int rbp_dev_worlds_ecbs_obstacles(const rbp_dev_worlds* ws, int32_t w
     unsigned outside = 0;
     memcpy(&outside, back.data() + mask_bytes, 4);
     return outside ? 1 : RBP_OK;
+}
+
+// the device search of kernels/ecbs.hip on resident worlds: the masks of all K missions in one launch, handed to the search where they are
+extern "C" int rbp_dev_worlds_ecbs_plan(const rbp_dev_worlds* ws, int32_t K, const int32_t* world_index, const rbp_mission* missions,
+                                        const rbp_param* param, int64_t max_high_level_nodes, rbp_ecbs_out* out) {
+    const char* who = "rbp_dev_worlds_ecbs_plan";
+    auto bad = [&](const char* what) { return rbp_set_error(RBP_ERR_BAD_ARGUMENT, (std::string(who) + ": " + what).c_str()); };
+    if (!ws || !world_index) return bad("need the set of worlds and world_index");
+    int32_t dim[3];
+    if (int rc = ecbs_check_arguments(who, K, nullptr, missions, param, max_high_level_nodes, out, dim)) return rc;
+    for (int k = 0; k < K; ++k)
+        if (world_index[k] < 0 || world_index[k] >= (int)ws->desc.size()) return bad("world index out of range");
+    std::vector<float> pos[3];
+    std::vector<int> cell[3];
+    int32_t sdim[3];
+    if (const char* what = lattice_samples(param, sdim, pos, cell)) return bad(what);
+    const int sx = (int)pos[0].size(), sy = (int)pos[1].size(), sz = (int)pos[2].size(), ns = sx + sy + sz;
+    const size_t ncell = (size_t)dim[0] * dim[1] * dim[2], mask_bytes = ((size_t)K * ncell + 3) & ~size_t(3);
+    std::vector<int> up(2 * (size_t)ns);
+    for (int a = 0, o = 0; a < 3; o += (int)pos[a].size(), ++a) {
+        memcpy(&up[o], pos[a].data(), sizeof(float) * pos[a].size());
+        memcpy(&up[ns + o], cell[a].data(), sizeof(int) * cell[a].size());
+    }
+    std::vector<DevWorld> worlds(K);
+    std::vector<double> limits(K);
+    for (int k = 0; k < K; ++k) {
+        const EdtWorldDesc& d = ws->desc[world_index[k]];
+        for (int a = 0; a < 3; ++a) worlds[k].dim[a] = d.dim[a], worlds[k].key_min[a] = d.kmin[a];
+        worlds[k].res = d.res, worlds[k].dist = ws->dist + d.cell_off;
+        double r = 0;
+        for (int qi = 0; qi < missions[k].N; ++qi) r = std::max(r, missions[k].radius[qi]);
+        limits[k] = r + param->grid_margin;
+    }
+    DeviceScope scope(ws->device);
+    int* d_up = nullptr;
+    DevWorld* d_worlds = nullptr;
+    double* d_limits = nullptr;
+    unsigned char* d_mask = nullptr;  // the K masks, then the K flag words
+    hipError_t e = hipMalloc((void**)&d_up, sizeof(int) * up.size());
+    if (e == hipSuccess) e = hipMalloc((void**)&d_worlds, sizeof(DevWorld) * K);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_limits, sizeof(double) * K);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_mask, mask_bytes + 4 * (size_t)K);
+    if (e == hipSuccess) e = hipMemcpy(d_up, up.data(), sizeof(int) * up.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_worlds, worlds.data(), sizeof(DevWorld) * K, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_limits, limits.data(), sizeof(double) * K, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(d_mask, 0, mask_bytes + 4 * (size_t)K, 0);
+    int rc = RBP_OK;
+    if (e == hipSuccess) {
+        const float* f = reinterpret_cast<const float*>(d_up);
+        const int* c = d_up + ns;
+        for (int k0 = 0; k0 < K && e == hipSuccess; k0 += 32768) {  // (grid dimension y)
+            const int nk = std::min(K - k0, 32768);
+            hipLaunchKernelGGL(ecbs_obstacle_set_kernel, dim3((unsigned)(((size_t)sx * sy * sz + 255) / 256), nk), dim3(256), 0, 0, d_worlds + k0, d_limits + k0, f,
+                               f + sx, f + sx + sy, c, c + sx, c + sx + sy, sx, sy, sz, dim[0], dim[1], dim[2], d_mask + (size_t)k0 * ncell,
+                               reinterpret_cast<unsigned*>(d_mask + mask_bytes) + k0);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) rc = ecbs_plan_on_device(who, K, dim, d_mask, reinterpret_cast<const unsigned*>(d_mask + mask_bytes), missions, param, max_high_level_nodes, out);
+    }
+    (void)hipFree(d_up), (void)hipFree(d_worlds), (void)hipFree(d_limits), (void)hipFree(d_mask);
+    if (e != hipSuccess) return rbp_set_error(RBP_ERR_HIP, (std::string(who) + ": " + hipGetErrorString(e)).c_str());
+    return rc;
 }

@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
+
 #include "rbp.h"
 
 #define SP_EPSILON 1e-9        /* reference: swarm_planner/include/sp_const.hpp:3 */
@@ -110,6 +112,41 @@ __device__ __forceinline__ double dummy_ctrl_point(const float* tr, int m, int j
 }
 
 int rbp_set_error(int code, const char* msg);  // abi/session.hip: records the message rbp_last_error() returns, returns code
+
+struct DeviceScope {  // the calling thread's current device is put back when the call returns
+    int prev = -1;
+    explicit DeviceScope(int device) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != device) (void)hipSetDevice(device);
+        else prev = -1;
+    }
+    ~DeviceScope() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// the planning lattice of the ECBS front-end (init_traj_planner.hpp:19-29; csrc/host/ecbs.cpp planning_grid), the one statement of it on this side:
+// per axis the first and last sample, the step and the cell count.  false when a step is not positive or an axis has no cell or more than max_cells.
+inline bool planning_lattice(const rbp_param* param, int max_cells, double gmin[3], double gmax[3], double gres[3], int32_t dim[3]) {
+    gres[0] = gres[1] = param->grid_xy_res, gres[2] = param->grid_z_res;
+    for (int a = 0; a < 3; ++a) {
+        if (!(gres[a] > 0)) return false;
+        gmin[a] = std::ceil((param->world_min[a] - SP_EPSILON) / gres[a]) * gres[a];
+        gmax[a] = std::floor((param->world_max[a] + SP_EPSILON) / gres[a]) * gres[a];
+        const double n = std::round((gmax[a] - gmin[a]) / gres[a]) + 1;
+        if (!(n > 0) || n > max_cells) return false;
+        dim[a] = (int32_t)n;
+    }
+    return true;
+}
+
+// kernels/ecbs.hip: the ECBS search on the device.  ecbs_check_arguments: the argument checks both entry points share (no device work; dim_in
+// may be null, dim receives the planning lattice of param).  ecbs_plan_on_device: the search on K masks that are already on the CURRENT
+// device ([K][dim0 * dim1 * dim2] bytes; d_outside [K] or null: missions whose lattice left the world's grid), results into `out`.
+int ecbs_check_arguments(const char* who, int32_t K, const int32_t* dim_in, const rbp_mission* missions, const rbp_param* param,
+                         int64_t max_high_level_nodes, const rbp_ecbs_out* out, int32_t dim[3]);
+int ecbs_plan_on_device(const char* who, int32_t K, const int32_t dim[3], const unsigned char* d_masks, const unsigned* d_outside,
+                        const rbp_mission* missions, const rbp_param* param, int64_t max_high_level_nodes, rbp_ecbs_out* out);
 
 // launchers (defined in the .hip files)
 int launch_corridor(const DevSession& s, hipStream_t st);

@@ -84,7 +84,7 @@ def lib():
             if L.rbp_abi_version() != A.RBP_ABI_VERSION:
                 raise RbpLibraryMissing(f"{path}: ABI version {L.rbp_abi_version()}, this binding expects {A.RBP_ABI_VERSION} (rebuild the library)")
             L.rbp_session_device_arrays.argtypes = [C.c_void_p, C.c_int32, P(A.rbp_device_arrays)]
-            for which, t in enumerate((A.rbp_world, A.rbp_mission, A.rbp_param, A.rbp_plan, A.rbp_counters, A.rbp_device_arrays, A.rbp_solver_opts)):
+            for which, t in enumerate((A.rbp_world, A.rbp_mission, A.rbp_param, A.rbp_plan, A.rbp_counters, A.rbp_device_arrays, A.rbp_solver_opts, A.rbp_ecbs_out)):
                 if L.rbp_sizeof(which) != C.sizeof(t):
                     raise RbpLibraryMissing(f"{path}: sizeof({t.__name__}) is {L.rbp_sizeof(which)} in the library, {C.sizeof(t)} in this binding")
             L.rbp_release_thread_context.restype = None
@@ -120,6 +120,9 @@ def lib():
             L.rbp_dev_worlds_destroy.argtypes = [C.c_void_p]
             L.rbp_dev_worlds_destroy.restype = None
             L.rbp_dev_worlds_ecbs_obstacles.argtypes = [C.c_void_p, C.c_int32, P(A.rbp_mission), P(A.rbp_param), C.c_int32 * 3, P(C.c_uint8), C.c_size_t]
+            L.rbp_dev_ecbs_plan_masks.argtypes = [C.c_int, C.c_int32, P(C.c_int32), P(P(C.c_uint8)), P(A.rbp_mission), P(A.rbp_param), C.c_int64,
+                                                  P(A.rbp_ecbs_out)]
+            L.rbp_dev_worlds_ecbs_plan.argtypes = [C.c_void_p, C.c_int32, A.c_int32_p, P(A.rbp_mission), P(A.rbp_param), C.c_int64, P(A.rbp_ecbs_out)]
         except AttributeError:
             if not os.environ.get("RBP_HIP_LIB"):
                 raise
@@ -154,7 +157,7 @@ EXPORTED_SYMBOLS = [
     "rbp_solver_opts_defaults", "rbp_session_set_solver_opts", "rbp_ctx_set_solver_opts", "rbp_session_workspace_bytes", "rbp_session_reserve_workspace",
     "rbp_edt_dims", "rbp_edt_build",
     "rbp_dev_worlds_create", "rbp_dev_worlds_count", "rbp_dev_worlds_get", "rbp_dev_worlds_download", "rbp_dev_worlds_destroy",
-    "rbp_dev_worlds_ecbs_obstacles",
+    "rbp_dev_worlds_ecbs_obstacles", "rbp_dev_ecbs_plan_masks", "rbp_dev_worlds_ecbs_plan",
 ]
 
 
@@ -546,3 +549,97 @@ def ecbs_plan(dev_world: DeviceWorld, mission: Mission, param: Param, max_nodes=
     """host.ecbs_plan for a world on the GPU: the obstacle mask from the resident grid, then the host search; same result, same errors."""
     from . import host
     return host.ecbs_plan_obstacles(ecbs_obstacles(dev_world, mission, param), mission, param, max_nodes)
+
+
+class EcbsOut:
+    """rbp_ecbs_out (include/rbp.h) for K missions of N agents: the caller-owned arrays of one device search and their C struct"""
+
+    def __init__(self, K, N, max_M):
+        import numpy as np
+        self.K, self.N, self.max_M = K, N, max_M
+        self.status, self.M, self.makespan, self.sum_cost = (np.zeros(K, np.int32) for _ in range(4))
+        self.high_level, self.low_level = np.zeros(K, np.int64), np.zeros(K, np.int64)
+        self.T = np.zeros((K, max_M + 1), np.float64)
+        self.init_traj = np.zeros((K, N, max_M + 1, 3), np.float32)
+
+    def c_struct(self):
+        o = A.rbp_ecbs_out()
+        o.max_M = self.max_M
+        o.status, o.M, o.makespan, o.sum_cost = (A.ptr(a, A.c_int32_p) for a in (self.status, self.M, self.makespan, self.sum_cost))
+        o.high_level_expanded, o.low_level_expanded = (A.ptr(a, C.POINTER(C.c_int64)) for a in (self.high_level, self.low_level))
+        o.T, o.init_traj = A.ptr(self.T, A.c_double_p), A.ptr(self.init_traj, A.c_float_p)
+        return o
+
+    def results(self):
+        """one PlanResult with ecbs_stats per mission, None where the mission's status is not 0"""
+        res = []
+        for k in range(self.K):
+            if self.status[k]:
+                res.append(None)
+                continue
+            M = int(self.M[k])
+            pr = PlanResult(self.init_traj[k, :, :M + 1].copy(), self.T[k, :M + 1].copy())
+            pr.ecbs_stats = dict(makespan=int(self.makespan[k]), sum_cost=int(self.sum_cost[k]), high_level=int(self.high_level[k]),
+                                 low_level=int(self.low_level[k]))
+            res.append(pr)
+        return res
+
+
+class EcbsPlans(list):
+    """what the device searches return: a list of PlanResult (None where the mission's status is not 0) with the `status` array and the
+    raw arrays of the call (`out`, an EcbsOut)"""
+    status = out = None
+
+
+def _ecbs_missions(missions):
+    missions = list(missions)
+    if not missions:
+        raise ValueError("need at least one mission")
+    keep = [m.c_struct() for m in missions]   # (the structs point into the missions' arrays, which `missions` keeps alive)
+    return missions, (A.rbp_mission * len(keep))(*keep)
+
+
+def _ecbs_finish(name, rc, out):
+    if rc == A.RBP_ERR_BAD_ARGUMENT:
+        raise ValueError(f"{name} rc={rc}: {last_error()}")
+    if rc:
+        raise RuntimeError(f"{name} rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+    plans = EcbsPlans(out.results())
+    plans.status, plans.out = out.status, out
+    return plans
+
+
+def ecbs_plan_masks(masks, missions, param: Param, max_nodes=A.RBP_ECBS_MAX_HIGH_LEVEL_NODES, max_M=64, device=0):
+    """host.ecbs_plan_obstacles for K missions in one call, searched on the GPU (rbp_dev_ecbs_plan_masks, kernels/ecbs.hip: one wavefront per
+    mission): masks[k] is mission k's obstacle mask [dimx][dimy][dimz] (host.ecbs_obstacles / planner.ecbs_obstacles).  Returns a list of
+    PlanResult with ecbs_stats, equal to the host search's bit for bit, None where the mission's `status` (the list's attribute) is not 0:
+    1 and 2 are the host's codes, 3 (RBP_ECBS_CAPACITY) says that a capacity of the device search -- max_M, a node pool -- was exceeded;
+    nothing falls back to the CPU."""
+    import numpy as np
+    missions, ms = _ecbs_missions(missions)
+    masks = [np.ascontiguousarray(m, np.uint8) for m in masks]
+    if len(masks) != len(missions) or any(m.ndim != 3 or m.shape != masks[0].shape for m in masks):
+        raise ValueError("need one mask [dimx][dimy][dimz] per mission, all of one shape")
+    mp = (C.POINTER(C.c_uint8) * len(masks))(*[m.ctypes.data_as(C.POINTER(C.c_uint8)) for m in masks])
+    out = EcbsOut(len(missions), missions[0].qn, int(max_M))
+    ps, oc = param.c_struct(), out.c_struct()
+    rc = lib().rbp_dev_ecbs_plan_masks(int(device), len(missions), (C.c_int32 * 3)(*masks[0].shape), mp, ms, C.byref(ps), int(max_nodes), C.byref(oc))
+    return _ecbs_finish("rbp_dev_ecbs_plan_masks", rc, out)
+
+
+def ecbs_plan_batch(dev_worlds: DeviceWorlds, world_indices, missions, param: Param, max_nodes=A.RBP_ECBS_MAX_HIGH_LEVEL_NODES, max_M=64):
+    """planner.ecbs_plan for K missions in one call, searched on the GPU: mission k on world world_indices[k] of the resident set; the masks
+    are made on the device and never leave it (rbp_dev_worlds_ecbs_plan).  Returns what ecbs_plan_masks returns."""
+    import numpy as np
+    if not isinstance(dev_worlds, DeviceWorlds):
+        raise TypeError("planner.ecbs_plan_batch takes a DeviceWorlds")
+    if not dev_worlds._h:
+        raise RuntimeError("DeviceWorlds is closed")
+    missions, ms = _ecbs_missions(missions)
+    idx = np.ascontiguousarray(world_indices, np.int32)
+    if idx.shape != (len(missions),):
+        raise ValueError("need one world index per mission")
+    out = EcbsOut(len(missions), missions[0].qn, int(max_M))
+    ps, oc = param.c_struct(), out.c_struct()
+    rc = lib().rbp_dev_worlds_ecbs_plan(dev_worlds._h, len(missions), A.ptr(idx, A.c_int32_p), ms, C.byref(ps), int(max_nodes), C.byref(oc))
+    return _ecbs_finish("rbp_dev_worlds_ecbs_plan", rc, out)

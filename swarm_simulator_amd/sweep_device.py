@@ -3,8 +3,10 @@
 With --device-worlds the distance grids of all maps are built on the GPU in one call and stay there (planner.DeviceWorlds): the ECBS
 front-end gets its obstacle mask from the resident grid (planner.ecbs_plan) and both modes plan on it, with the report lines of test_all.
 Without the flag this is test_all itself, argument for argument.
+With --device-ecbs (only with --device-worlds) the searches of all maps run on the GPU too, in one call (planner.ecbs_plan_batch): the same
+initial trajectories, and one report line for the whole front-end instead of one per map.
 
-usage: python -m swarm_simulator_amd.sweep_device [--device-worlds] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
+usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
        [--batch-size 4] [--iteration 1] [--joint] [--csv DIR]
 """
 import argparse
@@ -17,6 +19,9 @@ from .types import Param
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--device-worlds", action="store_true", help="build all distance grids on the GPU in one call and keep them there")
+    ap.add_argument("--device-ecbs", action="store_true", help="with --device-worlds: the ECBS searches of all maps in one call on the GPU, within the device search's capacities "
+                    "(512 high-level expansions where the host search allows 200000, paths of at most 62 steps): a map beyond them ends the sweep "
+                    "with an error where the host search would go on")
     ap.add_argument("--mission", default="mission_64agents_15.json")
     ap.add_argument("--maps", default="1-50")
     ap.add_argument("--mode", choices=["serial", "batched"], default="serial")
@@ -25,6 +30,8 @@ def main(argv=None):
     ap.add_argument("--joint", action="store_true")
     ap.add_argument("--csv", default=None, help="write coef<qi>.csv per map into DIR/map<i>/ (generateCoefCSV)")
     args, rest = ap.parse_known_args(argv)
+    if args.device_ecbs and not args.device_worlds:
+        ap.error("--device-ecbs needs --device-worlds")
     if not args.device_worlds:
         return test_all.main(argv)
     if rest:
@@ -38,17 +45,28 @@ def main(argv=None):
     worlds = planner.DeviceWorlds([o[0] for o in octrees], [o[1] for o in octrees], param)
     print(f"Euclidean Distmap runtime, {len(maps)} maps in one device build: {time.perf_counter() - t0:.6f}")
     try:
-        plans = []
+        plans, inits = [], None
+        if args.device_ecbs:
+            t0 = time.perf_counter()
+            inits = planner.ecbs_plan_batch(worlds, list(range(len(maps))), [mission] * len(maps), param)
+            print(f"Initial Trajectory Planner runtime, {len(maps)} maps in one device search: {time.perf_counter() - t0:.6f}")
+            for i, st in zip(maps, inits.status):
+                if st:  # (3: a capacity of the device search; the host search is the caller's choice, not a fallback)
+                    print(f"[ERROR] map{i}: {host.ECBS_ERROR_TEXT.get(int(st), 'ECBSPlanner: device search capacity exceeded (status 3)')}")
+                    return -1
         for n, i in enumerate(maps):
             print(f"Map: map{i}.bt")
             w = worlds[n]
-            t0 = time.perf_counter()
-            try:
-                pr = planner.ecbs_plan(w, mission, param)
-            except RuntimeError as e:
-                print(f"[ERROR] {e}")
-                return -1
-            print(f"Initial Trajectory Planner runtime: {time.perf_counter() - t0:.6f}")
+            if inits is not None:
+                pr = inits[n]
+            else:
+                t0 = time.perf_counter()
+                try:
+                    pr = planner.ecbs_plan(w, mission, param)
+                except RuntimeError as e:
+                    print(f"[ERROR] {e}")
+                    return -1
+                print(f"Initial Trajectory Planner runtime: {time.perf_counter() - t0:.6f}")
             if args.mode == "serial":
                 t0 = time.perf_counter()
                 cor = planner.Corridor(w, mission, param)
