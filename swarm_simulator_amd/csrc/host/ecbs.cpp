@@ -8,7 +8,11 @@
 // Own implementation on std::set queues with explicit, deterministic tie-breaks (node id); the reference's
 // ties are resolved by Boost.Heap internals, so bit-identical paths are not a goal:
 // the output is judged on validity (conflict-free under the same rules) and bounded sub-optimality.
+// The device search (kernels/ecbs.hip) returns this file's bits.  What decides them outside the search loops -- the planning lattice, position -> cell,
+// the samples of the obstacle mask, the two conflict predicates, the writer of T / init_traj -- is stated once for both, in common/ecbs_rules.h.
 #include "rbp_host.h"
+
+#include "common/ecbs_rules.h"
 
 #include <algorithm>
 #include <cmath>
@@ -28,6 +32,13 @@ namespace {
 struct Cell {
     int x, y, z;
     bool operator==(const Cell& o) const { return x == o.x && y == o.y && z == o.z; }
+};
+struct CellXYZ {  // a Cell as the conflict rules and the plan writer of common/ecbs_rules.h read one (the search keeps the plain fields)
+    const Cell& c;
+    int x() const { return c.x; }
+    int y() const { return c.y; }
+    int z() const { return c.z; }
+    bool operator==(const CellXYZ& o) const { return c == o.c; }
 };
 
 inline uint64_t pack4(int t, int x, int y, int z) {
@@ -53,33 +64,11 @@ using Path = std::vector<Cell>;  // state at time t = path[min(t, size-1)]
 
 inline const Cell& at(const Path& p, int t) { return p[(size_t)t < p.size() ? t : p.size() - 1]; }
 
-// environment.hpp:656-664
 bool vertex_conflict(const Grid& g, int i, int j, const Cell& a, const Cell& b) {
-    double rr = g.radius[i] + g.radius[j];
-    if (rr < g.grid_size) return a == b;
-    double dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
-    return std::sqrt(dx * dx + dy * dy + dz * dz) * g.grid_size < rr;
+    return ecbs_rules::vertex_conflict(g.radius[i] + g.radius[j], g.grid_size, CellXYZ{a}, CellXYZ{b});
 }
-
-// environment.hpp:69-93 (closest approach of the relative motion to the origin) and :666-681
 bool edge_conflict(const Grid& g, int i, int j, const Cell& a1, const Cell& b1, const Cell& a2, const Cell& b2) {
-    double rr = g.radius[i] + g.radius[j];
-    if (rr < g.grid_size * 0.5) return a1 == b2 && b1 == a2;
-    double ax = a2.x - a1.x, ay = a2.y - a1.y, az = a2.z - a1.z;
-    double bx = b2.x - b1.x, by = b2.y - b1.y, bz = b2.z - b1.z;
-    double md = std::sqrt(ax * ax + ay * ay + az * az);
-    if (!(ax == bx && ay == by && az == bz)) {
-        double d = std::sqrt(bx * bx + by * by + bz * bz);
-        if (md > d) md = d;
-        double nx = bx - ax, ny = by - ay, nz = bz - az;
-        double nn = std::sqrt(nx * nx + ny * ny + nz * nz);
-        nx /= nn, ny /= nn, nz /= nn;
-        double adn = ax * nx + ay * ny + az * nz;
-        double cx = ax - nx * adn, cy = ay - ny * adn, cz = az - nz * adn;
-        d = std::sqrt(cx * cx + cy * cy + cz * cz);
-        if ((cx - ax) * (cx - bx) + (cy - ay) * (cy - by) + (cz - az) * (cz - bz) < 0 && md > d) md = d;
-    }
-    return md * g.grid_size <= rr;
+    return ecbs_rules::edge_conflict(g.radius[i] + g.radius[j], g.grid_size, CellXYZ{a1}, CellXYZ{b1}, CellXYZ{a2}, CellXYZ{b2});
 }
 
 int count_conflicts(const Grid& g, const std::vector<Path>& sol) {  // environment.hpp:425-460
@@ -134,7 +123,7 @@ struct LLNode {
 
 struct LowLevelResult {
     Path path;
-    int cost = 0, fmin = 0;
+    int cost = 0;
 };
 
 bool low_level(const Grid& g, int agent, const Cell& start, const Cell& goal, const Constraints& cons,
@@ -201,7 +190,6 @@ bool low_level(const Grid& g, int agent, const Cell& start, const Cell& goal, co
             for (int id = cur; id >= 0; id = nodes[id].parent) out.path.push_back({nodes[id].x, nodes[id].y, nodes[id].z});
             std::reverse(out.path.begin(), out.path.end());
             out.cost = n.g;
-            out.fmin = std::get<0>(*open.begin());
             return true;
         }
         focal.erase(focal.begin());
@@ -238,9 +226,9 @@ bool low_level(const Grid& g, int agent, const Cell& start, const Cell& goal, co
 
 struct HLNode {
     std::vector<Path> sol;
-    std::vector<int> cost, fmin;
+    std::vector<int> cost;
     std::vector<std::shared_ptr<Constraints>> cons;
-    int total = 0, lb = 0, focal = 0, id = 0;
+    int total = 0, focal = 0, id = 0;
 };
 
 float world_distance(const rbp_world_buf* w, float x, float y, float z) {
@@ -252,18 +240,7 @@ float world_distance(const rbp_world_buf* w, float x, float y, float z) {
     return w->dist[((size_t)kx * w->dim[1] + ky) * w->dim[2] + kz];
 }
 
-// the planning lattice of init_traj_planner.hpp:19-29: false when an axis has no cell
-bool planning_grid(const rbp_param* param, double gmin[3], double gmax[3], double gres[3], int dim[3]) {
-    const double eps = 1e-9;  // SP_EPSILON
-    gres[0] = gres[1] = param->grid_xy_res, gres[2] = param->grid_z_res;
-    for (int a = 0; a < 3; ++a) {
-        gmin[a] = std::ceil((param->world_min[a] - eps) / gres[a]) * gres[a];
-        gmax[a] = std::floor((param->world_max[a] + eps) / gres[a]) * gres[a];
-        dim[a] = (int)std::round((gmax[a] - gmin[a]) / gres[a]) + 1;
-        if (dim[a] <= 0) return false;
-    }
-    return true;
-}
+constexpr int MAX_CELLS = 65535;  // per axis: pack4 holds 16 bits per coordinate
 
 }  // namespace
 
@@ -271,10 +248,9 @@ bool planning_grid(const rbp_param* param, double gmin[3], double gmax[3], doubl
 extern "C" int rbp_ecbs_obstacles(const rbp_world_buf* world, const rbp_mission* mission, const rbp_param* param, int32_t dim_out[3],
                                   uint8_t* obstacle, size_t capacity) {
     if (!world || !mission || !param || !dim_out) return RBP_ERR_BAD_ARGUMENT;
-    const double eps = 1e-9;  // SP_EPSILON
     double gmin[3], gmax[3], gres[3];
-    int dim[3];
-    if (!planning_grid(param, gmin, gmax, gres, dim)) return RBP_ERR_BAD_ARGUMENT;
+    int32_t dim[3];
+    if (!ecbs_rules::planning_lattice(param, MAX_CELLS, gmin, gmax, gres, dim)) return RBP_ERR_BAD_ARGUMENT;
     for (int a = 0; a < 3; ++a) dim_out[a] = dim[a];
     if (!obstacle) return RBP_OK;  // (only the shape was asked for)
     const size_t ncell = (size_t)dim[0] * dim[1] * dim[2];
@@ -282,18 +258,16 @@ extern "C" int rbp_ecbs_obstacles(const rbp_world_buf* world, const rbp_mission*
     memset(obstacle, 0, ncell);
     double r = 0;
     for (int qi = 0; qi < mission->N; ++qi) r = std::max(r, mission->radius[qi]);
-    for (double k = gmin[2]; k < gmax[2] + eps; k += gres[2])
-        for (double i = gmin[0]; i < gmax[0] + eps; i += gres[0])
-            for (double j = gmin[1]; j < gmax[1] + eps; j += gres[1]) {
-                float d = world_distance(world, (float)i, (float)j, (float)k);
+    std::vector<float> pos[3];
+    std::vector<int> cell[3];
+    ecbs_rules::lattice_samples(gmin, gmax, gres, dim, pos, cell);
+    for (size_t k = 0; k < pos[2].size(); ++k)  // the reference's nesting: z, x, y
+        for (size_t i = 0; i < pos[0].size(); ++i)
+            for (size_t j = 0; j < pos[1].size(); ++j) {
+                float d = world_distance(world, pos[0][i], pos[1][j], pos[2][k]);
                 if (d < 0) return 1;
-                if (d < r + param->grid_margin) {
-                    int x = (int)std::round((i - gmin[0]) / gres[0]);
-                    int y = (int)std::round((j - gmin[1]) / gres[1]);
-                    int z = (int)std::round((k - gmin[2]) / gres[2]);
-                    if (x >= 0 && y >= 0 && z >= 0 && x < dim[0] && y < dim[1] && z < dim[2])
-                        obstacle[((size_t)x * dim[1] + y) * dim[2] + z] = 1;
-                }
+                const int x = cell[0][i], y = cell[1][j], z = cell[2][k];
+                if (d < r + param->grid_margin && x >= 0 && y >= 0 && z >= 0) obstacle[((size_t)x * dim[1] + y) * dim[2] + z] = 1;
             }
     return RBP_OK;
 }
@@ -318,8 +292,8 @@ extern "C" int rbp_ecbs_plan_obstacles(const int32_t dim_in[3], const uint8_t* o
     memset(out, 0, sizeof(*out));
     const int N = mission->N;
     double gmin[3], gmax[3], gres[3];
-    int dim[3];
-    if (!planning_grid(param, gmin, gmax, gres, dim)) return RBP_ERR_BAD_ARGUMENT;
+    int32_t dim[3];
+    if (!ecbs_rules::planning_lattice(param, MAX_CELLS, gmin, gmax, gres, dim)) return RBP_ERR_BAD_ARGUMENT;
     if (dim_in[0] != dim[0] || dim_in[1] != dim[1] || dim_in[2] != dim[2]) return RBP_ERR_BAD_ARGUMENT;  // a mask of another lattice
     Grid g;
     g.dimx = dim[0], g.dimy = dim[1], g.dimz = dim[2];
@@ -329,12 +303,12 @@ extern "C" int rbp_ecbs_plan_obstacles(const int32_t dim_in[3], const uint8_t* o
     // ecbs_planner.hpp:112-136
     std::vector<Cell> starts(N), goals(N);
     for (int i = 0; i < N; ++i) {
+        int s[3], e[3];  // (a position off the lattice is -1 on that axis: blocked)
         for (int a = 0; a < 3; ++a) {
-            int s = (int)std::round((mission->start[9 * i + a] - gmin[a]) / gres[a]);
-            int e = (int)std::round((mission->goal[9 * i + a] - gmin[a]) / gres[a]);
-            (a == 0 ? starts[i].x : a == 1 ? starts[i].y : starts[i].z) = s;
-            (a == 0 ? goals[i].x : a == 1 ? goals[i].y : goals[i].z) = e;
+            s[a] = ecbs_rules::position_to_cell(mission->start[9 * i + a], gmin[a], gres[a], dim[a]);
+            e[a] = ecbs_rules::position_to_cell(mission->goal[9 * i + a], gmin[a], gres[a], dim[a]);
         }
+        starts[i] = {s[0], s[1], s[2]}, goals[i] = {e[0], e[1], e[2]};
         if (g.blocked(starts[i].x, starts[i].y, starts[i].z) || g.blocked(goals[i].x, goals[i].y, goals[i].z)) return 1;
     }
 
@@ -344,7 +318,6 @@ extern "C" int rbp_ecbs_plan_obstacles(const int32_t dim_in[3], const uint8_t* o
     auto root = std::make_shared<HLNode>();
     root->sol.resize(N);
     root->cost.assign(N, 0);
-    root->fmin.assign(N, 0);
     root->cons.resize(N);
     for (int i = 0; i < N; ++i) root->cons[i] = std::make_shared<Constraints>();
     for (int i = 0; i < N; ++i) {
@@ -352,9 +325,7 @@ extern "C" int rbp_ecbs_plan_obstacles(const int32_t dim_in[3], const uint8_t* o
         if (!low_level(g, i, starts[i], goals[i], *root->cons[i], root->sol, w, ll_expanded, res)) return 2;
         root->sol[i] = res.path;
         root->cost[i] = res.cost;
-        root->fmin[i] = res.fmin;
         root->total += res.cost;
-        root->lb += res.fmin;
     }
     root->focal = count_conflicts(g, root->sol);
 
@@ -403,15 +374,12 @@ extern "C" int rbp_ecbs_plan_obstacles(const int32_t dim_in[3], const uint8_t* o
                 nc->vertex.insert(pack4(c.t, a.x, a.y, a.z));          // environment.hpp:593-599
             child->cons[ag] = nc;
             child->total -= child->cost[ag];
-            child->lb -= child->fmin[ag];
             LowLevelResult res;
             bool ok = low_level(g, ag, starts[ag], goals[ag], *nc, child->sol, w, ll_expanded, res);
             if (ok) {
                 child->sol[ag] = res.path;
                 child->cost[ag] = res.cost;
-                child->fmin[ag] = res.fmin;
                 child->total += res.cost;
-                child->lb += res.fmin;
                 child->focal = count_conflicts(g, child->sol);
                 all.push_back(child);
                 open.insert({child->total, child->id});
@@ -425,32 +393,17 @@ extern "C" int rbp_ecbs_plan_obstacles(const int32_t dim_in[3], const uint8_t* o
     if (!goal_node) return 2;
 
     // ecbs_planner.hpp:34-70
-    int makespan = 0, sum = 0;
-    for (int i = 0; i < N; ++i) {
-        makespan = std::max(makespan, goal_node->cost[i]);
-        sum += goal_node->cost[i];
-    }
-    const int M = makespan + 2;
+    const std::vector<Path>& sol = goal_node->sol;  // (a path's cost is its cell count - 1)
+    auto len_of = [&](int a) { return (int)sol[a].size(); };
+    const int M = ecbs_rules::plan_segments(N, len_of, &out->makespan, &out->sum_cost);
     out->N = N;
     out->M = M;
-    out->makespan = makespan;
-    out->sum_cost = sum;
     out->high_level_expanded = hl_expanded;
     out->low_level_expanded = ll_expanded;
     out->T = (double*)malloc(sizeof(double) * (M + 1));
-    for (int i = 0; i <= M; ++i) out->T[i] = i * param->time_step;
     out->init_traj = (float*)malloc(sizeof(float) * (size_t)N * (M + 1) * 3);
-    for (int a = 0; a < N; ++a) {
-        float* tr = out->init_traj + (size_t)a * (M + 1) * 3;
-        int n = 0;
-        auto push = [&](double x, double y, double z) {
-            tr[3 * n] = (float)x, tr[3 * n + 1] = (float)y, tr[3 * n + 2] = (float)z;
-            ++n;
-        };
-        push(mission->start[9 * a], mission->start[9 * a + 1], mission->start[9 * a + 2]);
-        for (auto& c : goal_node->sol[a]) push(c.x * gres[0] + gmin[0], c.y * gres[1] + gmin[1], c.z * gres[2] + gmin[2]);
-        while (n <= makespan + 2) push(mission->goal[9 * a], mission->goal[9 * a + 1], mission->goal[9 * a + 2]);
-    }
+    ecbs_rules::write_plan(M, N, len_of, [&](int a, int p) { return CellXYZ{sol[a][p]}; }, mission->start, mission->goal, gmin, gres,
+                           param->time_step, (size_t)M + 1, out->T, out->init_traj);
     return RBP_OK;
 }
 

@@ -4,7 +4,7 @@
 // A*-epsilon over (t, x, y, z), the final statistics), run where the missions already are.  The host library is the reference, and the
 // device search returns ITS bits: every queue of ecbs.cpp has a total order that ends in a node id, so the minimum std::set::begin()
 // returns is the minimum a lane-strided scan with a wave reduction finds over an unordered array; everything is integer arithmetic apart
-// from the two conflict predicates, restated in double without contraction (f64 sqrt and division are correctly rounded here as there).
+// from the two conflict predicates; those, the planning lattice, position -> cell and the writer of T / init_traj are read from common/ecbs_rules.h.
 //
 // One workgroup is one wavefront; it takes missions from an atomic counter until none is left, so the grid is sized to the device and the
 // workspace belongs to the wave SLOT: a low-level node pool with its open array, a "seen" bitmap over (t, cell), a high-level node pool.
@@ -19,18 +19,16 @@
 //               count_conflicts / first_conflict: per time step and agent i, lanes are the agents j > i.
 // In-focal membership is explicit state, set by the host's two rules only (at creation, at a widening): at the high level the bound can
 // go DOWN, and the host's focal set then keeps nodes the current bound would exclude.
-// LowLevelResult::fmin / HLNode::lb are computed by the host and read by nothing; they are not computed here.
 // Every loop is bounded (node pools, the high-level budget, t_limit), nothing waits for another wave.  A mission that exceeds a device
 // capacity ends with status 3 (RBP_ECBS_CAPACITY) and the wave takes the next one.
 #include "rbp_dev.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#pragma clang fp contract(off)  // the conflict predicates give the host's booleans only without fused multiply-adds
+#include "common/ecbs_rules.h"
 
 namespace {
 
@@ -90,9 +88,16 @@ struct Slot {  // what one wave works on
     int *len, *owner;
 };
 
-__device__ __forceinline__ int cx(unsigned c) { return (int)(c & 1023u); }
-__device__ __forceinline__ int cy(unsigned c) { return (int)((c >> 10) & 1023u); }
-__device__ __forceinline__ int cz(unsigned c) { return (int)(c >> 20); }
+__host__ __device__ __forceinline__ int cx(unsigned c) { return (int)(c & 1023u); }
+__host__ __device__ __forceinline__ int cy(unsigned c) { return (int)((c >> 10) & 1023u); }
+__host__ __device__ __forceinline__ int cz(unsigned c) { return (int)(c >> 20); }
+struct PackedCell {  // a packed cell as the conflict rules and the plan writer of common/ecbs_rules.h read one
+    unsigned c;
+    __host__ __device__ int x() const { return cx(c); }
+    __host__ __device__ int y() const { return cy(c); }
+    __host__ __device__ int z() const { return cz(c); }
+    __host__ __device__ bool operator==(const PackedCell& o) const { return c == o.c; }
+};
 __device__ __forceinline__ unsigned pack_cell(int x, int y, int z) { return (unsigned)x | ((unsigned)y << 10) | ((unsigned)z << 20); }
 
 __device__ __forceinline__ int wave_min(int v) {
@@ -116,31 +121,11 @@ __device__ __forceinline__ void wave_argmin(unsigned long long& key, unsigned& i
     }
 }
 
-// ecbs.cpp vertex_conflict (environment.hpp:656-664)
 __device__ __forceinline__ bool vertex_conflict(double rr, double grid, unsigned a, unsigned b) {
-    if (rr < grid) return a == b;
-    const double dx = cx(b) - cx(a), dy = cy(b) - cy(a), dz = cz(b) - cz(a);
-    return __dsqrt_rn(dx * dx + dy * dy + dz * dz) * grid < rr;
+    return ecbs_rules::vertex_conflict(rr, grid, PackedCell{a}, PackedCell{b});
 }
-
-// ecbs.cpp edge_conflict (environment.hpp:69-93, :666-681)
 __device__ __forceinline__ bool edge_conflict(double rr, double grid, unsigned a1, unsigned b1, unsigned a2, unsigned b2) {
-    if (rr < grid * 0.5) return a1 == b2 && b1 == a2;
-    const double ax = cx(a2) - cx(a1), ay = cy(a2) - cy(a1), az = cz(a2) - cz(a1);
-    const double bx = cx(b2) - cx(b1), by = cy(b2) - cy(b1), bz = cz(b2) - cz(b1);
-    double md = __dsqrt_rn(ax * ax + ay * ay + az * az);
-    if (!(ax == bx && ay == by && az == bz)) {
-        double d = __dsqrt_rn(bx * bx + by * by + bz * bz);
-        if (md > d) md = d;
-        double nx = bx - ax, ny = by - ay, nz = bz - az;
-        const double nn = __dsqrt_rn(nx * nx + ny * ny + nz * nz);
-        nx = __ddiv_rn(nx, nn), ny = __ddiv_rn(ny, nn), nz = __ddiv_rn(nz, nn);
-        const double adn = ax * nx + ay * ny + az * nz;
-        const double px = ax - nx * adn, py = ay - ny * adn, pz = az - nz * adn;
-        d = __dsqrt_rn(px * px + py * py + pz * pz);
-        if ((px - ax) * (px - bx) + (py - ay) * (py - by) + (pz - az) * (pz - bz) < 0 && md > d) md = d;
-    }
-    return md * grid <= rr;
+    return ecbs_rules::edge_conflict(rr, grid, PackedCell{a1}, PackedCell{b1}, PackedCell{a2}, PackedCell{b2});
 }
 
 // state of agent i at time t: path[min(t, size - 1)]
@@ -531,29 +516,6 @@ size_t ecbs_lds_bytes(int N, int stride, bool sol_in_lds) {
 
 int seen_layers(const int dim[3], int max_M) { return 8 * (dim[0] + dim[1] + dim[2]) + 64 + (max_M - 2) + 2; }
 
-struct DeviceBuffers {  // freed when the call returns
-    std::vector<void*> ptrs;
-    hipError_t err = hipSuccess;
-    template <class T>
-    T* get(size_t count, bool zero = false) {
-        void* p = nullptr;
-        if (err == hipSuccess) err = hipMalloc(&p, std::max<size_t>(sizeof(T) * count, 16));
-        if (err != hipSuccess) return nullptr;
-        ptrs.push_back(p);
-        if (zero) err = hipMemsetAsync(p, 0, sizeof(T) * count, 0);
-        return static_cast<T*>(p);
-    }
-    template <class T>
-    T* upload(const std::vector<T>& v) {
-        T* p = get<T>(v.size());
-        if (p && !v.empty()) err = hipMemcpy(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
-        return p;
-    }
-    ~DeviceBuffers() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-};
-
 }  // namespace
 
 int ecbs_check_arguments(const char* who, int32_t K, const int32_t* dim_in, const rbp_mission* missions, const rbp_param* param,
@@ -572,7 +534,7 @@ int ecbs_check_arguments(const char* who, int32_t K, const int32_t* dim_in, cons
     }
     double gmin[3], gmax[3], gres[3];
     int d[3];
-    if (!planning_lattice(param, ECBS_MAX_DIM, gmin, gmax, gres, d)) return bad("the planning lattice needs 1..1024 cells per axis");
+    if (!ecbs_rules::planning_lattice(param, ECBS_MAX_DIM, gmin, gmax, gres, d)) return bad("the planning lattice needs 1..1024 cells per axis");
     if (dim_in && (dim_in[0] != d[0] || dim_in[1] != d[1] || dim_in[2] != d[2])) return bad("dim is not the planning lattice of param");
     const size_t seen_bytes = (size_t)seen_layers(d, out->max_M) * (((size_t)d[0] * d[1] * d[2] + 31) / 32) * 4;
     if (seen_bytes > ECBS_MAX_SEEN_BYTES) return bad("lattice x time layers beyond the 16 MB seen bitmap of a wave");
@@ -585,7 +547,7 @@ int ecbs_plan_on_device(const char* who, int32_t K, const int32_t dim[3], const 
     const int N = missions[0].N, max_M = out->max_M;
     double gmin[3], gmax[3], gres[3];
     int gd[3];
-    planning_lattice(param, ECBS_MAX_DIM, gmin, gmax, gres, gd);
+    ecbs_rules::planning_lattice(param, ECBS_MAX_DIM, gmin, gmax, gres, gd);
     // every mission starts as "no result"
     const size_t t_stride = (size_t)max_M + 1, traj_stride = (size_t)N * t_stride * 3;
     for (int k = 0; k < K; ++k) out->status[k] = out->M[k] = out->makespan[k] = out->sum_cost[k] = 0, out->high_level_expanded[k] = out->low_level_expanded[k] = 0;
@@ -595,10 +557,7 @@ int ecbs_plan_on_device(const char* who, int32_t K, const int32_t dim[3], const 
     // ecbs_planner.hpp:112-136: the cells of the start and goal positions (anything off the lattice is "occluded")
     std::vector<int> start((size_t)K * N * 3), goal(start.size());
     std::vector<double> radius((size_t)K * N);
-    auto cell = [&](double v, int a) {
-        const double c = std::round((v - gmin[a]) / gres[a]);
-        return c >= 0 && c < gd[a] ? (int)c : -1;
-    };
+    auto cell = [&](double v, int a) { return ecbs_rules::position_to_cell(v, gmin[a], gres[a], gd[a]); };
     for (int k = 0; k < K; ++k)
         for (int i = 0; i < N; ++i) {
             radius[(size_t)k * N + i] = missions[k].radius[i];
@@ -655,33 +614,14 @@ int ecbs_plan_on_device(const char* who, int32_t K, const int32_t dim[3], const 
     if (e == hipSuccess) e = hipMemcpy(count.data(), d.out_count, sizeof(long long) * count.size(), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(e, "results");
 
-    // ecbs_planner.hpp:34-70, with the host's expressions: waypoints in double, then octomap::point3d's float
     for (int k = 0; k < K; ++k) {
         out->status[k] = status[k];
         if (status[k]) continue;
-        int makespan = 0, sum = 0;
-        for (int i = 0; i < N; ++i) {
-            makespan = std::max(makespan, len[(size_t)k * N + i] - 1);
-            sum += len[(size_t)k * N + i] - 1;
-        }
-        const int M = makespan + 2;  // <= max_M: no path is longer than max_M - 2
-        out->M[k] = M, out->makespan[k] = makespan, out->sum_cost[k] = sum;
+        auto len_of = [&](int a) { return len[(size_t)k * N + a]; };
+        out->M[k] = ecbs_rules::plan_segments(N, len_of, &out->makespan[k], &out->sum_cost[k]);  // <= max_M: no path is longer than max_M - 2
         out->high_level_expanded[k] = count[2 * (size_t)k], out->low_level_expanded[k] = count[2 * (size_t)k + 1];
-        for (int i = 0; i <= M; ++i) out->T[k * t_stride + i] = i * param->time_step;
-        for (int a = 0; a < N; ++a) {
-            float* tr = out->init_traj + k * traj_stride + a * t_stride * 3;
-            int n = 0;
-            auto push = [&](double x, double y, double z) {
-                tr[3 * n] = (float)x, tr[3 * n + 1] = (float)y, tr[3 * n + 2] = (float)z;
-                ++n;
-            };
-            const double *st = missions[k].start + 9 * a, *go = missions[k].goal + 9 * a;
-            push(st[0], st[1], st[2]);
-            const unsigned* c = path.data() + ((size_t)k * N + a) * d.stride;
-            for (int p = 0; p < len[(size_t)k * N + a]; ++p)
-                push((int)(c[p] & 1023u) * gres[0] + gmin[0], (int)((c[p] >> 10) & 1023u) * gres[1] + gmin[1], (int)(c[p] >> 20) * gres[2] + gmin[2]);
-            while (n <= makespan + 2) push(go[0], go[1], go[2]);
-        }
+        ecbs_rules::write_plan(out->M[k], N, len_of, [&](int a, int p) { return PackedCell{path[((size_t)k * N + a) * d.stride + p]}; }, missions[k].start,
+                               missions[k].goal, gmin, gres, param->time_step, t_stride, out->T + k * t_stride, out->init_traj + k * traj_stride);
     }
     return RBP_OK;
 }

@@ -21,6 +21,8 @@
 #include <string>
 #include <vector>
 
+#include "common/ecbs_rules.h"
+
 namespace {
 
 constexpr int EDT_INF = 0x3f3f3f3f;
@@ -144,7 +146,7 @@ __global__ __launch_bounds__(256) void edt_set_x_finish_kernel(const EdtWorldDes
 // ---- the coarse obstacle mask of the ECBS front-end from a resident grid (ECBSPlanner::setObstacles, ecbs_planner.hpp:80-109) ----------
 // One thread per sample (x, y, z) of the planning lattice: getDistance's lookup and `dist < r + grid_margin` in double.  xs / ys / zs hold the
 // sample coordinates as float (octomap::point3d), cx / cy / cz the mask cell of each sample (-1: none), both made on the host by the
-// reference's own loops.  A sample outside the grid sets *outside.
+// reference's own loops (common/ecbs_rules.h lattice_samples).  A sample outside the grid sets *outside.
 __device__ __forceinline__ void ecbs_obstacle_sample(const DevWorld& w, const float* __restrict__ xs, const float* __restrict__ ys,
                                                      const float* __restrict__ zs, const int* __restrict__ cx, const int* __restrict__ cy,
                                                      const int* __restrict__ cz, int sx, int sy, int sz, int dimy, int dimz, double limit,
@@ -164,14 +166,7 @@ __device__ __forceinline__ void ecbs_obstacle_sample(const DevWorld& w, const fl
     if ((double)d < limit && cx[a] >= 0 && cy[b] >= 0 && cz[c] >= 0) mask[((size_t)cx[a] * dimy + cy[b]) * dimz + cz[c]] = 1;
 }
 
-__global__ __launch_bounds__(256) void ecbs_obstacle_kernel(DevWorld w, const float* __restrict__ xs, const float* __restrict__ ys,
-                                                            const float* __restrict__ zs, const int* __restrict__ cx, const int* __restrict__ cy,
-                                                            const int* __restrict__ cz, int sx, int sy, int sz, int dimy, int dimz, double limit,
-                                                            unsigned char* __restrict__ mask, unsigned* __restrict__ outside) {
-    ecbs_obstacle_sample(w, xs, ys, zs, cx, cy, cz, sx, sy, sz, dimy, dimz, limit, mask, outside);
-}
-
-// the same for K missions in one launch (blockIdx.y): mission k reads worlds[k] against limits[k] and writes masks[k][ncell], outside[k]
+// K missions in one launch (blockIdx.y): mission k reads worlds[k] against limits[k] and writes masks[k][ncell], outside[k]
 __global__ __launch_bounds__(256) void ecbs_obstacle_set_kernel(const DevWorld* __restrict__ worlds, const double* __restrict__ limits,
                                                                 const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
                                                                 const int* __restrict__ cx, const int* __restrict__ cy, const int* __restrict__ cz, int sx,
@@ -206,18 +201,58 @@ struct rbp_dev_worlds {
 
 namespace {
 
-// the planning lattice and its samples, by the reference's own loops (init_traj_planner.hpp:19-29, ecbs_planner.hpp:80-109): per axis the
-// sample coordinates as float (octomap::point3d) and the mask cell of each sample (-1: none); an error text on a bad lattice
-const char* lattice_samples(const rbp_param* param, int32_t dim[3], std::vector<float> pos[3], std::vector<int> cell[3]) {
-    const double eps = SP_EPSILON;
+// The obstacle masks of K missions on resident worlds, made where the grids are and left there: [K][ncell] bytes, padded to a word, then the
+// K flag words (a lattice sample lay outside the world's grid).  The buffers (the kernel's inputs too) are freed with the struct.
+struct EcbsMasks {
+    DeviceBuffers buffers;
+    unsigned char* mask = nullptr;
+    size_t mask_bytes = 0;
+    const unsigned* outside() const { return reinterpret_cast<const unsigned*>(mask + mask_bytes); }
+};
+
+// Fills `m` on the current device (that of `ws`) for missions that read worlds world_index[k], launches queued on the null stream; dim receives the lattice.
+int ecbs_masks_on_device(const char* who, const rbp_dev_worlds* ws, int K, const int32_t* world_index, const rbp_mission* missions,
+                         const rbp_param* param, int32_t dim[3], EcbsMasks& m) {
+    auto bad = [&](const char* what) { return rbp_set_error(RBP_ERR_BAD_ARGUMENT, (std::string(who) + ": " + what).c_str()); };
     double gmin[3], gmax[3], gres[3];
-    if (!planning_lattice(param, 4096, gmin, gmax, gres, dim)) return "grid resolution must be positive, planning grid of 1..4096 cells per axis";
-    for (int a = 0; a < 3; ++a)
-        for (double i = gmin[a]; i < gmax[a] + eps; i += gres[a]) {
-            const int c = (int)std::round((i - gmin[a]) / gres[a]);
-            pos[a].push_back((float)i), cell[a].push_back(c >= 0 && c < dim[a] ? c : -1);
-        }
-    return nullptr;
+    if (!ecbs_rules::planning_lattice(param, 4096, gmin, gmax, gres, dim)) return bad("grid resolution must be positive, planning grid of 1..4096 cells per axis");
+    std::vector<float> pos[3];
+    std::vector<int> cell[3];
+    ecbs_rules::lattice_samples(gmin, gmax, gres, dim, pos, cell);
+    const int sx = (int)pos[0].size(), sy = (int)pos[1].size(), sz = (int)pos[2].size(), ns = sx + sy + sz;
+    if ((double)sx * sy * sz > (double)(1 << 30)) return bad("more than 2^30 samples");
+    const size_t ncell = (size_t)dim[0] * dim[1] * dim[2];
+    m.mask_bytes = ((size_t)K * ncell + 3) & ~size_t(3);
+    std::vector<int> up(2 * (size_t)ns);  // the sample coordinates of the three axes, then their mask cells
+    for (int a = 0, o = 0; a < 3; o += (int)pos[a].size(), ++a) {
+        memcpy(&up[o], pos[a].data(), sizeof(float) * pos[a].size());
+        memcpy(&up[ns + o], cell[a].data(), sizeof(int) * cell[a].size());
+    }
+    std::vector<DevWorld> worlds(K);
+    std::vector<double> limits(K);
+    for (int k = 0; k < K; ++k) {
+        const EdtWorldDesc& d = ws->desc[world_index[k]];
+        for (int a = 0; a < 3; ++a) worlds[k].dim[a] = d.dim[a], worlds[k].key_min[a] = d.kmin[a];
+        worlds[k].res = d.res, worlds[k].dist = ws->dist + d.cell_off;
+        double r = 0;
+        for (int qi = 0; qi < missions[k].N; ++qi) r = std::max(r, missions[k].radius[qi]);
+        limits[k] = r + param->grid_margin;
+    }
+    const int* c = m.buffers.upload(up);
+    const DevWorld* d_worlds = m.buffers.upload(worlds);
+    const double* d_limits = m.buffers.upload(limits);
+    m.mask = m.buffers.get<unsigned char>(m.mask_bytes + 4 * (size_t)K, true);
+    hipError_t e = m.buffers.err;
+    const float* f = reinterpret_cast<const float*>(c);
+    c += ns;
+    for (int k0 = 0; k0 < K && e == hipSuccess; k0 += 32768) {  // (grid dimension y)
+        const int nk = std::min(K - k0, 32768);
+        hipLaunchKernelGGL(ecbs_obstacle_set_kernel, dim3((unsigned)(((size_t)sx * sy * sz + 255) / 256), nk), dim3(256), 0, 0, d_worlds + k0, d_limits + k0, f,
+                           f + sx, f + sx + sy, c, c + sx, c + sx + sy, sx, sy, sz, dim[0], dim[1], dim[2], m.mask + (size_t)k0 * ncell,
+                           reinterpret_cast<unsigned*>(m.mask + m.mask_bytes) + k0);
+        e = hipGetLastError();
+    }
+    return e == hipSuccess ? RBP_OK : rbp_set_error(RBP_ERR_HIP, (std::string(who) + ": " + hipGetErrorString(e)).c_str());
 }
 
 // builds the grids of `ws` (desc filled but for chunk_off; ws->dist allocated) on the current device; returns when they are complete
@@ -411,50 +446,25 @@ extern "C" void rbp_dev_worlds_destroy(rbp_dev_worlds* ws) {
 
 extern "C" int rbp_dev_worlds_ecbs_obstacles(const rbp_dev_worlds* ws, int32_t w, const rbp_mission* mission, const rbp_param* param, int32_t dim[3],
                                              uint8_t* obstacle_host, size_t capacity) {
+    const char* who = "rbp_dev_worlds_ecbs_obstacles";
+    auto bad = [&](const char* what) { return rbp_set_error(RBP_ERR_BAD_ARGUMENT, (std::string(who) + ": " + what).c_str()); };
     rbp_world g;
-    if (!mission || !param || !dim || mission->N <= 0 || !mission->radius) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_ecbs_obstacles: null argument");
+    if (!mission || !param || !dim || mission->N <= 0 || !mission->radius) return bad("null argument");
     if (int rc = rbp_dev_worlds_get(ws, w, &g)) return rc;
-    std::vector<float> pos[3];
-    std::vector<int> cell[3];
-    if (const char* what = lattice_samples(param, dim, pos, cell)) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, (std::string("rbp_dev_worlds_ecbs_obstacles: ") + what).c_str());
+    double gmin[3], gmax[3], gres[3];
+    if (!ecbs_rules::planning_lattice(param, 4096, gmin, gmax, gres, dim)) return bad("grid resolution must be positive, planning grid of 1..4096 cells per axis");
     if (!obstacle_host) return RBP_OK;  // (only the shape was asked for)
     const size_t ncell = (size_t)dim[0] * dim[1] * dim[2];
-    if (capacity < ncell) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_ecbs_obstacles: obstacle buffer smaller than dim[0] * dim[1] * dim[2]");
-    double r = 0;
-    for (int qi = 0; qi < mission->N; ++qi) r = std::max(r, mission->radius[qi]);
-    const int sx = (int)pos[0].size(), sy = (int)pos[1].size(), sz = (int)pos[2].size(), ns = sx + sy + sz;
-    if ((double)sx * sy * sz > (double)(1 << 30)) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_ecbs_obstacles: more than 2^30 samples");
-    // one upload (sample coordinates, then their mask cells), one buffer back (the mask, then the flag word)
-    std::vector<int> up(2 * (size_t)ns);
-    for (int a = 0, o = 0; a < 3; o += (int)pos[a].size(), ++a) {
-        memcpy(&up[o], pos[a].data(), sizeof(float) * pos[a].size());
-        memcpy(&up[ns + o], cell[a].data(), sizeof(int) * cell[a].size());
-    }
-    const size_t mask_bytes = (ncell + 3) & ~size_t(3);
-    std::vector<unsigned char> back(mask_bytes + 4);
+    if (capacity < ncell) return bad("obstacle buffer smaller than dim[0] * dim[1] * dim[2]");
     DeviceScope scope(ws->device);
-    int* d_up = nullptr;
-    unsigned char* d_mask = nullptr;
-    hipError_t e = hipMalloc((void**)&d_up, sizeof(int) * up.size());
-    if (e == hipSuccess) e = hipMalloc((void**)&d_mask, back.size());
-    if (e == hipSuccess) e = hipMemcpy(d_up, up.data(), sizeof(int) * up.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemsetAsync(d_mask, 0, back.size(), 0);
-    if (e == hipSuccess) {
-        DevWorld dw;
-        for (int a = 0; a < 3; ++a) dw.dim[a] = g.dim[a], dw.key_min[a] = g.key_min[a];
-        dw.res = g.res, dw.dist = g.dist;
-        const float* f = reinterpret_cast<const float*>(d_up);
-        const int* c = d_up + ns;
-        hipLaunchKernelGGL(ecbs_obstacle_kernel, dim3((unsigned)(((size_t)sx * sy * sz + 255) / 256)), dim3(256), 0, 0, dw, f, f + sx, f + sx + sy, c, c + sx,
-                           c + sx + sy, sx, sy, sz, dim[1], dim[2], r + param->grid_margin, d_mask, reinterpret_cast<unsigned*>(d_mask + mask_bytes));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(back.data(), d_mask, back.size(), hipMemcpyDeviceToHost);
-    (void)hipFree(d_up), (void)hipFree(d_mask);
-    if (e != hipSuccess) return rbp_set_error(RBP_ERR_HIP, (std::string("rbp_dev_worlds_ecbs_obstacles: ") + hipGetErrorString(e)).c_str());
+    EcbsMasks m;
+    if (int rc = ecbs_masks_on_device(who, ws, 1, &w, mission, param, dim, m)) return rc;
+    std::vector<unsigned char> back(m.mask_bytes + 4);  // one buffer back: the mask, then the flag word
+    const hipError_t e = hipMemcpy(back.data(), m.mask, back.size(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return rbp_set_error(RBP_ERR_HIP, (std::string(who) + ": " + hipGetErrorString(e)).c_str());
     memcpy(obstacle_host, back.data(), ncell);
     unsigned outside = 0;
-    memcpy(&outside, back.data() + mask_bytes, 4);
+    memcpy(&outside, back.data() + m.mask_bytes, 4);
     return outside ? 1 : RBP_OK;
 }
 
@@ -464,58 +474,12 @@ extern "C" int rbp_dev_worlds_ecbs_plan(const rbp_dev_worlds* ws, int32_t K, con
     const char* who = "rbp_dev_worlds_ecbs_plan";
     auto bad = [&](const char* what) { return rbp_set_error(RBP_ERR_BAD_ARGUMENT, (std::string(who) + ": " + what).c_str()); };
     if (!ws || !world_index) return bad("need the set of worlds and world_index");
-    int32_t dim[3];
+    int32_t dim[3], sdim[3];
     if (int rc = ecbs_check_arguments(who, K, nullptr, missions, param, max_high_level_nodes, out, dim)) return rc;
     for (int k = 0; k < K; ++k)
         if (world_index[k] < 0 || world_index[k] >= (int)ws->desc.size()) return bad("world index out of range");
-    std::vector<float> pos[3];
-    std::vector<int> cell[3];
-    int32_t sdim[3];
-    if (const char* what = lattice_samples(param, sdim, pos, cell)) return bad(what);
-    const int sx = (int)pos[0].size(), sy = (int)pos[1].size(), sz = (int)pos[2].size(), ns = sx + sy + sz;
-    const size_t ncell = (size_t)dim[0] * dim[1] * dim[2], mask_bytes = ((size_t)K * ncell + 3) & ~size_t(3);
-    std::vector<int> up(2 * (size_t)ns);
-    for (int a = 0, o = 0; a < 3; o += (int)pos[a].size(), ++a) {
-        memcpy(&up[o], pos[a].data(), sizeof(float) * pos[a].size());
-        memcpy(&up[ns + o], cell[a].data(), sizeof(int) * cell[a].size());
-    }
-    std::vector<DevWorld> worlds(K);
-    std::vector<double> limits(K);
-    for (int k = 0; k < K; ++k) {
-        const EdtWorldDesc& d = ws->desc[world_index[k]];
-        for (int a = 0; a < 3; ++a) worlds[k].dim[a] = d.dim[a], worlds[k].key_min[a] = d.kmin[a];
-        worlds[k].res = d.res, worlds[k].dist = ws->dist + d.cell_off;
-        double r = 0;
-        for (int qi = 0; qi < missions[k].N; ++qi) r = std::max(r, missions[k].radius[qi]);
-        limits[k] = r + param->grid_margin;
-    }
     DeviceScope scope(ws->device);
-    int* d_up = nullptr;
-    DevWorld* d_worlds = nullptr;
-    double* d_limits = nullptr;
-    unsigned char* d_mask = nullptr;  // the K masks, then the K flag words
-    hipError_t e = hipMalloc((void**)&d_up, sizeof(int) * up.size());
-    if (e == hipSuccess) e = hipMalloc((void**)&d_worlds, sizeof(DevWorld) * K);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_limits, sizeof(double) * K);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_mask, mask_bytes + 4 * (size_t)K);
-    if (e == hipSuccess) e = hipMemcpy(d_up, up.data(), sizeof(int) * up.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_worlds, worlds.data(), sizeof(DevWorld) * K, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_limits, limits.data(), sizeof(double) * K, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemsetAsync(d_mask, 0, mask_bytes + 4 * (size_t)K, 0);
-    int rc = RBP_OK;
-    if (e == hipSuccess) {
-        const float* f = reinterpret_cast<const float*>(d_up);
-        const int* c = d_up + ns;
-        for (int k0 = 0; k0 < K && e == hipSuccess; k0 += 32768) {  // (grid dimension y)
-            const int nk = std::min(K - k0, 32768);
-            hipLaunchKernelGGL(ecbs_obstacle_set_kernel, dim3((unsigned)(((size_t)sx * sy * sz + 255) / 256), nk), dim3(256), 0, 0, d_worlds + k0, d_limits + k0, f,
-                               f + sx, f + sx + sy, c, c + sx, c + sx + sy, sx, sy, sz, dim[0], dim[1], dim[2], d_mask + (size_t)k0 * ncell,
-                               reinterpret_cast<unsigned*>(d_mask + mask_bytes) + k0);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) rc = ecbs_plan_on_device(who, K, dim, d_mask, reinterpret_cast<const unsigned*>(d_mask + mask_bytes), missions, param, max_high_level_nodes, out);
-    }
-    (void)hipFree(d_up), (void)hipFree(d_worlds), (void)hipFree(d_limits), (void)hipFree(d_mask);
-    if (e != hipSuccess) return rbp_set_error(RBP_ERR_HIP, (std::string(who) + ": " + hipGetErrorString(e)).c_str());
-    return rc;
+    EcbsMasks m;
+    if (int rc = ecbs_masks_on_device(who, ws, K, world_index, missions, param, sdim, m)) return rc;
+    return ecbs_plan_on_device(who, K, dim, m.mask, m.outside(), missions, param, max_high_level_nodes, out);
 }

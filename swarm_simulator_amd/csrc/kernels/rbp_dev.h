@@ -16,7 +16,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "rbp.h"
 
@@ -125,22 +127,31 @@ struct DeviceScope {  // the calling thread's current device is put back when th
     }
 };
 
-// the planning lattice of the ECBS front-end (init_traj_planner.hpp:19-29; csrc/host/ecbs.cpp planning_grid), the one statement of it on this side:
-// per axis the first and last sample, the step and the cell count.  false when a step is not positive or an axis has no cell or more than max_cells.
-inline bool planning_lattice(const rbp_param* param, int max_cells, double gmin[3], double gmax[3], double gres[3], int32_t dim[3]) {
-    gres[0] = gres[1] = param->grid_xy_res, gres[2] = param->grid_z_res;
-    for (int a = 0; a < 3; ++a) {
-        if (!(gres[a] > 0)) return false;
-        gmin[a] = std::ceil((param->world_min[a] - SP_EPSILON) / gres[a]) * gres[a];
-        gmax[a] = std::floor((param->world_max[a] + SP_EPSILON) / gres[a]) * gres[a];
-        const double n = std::round((gmax[a] - gmin[a]) / gres[a]) + 1;
-        if (!(n > 0) || n > max_cells) return false;
-        dim[a] = (int32_t)n;
+struct DeviceBuffers {  // device allocations of one call, freed when it returns; the first error sticks
+    std::vector<void*> ptrs;
+    hipError_t err = hipSuccess;
+    template <class T>
+    T* get(size_t count, bool zero = false) {
+        void* p = nullptr;
+        if (err == hipSuccess) err = hipMalloc(&p, std::max<size_t>(sizeof(T) * count, 16));
+        if (err != hipSuccess) return nullptr;
+        ptrs.push_back(p);
+        if (zero) err = hipMemsetAsync(p, 0, sizeof(T) * count, 0);
+        return static_cast<T*>(p);
     }
-    return true;
-}
+    template <class T>
+    T* upload(const std::vector<T>& v) {
+        T* p = get<T>(v.size());
+        if (p && !v.empty()) err = hipMemcpy(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
+        return p;
+    }
+    ~DeviceBuffers() {
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+};
 
-// kernels/ecbs.hip: the ECBS search on the device.  ecbs_check_arguments: the argument checks both entry points share (no device work; dim_in
+// kernels/ecbs.hip: the ECBS search on the device (the rules it shares with csrc/host/ecbs.cpp, the planning lattice among them, are in
+// common/ecbs_rules.h).  ecbs_check_arguments: the argument checks both entry points share (no device work; dim_in
 // may be null, dim receives the planning lattice of param).  ecbs_plan_on_device: the search on K masks that are already on the CURRENT
 // device ([K][dim0 * dim1 * dim2] bytes; d_outside [K] or null: missions whose lattice left the world's grid), results into `out`.
 int ecbs_check_arguments(const char* who, int32_t K, const int32_t* dim_in, const rbp_mission* missions, const rbp_param* param,

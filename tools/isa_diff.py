@@ -42,7 +42,7 @@ def functions(asm):
 def compile_tree(tree, pool):
     """{variant: {function: (file, text)}}: the plain files alone, and together with each build of qp.hip"""
     src = os.path.join(tree, "swarm_simulator_amd", "csrc")
-    inc = ["-I" + os.path.join(tree, "include"), "-I" + os.path.join(src, "kernels"), "-I" + os.path.join(src, "abi")]
+    inc = ["-I" + os.path.join(tree, "include"), "-I" + src, "-I" + os.path.join(src, "kernels"), "-I" + os.path.join(src, "abi")]
     run = lambda f, fl: pool.submit(lambda: functions(subprocess.run(["hipcc"] + BASE + inc + fl + [f], check=True, stdout=subprocess.PIPE,
                                                                      stderr=subprocess.DEVNULL, text=True).stdout))
     files = sorted(glob.glob(os.path.join(src, "kernels", "*.hip")))

@@ -6,7 +6,7 @@
 # usage: tools/resource_usage.sh r03
 TAG=${1:-r05}; cd "$(dirname "$0")/../swarm_simulator_amd/csrc" || exit 1
 OUT=../../profiles/${TAG}_resource_usage.txt
-FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include -Ikernels -Iabi --cuda-device-only"
+FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include -I. -Ikernels -Iabi --cuda-device-only"
 one() {  # name, source, extra flags
   echo; echo "## $2 $1"
   hipcc $FL $3 -Rpass-analysis=kernel-resource-usage -c -o /dev/null $2 2>&1 | grep -E "Function Name|SGPRs:|VGPRs:|ScratchSize|Occupancy|Spill|LDS Size" | sed 's/^.*remark: [^ ]* //; s/^ *//'
