@@ -47,7 +47,10 @@
 
 #pragma clang fp contract(fast)
 
+#include "common/ipm_rows.h"  // the arithmetic of a row, shared with qp.hip
+
 namespace {
+using namespace ipm;
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -83,23 +86,11 @@ __host__ __device__ inline JDims jdims(int N, int M) {
     return d;
 }
 
-__constant__ double jc_Qbase[36] = {720,  -1800, 1200,  0,     0,     -120, -1800, 4800,  -3600, 0,     600,   0,
-                                    1200, -3600, 3600,  -1200, 0,     0,    0,     0,     -1200, 3600,  -3600, 1200,
-                                    0,    600,   0,     -3600, 4800,  -1800, -120, 0,     0,     1200,  -1800, 720};
-
-__device__ inline size_t pair_index(int N, int qi, int qj) { return (size_t)qi * N - (size_t)qi * (qi + 1) / 2 + (qj - qi - 1); }
-
 // element (r, c) of a tile-major matrix with nblk tile columns
 __device__ __forceinline__ size_t telem(int nblk, int r, int c) { return ((size_t)(r >> 6) * nblk + (c >> 6)) * JTT + (size_t)(r & 63) * JT + (c & 63); }
 
-__device__ __forceinline__ double fast_rcp(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    r = fma(fma(-x, r, 1.0), r, r);
-    r = fma(fma(-x, r, 1.0), r, r);
-    return r;
-}
-
 // ---- deterministic block reduction (256 threads): op 0 sum, 1 max, 2 min ------------------------------------------------
+// (not qp.hip's DPP reduction: this butterfly adds in a different tree, and merging the two would change bits)
 __device__ __forceinline__ double red_op(double a, double b, int op) { return op == 0 ? a + b : (op == 1 ? fmax(a, b) : fmin(a, b)); }
 __device__ inline double block_reduce(double v, int op, double* red /* >= 4 doubles of LDS */) {
     for (int o = 32; o > 0; o >>= 1) v = red_op(v, __shfl_xor(v, o), op);
@@ -175,21 +166,21 @@ __global__ __launch_bounds__(256) void jq_setup(JArgs A) {
             for (int a = 0; a < 3; ++a)
                 for (int b = 0; b < 3; ++b) {
                     double s = 0;
-                    for (int c = 0; c < 3; ++c) s += jc_Qbase[6 * (3 + a) + 3 + c] * sl * L[3 * c + b];
+                    for (int c = 0; c < 3; ++c) s += Qbase[6 * (3 + a) + 3 + c] * sl * L[3 * c + b];
                     QL[3 * a + b] = s;
                 }
             for (int a = 0; a < 3; ++a)
                 for (int b = 0; b < 3; ++b) {
                     double s = 0;
                     for (int c = 0; c < 3; ++c) s += L[3 * c + a] * QL[3 * c + b];
-                    D[3 * a + b] = 2 * (s + jc_Qbase[6 * a + b] * sr);
+                    D[3 * a + b] = 2 * (s + Qbase[6 * a + b] * sr);
                 }
             if (j + 1 < M) {
                 const double* Ln = w.Lk + 9 * (j + 1);
                 for (int a = 0; a < 3; ++a)
                     for (int b = 0; b < 3; ++b) {
                         double s = 0;
-                        for (int c = 0; c < 3; ++c) s += jc_Qbase[6 * a + 3 + c] * sr * Ln[3 * c + b];
+                        for (int c = 0; c < 3; ++c) s += Qbase[6 * a + 3 + c] * sr * Ln[3 * c + b];
                         E[3 * a + b] = 2 * s;
                     }
             }
@@ -241,7 +232,8 @@ struct PassIO {
     double sum0, sum1, sum2, vmax, vmin;
 };
 
-// one row: see row_op in qp.hip (same arithmetic).  s, z: current state; out: new state (INIT, UPBUILD) through so / zo2.
+// one row, as row_op in qp.hip: the arithmetic is common/ipm_rows.h.  s, z: current state; out: new state (INIT, UPBUILD) through
+// sn_out / zn_out, the target shift (GOND) through sn_out.  BUILD assembles the NEXT iteration's matrix: dregn
 template <int PASS>
 __device__ __forceinline__ void row_op(double slack, double ga, double gd, double s, double z, PassIO& io, double cw, double& wgt, double& v,
                                        double& zo, double& sn_out, double& zn_out, double tt = 0.0) {
@@ -249,72 +241,33 @@ __device__ __forceinline__ void row_op(double slack, double ga, double gd, doubl
         const double s0 = slack < io.sfloor ? io.sfloor : slack;
         sn_out = s0, zn_out = io.mu0 / s0;
     } else if (PASS == PASS_BUILD) {
-        const double rg = s - slack;
-        wgt = z * fast_rcp(s + io.dregn * z);
-        v = -wgt * (rg - s);
-        zo = z;
+        const Build b = build(s, z, slack, io.dregn);
+        wgt = b.wgt, v = b.v, zo = z;
         io.sum0 += cw * s * z;
-        io.vmax = fmax(io.vmax, fabs(rg));
+        io.vmax = fmax(io.vmax, fabs(b.rg));
     } else if (PASS == PASS_AFF) {
-        const double rg = s - slack;
-        const double iz = fast_rcp(z), is = fast_rcp(s);
-        wgt = z * fast_rcp(s + io.dreg * z);
-        const double dza = wgt * (ga + rg - s);
-        const double dsa = -s - s * dza * iz;
-        const double cc = dsa * dza;
-        io.vmax = fmax(io.vmax, fmax(-dsa * is, -dza * iz));
-        io.sum0 += cw * s * z, io.sum1 += cw * (s * dza + z * dsa), io.sum2 += cw * cc;
-        v = -wgt * (rg - s - cc * iz);
-        wgt = wgt * iz;
+        const Affine a = affine(s, z, slack, ga, io.dreg);
+        io.vmax = fmax(io.vmax, a.lim);
+        io.sum0 += cw * s * z, io.sum1 += cw * (s * a.dza + z * a.dsa), io.sum2 += cw * a.cc;
+        v = a.v, wgt = a.wz;
     } else if (PASS == PASS_STEP || PASS == PASS_STEPG) {
-        const double rg = s - slack;
-        const double iz = fast_rcp(z), is = fast_rcp(s);
-        wgt = z * fast_rcp(s + io.dreg * z);
-        const double dza = wgt * (ga + rg - s);
-        const double cc = (-s - s * dza * iz) * dza;
-        const double rcc = s * z + cc - io.sigma_mu - tt;
-        const double dz = wgt * (gd + rg - rcc * iz);
-        const double ds = -(rcc + s * dz) * iz;
-        io.vmax = fmax(io.vmax, fmax(-ds * is, -dz * iz));
+        const Dir d = direction(s, z, slack, ga, gd, io.dreg, io.sigma_mu, tt);
+        io.vmax = fmax(io.vmax, step_limit(s, z, d.ds, d.dz));
     } else if (PASS == PASS_GOND) {
-        // Gondzio's centrality corrector: at the trial step length the complementarity products of the Mehrotra direction are projected
-        // onto [0.1, 10] x (sigma mu); the shift t = projected - actual (not below -10 sigma mu) moves the row's target, and the
-        // direction is solved for again: rcc - t instead of rcc, i.e. the right-hand side changes by -G'(W t / z)
-        const double rg = s - slack;
-        const double iz = fast_rcp(z);
-        const double w0 = z * fast_rcp(s + io.dreg * z);
-        const double dza = w0 * (ga + rg - s);
-        const double cc = (-s - s * dza * iz) * dza;
-        const double rcc = s * z + cc - io.sigma_mu;
-        const double dz = w0 * (gd + rg - rcc * iz);
-        const double ds = -(rcc + s * dz) * iz;
-        const double pr = (s + io.atr * ds) * (z + io.atr * dz);
-        const double lo = 0.1 * io.mut, hi = 10.0 * io.mut;
-        double t = (pr < lo ? lo : (pr > hi ? hi : pr)) - pr;
-        t = fmax(t, -hi);
-        sn_out = t;
-        v = -w0 * t * iz;
+        const Gondzio g = gondzio(s, z, direction(s, z, slack, ga, gd, io.dreg, io.sigma_mu, 0.0), io.dreg, io.atr, io.mut);
+        sn_out = g.t;
+        v = g.v;
     } else if (PASS == PASS_UPBUILD) {
-        const double rg = s - (slack + io.alpha * gd);  // the old point: slack_old = slack + alpha * gd
-        const double iz = fast_rcp(z);
-        const double w0 = z * fast_rcp(s + io.dreg * z);
-        const double dza = w0 * (ga + rg - s);
-        const double cc = (-s - s * dza * iz) * dza;
-        const double rcc = s * z + cc - io.sigma_mu - tt;
-        const double dz = w0 * (gd + rg - rcc * iz);
-        const double ds = -(rcc + s * dz) * iz;
-        const double sn = s + io.alpha * ds, zn = z + io.alpha * dz;
-        sn_out = sn, zn_out = zn;
-        io.vmin = fmin(io.vmin, sn * zn);
-        const double rgn = sn - slack;
-        wgt = zn * fast_rcp(sn + io.dregn * zn);
-        v = -wgt * (rgn - sn);
-        zo = zn;
-        io.sum0 += cw * sn * zn;
-        io.vmax = fmax(io.vmax, fabs(rgn));
+        // the old point: slack_old = slack + alpha * gd
+        const State n = step_state(s, z, direction(s, z, slack + io.alpha * gd, ga, gd, io.dreg, io.sigma_mu, tt), io.alpha);
+        sn_out = n.s, zn_out = n.z;
+        io.vmin = fmin(io.vmin, n.sz);
+        const Build b = build(n.s, n.z, slack, io.dregn);
+        wgt = b.wgt, v = b.v, zo = n.z;
+        io.sum0 += cw * n.s * n.z;
+        io.vmax = fmax(io.vmax, fabs(b.rg));
     } else if (PASS == PASS_KMUL_A || PASS == PASS_KMUL_D || PASS == PASS_KMUL_G) {
-        wgt = z * fast_rcp(s + io.dreg * z);  // the weight this iteration's Newton matrix was assembled with
-        v = wgt * gd;
+        v = kmul(s, z, io.dreg, gd);
     }
 }
 
@@ -396,16 +349,15 @@ __global__ __launch_bounds__(256) void jq_sweep(JArgs A) {
                     if (polish) {
                         const int snap = (int)(((size_t)a * 3 + k) * oq + j6);
                         if (PASS == PASS_CAND) {
-                            if (z > s || s < 1e-6)
-                                pol_emit(pol, (int)r, a, -1, j6, k == 0 ? sg : 0.0, k == 1 ? sg : 0.0, k == 2 ? sg : 0.0, slack, snap, side == 0 ? hi : lo,
-                                         fmax(z / s, 1e-300));
+                            const double str = cand_strength(s, z);
+                            if (str != 0.0) pol_emit(pol, (int)r, a, -1, j6, k == 0 ? sg : 0.0, k == 1 ? sg : 0.0, k == 2 ? sg : 0.0, slack, snap, side == 0 ? hi : lo, str);
                         } else {
                             const double snv = slack - sg * dd[k];  // slack at x + dx
                             io.vmax = fmax(io.vmax, -snv);
                             const int q = pol.pos[r];
                             if (q >= 0)
                                 pol.e[q] = snv;
-                            else if (snv < -1e-11)
+                            else if (snv < VERIFY_TOL)
                                 pol_emit(pol, (int)r, a, -1, j6, k == 0 ? sg : 0.0, k == 1 ? sg : 0.0, k == 2 ? sg : 0.0, slack, snap, side == 0 ? hi : lo, 1.0);
                         }
                         continue;
@@ -436,9 +388,7 @@ __global__ __launch_bounds__(256) void jq_sweep(JArgs A) {
             double xb[3], gab = 0, gdb = 0;
 #pragma unroll
             for (int k = 0; k < 3; ++k) xb[k] = ctrl[((size_t)b * 3 + k) * oq + j6];
-            const double e0 = a_lo ? xb[0] - xa[0] : xa[0] - xb[0], e1 = a_lo ? xb[1] - xa[1] : xa[1] - xb[1],
-                         e2 = a_lo ? xb[2] - xa[2] : xa[2] - xb[2];
-            const double slack = n0 * e0 + n1 * e1 + n2 * e2 - (a_lo ? ra + radius[b] : radius[b] + ra);
+            const double slack = pair_slack(a_lo, n0, n1, n2, xa[0], xa[1], xa[2], xb[0], xb[1], xb[2], a_lo ? ra + radius[b] : radius[b] + ra);
             if (pinned) {
                 pin_viol = fmax(pin_viol, -slack);
                 continue;
@@ -446,12 +396,12 @@ __global__ __launch_bounds__(256) void jq_sweep(JArgs A) {
             if (need_da) {
                 const double f0 = w.dxa[((size_t)b * 3 + 0) * oq + j6], f1 = w.dxa[((size_t)b * 3 + 1) * oq + j6],
                              f2 = w.dxa[((size_t)b * 3 + 2) * oq + j6];
-                gab = a_lo ? n0 * (da[0] - f0) + n1 * (da[1] - f1) + n2 * (da[2] - f2) : n0 * (f0 - da[0]) + n1 * (f1 - da[1]) + n2 * (f2 - da[2]);
+                gab = pair_dot(a_lo, n0, n1, n2, da[0], da[1], da[2], f0, f1, f2);
             }
             if (need_dd) {
                 const double* dxp = dvec;
                 const double f0 = dxp[((size_t)b * 3 + 0) * oq + j6], f1 = dxp[((size_t)b * 3 + 1) * oq + j6], f2 = dxp[((size_t)b * 3 + 2) * oq + j6];
-                gdb = a_lo ? n0 * (dd[0] - f0) + n1 * (dd[1] - f1) + n2 * (dd[2] - f2) : n0 * (f0 - dd[0]) + n1 * (f1 - dd[1]) + n2 * (f2 - dd[2]);
+                gdb = pair_dot(a_lo, n0, n1, n2, dd[0], dd[1], dd[2], f0, f1, f2);
             }
             double wgt = 0, v = 0, zo = 0, sn = 0, zn = 0;
             const double s = rd_sz ? ps[r] : 0.0, z = rd_sz ? pz[r] : 0.0;
@@ -459,14 +409,15 @@ __global__ __launch_bounds__(256) void jq_sweep(JArgs A) {
                 if (!a_lo) continue;  // (one copy of a pair row is enough here)
                 const int rowid = (int)(6 * (size_t)ncp + r);
                 if (PASS == PASS_CAND) {
-                    if (z > s || s < 1e-6) pol_emit(pol, rowid, a, b, j6, n0, n1, n2, slack, -1, 0.0, fmax(z / s, 1e-300));
+                    const double str = cand_strength(s, z);
+                    if (str != 0.0) pol_emit(pol, rowid, a, b, j6, n0, n1, n2, slack, -1, 0.0, str);
                 } else {
                     const double snv = slack - gdb;
                     io.vmax = fmax(io.vmax, -snv);
                     const int q = pol.pos[rowid];
                     if (q >= 0)
                         pol.e[q] = snv;
-                    else if (snv < -1e-11)
+                    else if (snv < VERIFY_TOL)
                         pol_emit(pol, rowid, a, b, j6, n0, n1, n2, slack, -1, 0.0, 1.0);
                 }
                 continue;
@@ -474,23 +425,13 @@ __global__ __launch_bounds__(256) void jq_sweep(JArgs A) {
             row_op<PASS>(slack, gab, gdb, s, z, io, a_lo ? 1.0 : 0.0, wgt, v, zo, sn, zn, use_t ? w.tp[r] : 0.0);
             if (wr_sz && a_lo) ps2[r] = sn, pz2[r] = zn;
             if (gond && a_lo) w.tp[r] = sn;
-            if (accum) {
-                const double sg = a_lo ? 1.0 : -1.0;
-                if (build) {
-                    if (a_lo) w.pwgt[r] = wgt;
-                    Sm[0] += wgt * n0 * n0, Sm[1] += wgt * n0 * n1, Sm[2] += wgt * n0 * n2;
-                    Sm[3] += wgt * n1 * n1, Sm[4] += wgt * n1 * n2, Sm[5] += wgt * n2 * n2;
-                    const double zz = sg * zo, vv = sg * v;
-                    gz[0] += zz * n0, gz[1] += zz * n1, gz[2] += zz * n2;
-                    yv[0] += vv * n0, yv[1] += vv * n1, yv[2] += vv * n2;
-                } else if (kmul) {
-                    const double vv = sg * v;
-                    Sm[0] += vv * n0, Sm[1] += vv * n1, Sm[2] += vv * n2;
-                } else {
-                    const double vv = sg * v, ww = sg * wgt;
-                    Sm[0] += vv * n0, Sm[1] += vv * n1, Sm[2] += vv * n2;
-                    Sm[3] += ww * n0, Sm[4] += ww * n1, Sm[5] += ww * n2;
-                }
+            if (build) {
+                if (a_lo) w.pwgt[r] = wgt;
+                acc_build(Sm, yv, gz, wgt, v, zo, pair_sign(a_lo), n0, n1, n2);
+            } else if (kmul) {
+                acc_kmul(Sm, v, pair_sign(a_lo), n0, n1, n2);
+            } else if (aff) {
+                acc_aff(Sm, v, wgt, pair_sign(a_lo), n0, n1, n2);
             }
         }
         if (accum && !pinned) {
@@ -577,7 +518,7 @@ __global__ __launch_bounds__(256) void jq_post(JArgs A) {
                 const double* xs = ctrl + ((size_t)a * 3 + k) * oq + 6 * m;
                 double gv = 0;
 #pragma unroll
-                for (int jj = 0; jj < 6; ++jj) gv += jc_Qbase[6 * i + jj] * xs[jj];
+                for (int jj = 0; jj < 6; ++jj) gv += Qbase[6 * i + jj] * xs[jj];
                 gv *= 2 * w.segsc[m];
                 gv += acc_sum(w, d, 9 + k, cp);
                 g[q] = -gv;
@@ -712,7 +653,7 @@ __global__ __launch_bounds__(256) void jq_refine(JArgs A, int op, int which) {
         const int j6 = 6 * (j - 1) + 3 + q, m = j6 / 6, i = j6 % 6;
         double gv = 0;
 #pragma unroll
-        for (int jj = 0; jj < 6; ++jj) gv += jc_Qbase[6 * i + jj] * dxp[6 * m + jj];
+        for (int jj = 0; jj < 6; ++jj) gv += Qbase[6 * i + jj] * dxp[6 * m + jj];
         g[q] = 2 * w.segsc[m] * gv + acc_sum(w, d, k, (size_t)a * oq + j6);
     }
 #pragma unroll
@@ -1151,7 +1092,7 @@ __global__ __launch_bounds__(256) void jq_finish(JArgs A) {
         const double* xs = ctrl + ((size_t)a * 3 + k) * oq + 6 * m;
         double q = 0;
         for (int i = 0; i < 6; ++i)
-            for (int jj = 0; jj < 6; ++jj) q += jc_Qbase[6 * i + jj] * xs[i] * xs[jj];
+            for (int jj = 0; jj < 6; ++jj) q += Qbase[6 * i + jj] * xs[i] * xs[jj];
         obj += q * w.segsc[m];
     }
     obj = block_reduce(obj, 0, red);

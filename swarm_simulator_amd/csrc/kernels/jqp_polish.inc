@@ -119,8 +119,7 @@ __global__ __launch_bounds__(256) void jp_begin(JArgs A) {
     if (tid < PC_N) p.cnt[tid] = 0;
     if (tid == 0) p.cnt[PC_BEST] = 0x7fffffff, w.st[ST_PSTATE] = PS_SOLVE, w.st[ST_PTAU] = 1.0;
     if (w.st[ST_RDONE] != 0.0) return;
-    // factor of the 3x3-block tridiagonal K0 chain (k0_factor3 of qp_polish.inc): f[0..8] = L_jj with reciprocal diagonal,
-    // f[9..17] = B_jj = T_{jj+1,jj} L_jj^-T
+    // factor of the 3x3-block tridiagonal K0 chain (common/ipm_rows.h), 18 doubles per knot
     extern __shared__ double f3[];  // 18 * nj
     for (int it = tid; it < 18 * nj; it += 256) {
         const int jj = it / 18, e = it % 18, j = jj + 1;
@@ -129,57 +128,23 @@ __global__ __launch_bounds__(256) void jp_begin(JArgs A) {
     __syncthreads();
     if (tid == 0) {
         double Bp[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int jj = 0; jj < nj; ++jj) {
-            double* f = f3 + 18 * jj;
-            double Am[9], Ej[9];
-            for (int e = 0; e < 9; ++e) Am[e] = f[e], Ej[e] = f[9 + e];
-            if (jj > 0)
-                for (int r = 0; r < 3; ++r)
-                    for (int c = 0; c < 3; ++c) Am[3 * r + c] -= Bp[3 * r] * Bp[3 * c] + Bp[3 * r + 1] * Bp[3 * c + 1] + Bp[3 * r + 2] * Bp[3 * c + 2];
-            const double l00 = sqrt(Am[0]), l10 = Am[3] / l00, l20 = Am[6] / l00;
-            const double l11 = sqrt(Am[4] - l10 * l10), l21 = (Am[7] - l20 * l10) / l11;
-            const double l22 = sqrt(Am[8] - l20 * l20 - l21 * l21);
-            f[0] = 1.0 / l00, f[1] = 0, f[2] = 0, f[3] = l10, f[4] = 1.0 / l11, f[5] = 0, f[6] = l20, f[7] = l21, f[8] = 1.0 / l22;
-            for (int r = 0; r < 3; ++r) {
-                const double o0 = Ej[r], o1 = Ej[3 + r], o2 = Ej[6 + r];
-                const double x0 = o0 / l00, x1 = (o1 - x0 * l10) / l11, x2 = (o2 - x0 * l20 - x1 * l21) / l22;
-                f[9 + 3 * r] = Bp[3 * r] = x0, f[10 + 3 * r] = Bp[3 * r + 1] = x1, f[11 + 3 * r] = Bp[3 * r + 2] = x2;
-            }
-        }
+        for (int jj = 0; jj < nj; ++jj) (void)k0_factor_step(f3 + 18 * jj, Bp, jj == 0);  // (a pivot that is not positive shows in the KKT check)
     }
     __syncthreads();
     // column c of R: solve K0 y = e_c  (R is symmetric: stored as row c)
     for (int c = tid; c < nr; c += 256) {
         double* y = p.R + (size_t)c * nr;
         for (int i = 0; i < nr; ++i) y[i] = i == c ? 1.0 : 0.0;
-        double p0 = 0, p1 = 0, p2 = 0;
+        double p[3] = {0, 0, 0};
         for (int jj = 0; jj < nj; ++jj) {
-            const double* f = f3 + 18 * jj;
-            double y0 = y[3 * jj], y1 = y[3 * jj + 1], y2 = y[3 * jj + 2];
-            if (jj > 0) {
-                const double* B = f - 9;
-                y0 -= B[0] * p0 + B[1] * p1 + B[2] * p2;
-                y1 -= B[3] * p0 + B[4] * p1 + B[5] * p2;
-                y2 -= B[6] * p0 + B[7] * p1 + B[8] * p2;
-            }
-            y0 = y0 * f[0];
-            y1 = (y1 - f[3] * y0) * f[4];
-            y2 = (y2 - f[6] * y0 - f[7] * y1) * f[8];
-            y[3 * jj] = p0 = y0, y[3 * jj + 1] = p1 = y1, y[3 * jj + 2] = p2 = y2;
+            double yk[3] = {y[3 * jj], y[3 * jj + 1], y[3 * jj + 2]};
+            k0_forward_step((const double*)f3 + 18 * jj, jj > 0, yk, p);
+            y[3 * jj] = p[0] = yk[0], y[3 * jj + 1] = p[1] = yk[1], y[3 * jj + 2] = p[2] = yk[2];
         }
         for (int jj = nj - 1; jj >= 0; --jj) {
-            const double* f = f3 + 18 * jj;
-            double y0 = y[3 * jj], y1 = y[3 * jj + 1], y2 = y[3 * jj + 2];
-            if (jj + 1 < nj) {
-                const double* B = f + 9;
-                y0 -= B[0] * p0 + B[3] * p1 + B[6] * p2;
-                y1 -= B[1] * p0 + B[4] * p1 + B[7] * p2;
-                y2 -= B[2] * p0 + B[5] * p1 + B[8] * p2;
-            }
-            y2 = y2 * f[8];
-            y1 = (y1 - f[7] * y2) * f[4];
-            y0 = (y0 - f[3] * y1 - f[6] * y2) * f[0];
-            y[3 * jj] = p0 = y0, y[3 * jj + 1] = p1 = y1, y[3 * jj + 2] = p2 = y2;
+            double yk[3] = {y[3 * jj], y[3 * jj + 1], y[3 * jj + 2]};
+            k0_backward_step((const double*)f3 + 18 * jj, jj + 1 < nj, yk, p);
+            y[3 * jj] = p[0] = yk[0], y[3 * jj + 1] = p[1] = yk[1], y[3 * jj + 2] = p[2] = yk[2];
         }
     }
     if (tid == 0) w.st[ST_RDONE] = 1.0;
@@ -205,7 +170,7 @@ __global__ __launch_bounds__(256) void jp_c0(JArgs A) {
         const int j6 = 6 * (j - 1) + 3 + q, m = j6 / 6, i = j6 % 6;
         double gv = 0;
 #pragma unroll
-        for (int jj = 0; jj < 6; ++jj) gv += jc_Qbase[6 * i + jj] * ctrl[6 * m + jj];
+        for (int jj = 0; jj < 6; ++jj) gv += Qbase[6 * i + jj] * ctrl[6 * m + jj];
         g[q] = 2 * w.segsc[m] * gv;
     }
 #pragma unroll

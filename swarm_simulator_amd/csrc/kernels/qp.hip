@@ -34,6 +34,7 @@
 #pragma clang fp contract(fast)
 
 #include "knot_lds.inc"  // (below the pragma: its multiply-adds must contract)
+#include "common/ipm_rows.h"  // the arithmetic of a row, shared with jqp.hip
 
 #ifndef QP_THREADS
 #define QP_THREADS 512
@@ -124,6 +125,7 @@ __host__ __device__ inline int polish_lds_doubles(int nk) {
 }
 
 namespace {
+using namespace ipm;
 
 #ifdef QP_PROFILE
 #define PROF_DECL long long prof_t0 = wall_clock64(), prof_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
@@ -276,38 +278,36 @@ __device__ inline QpWs carve(double* base, const QpDims& d, int nbmax) {
     return w;
 }
 
-// Q_base (rbp_planner.hpp:330-335) = int_0^1 B'''_i B'''_j
-__constant__ double c_Qbase[36] = {720,  -1800, 1200,  0,     0,     -120, -1800, 4800,  -3600, 0,     600,   0,
-                                   1200, -3600, 3600,  -1200, 0,     0,    0,     0,     -1200, 3600,  -3600, 1200,
-                                   0,    600,   0,     -3600, 4800,  -1800, -120, 0,     0,     1200,  -1800, 720};
-__device__ inline size_t pair_index(int N, int qi, int qj) { return (size_t)qi * N - (size_t)qi * (qi + 1) / 2 + (qj - qi - 1); }
-
-// ---- block reductions ------------------------------------------------------------------------------------------
-// Inside a wave by DPP (quad permutes, half-row and row mirrors) and four readlanes -- six butterfly steps of ds_bpermute pairs are
-// ~1000 cycles of dependent LDS round trips, and an interior-point iteration has ten of these reductions --, across the waves through
-// `red`.  Two barriers: the one in front of the write would only protect the previous reduction's readers, which the barrier at ITS
-// end has already let go.
+// ---- reductions ------------------------------------------------------------------------------------------------
+// Wave-wide (result in every lane): inside a row of 16 lanes by DPP (quad permutes, half-row and row mirrors: VALU latency), across the
+// four rows through readlane: ~300 cycles, where six butterfly steps of ds_bpermute pairs took ~1000 of dependent LDS round trips -- an
+// interior-point iteration has ten of these reductions, and every Lawson-Hanson step of the polish two or three on its dependent path.
 template <int CTRL>
-__device__ __forceinline__ double qp_dpp_f64(double v) {
+__device__ __forceinline__ double dpp_f64(double v) {
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
     const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
     return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ double qp_red_op(double a, double b, int op) { return op == 0 ? a + b : (op == 1 ? fmax(a, b) : fmin(a, b)); }
-__device__ __forceinline__ double qp_rl(double v, int lane) {
+__device__ __forceinline__ double red_op(double a, double b, int op) { return op == 0 ? a + b : (op == 1 ? fmax(a, b) : fmin(a, b)); }
+__device__ __forceinline__ double rl(double v, int lane) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
 }
+__device__ __forceinline__ double wave_red(double v, int op /*0 sum,1 max,2 min*/) {
+    v = red_op(v, dpp_f64<0xB1>(v), op);   // quad_perm [1,0,3,2]
+    v = red_op(v, dpp_f64<0x4E>(v), op);   // quad_perm [2,3,0,1]
+    v = red_op(v, dpp_f64<0x141>(v), op);  // row_half_mirror
+    v = red_op(v, dpp_f64<0x140>(v), op);  // row_mirror: every lane of a row holds the row's result
+    return red_op(red_op(rl(v, 0), rl(v, 16), op), red_op(rl(v, 32), rl(v, 48), op), op);
+}
+// Block-wide: the wave reduction, then across the waves through `red`.  Two barriers: the one in front of the write would only protect
+// the previous reduction's readers, which the barrier at ITS end has already let go.
 __device__ inline double block_reduce(double v, int op /*0 sum,1 max,2 min*/, double* red) {
-    v = qp_red_op(v, qp_dpp_f64<0xB1>(v), op);   // quad_perm [1,0,3,2]
-    v = qp_red_op(v, qp_dpp_f64<0x4E>(v), op);   // quad_perm [2,3,0,1]
-    v = qp_red_op(v, qp_dpp_f64<0x141>(v), op);  // row_half_mirror
-    v = qp_red_op(v, qp_dpp_f64<0x140>(v), op);  // row_mirror: every lane of a row holds the row's result
-    v = qp_red_op(qp_red_op(qp_rl(v, 0), qp_rl(v, 16), op), qp_red_op(qp_rl(v, 32), qp_rl(v, 48), op), op);
+    v = wave_red(v, op);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (lane == 0) red[wave] = v;
     __syncthreads();
     double r = red[0];
-    for (int i = 1; i < QP_THREADS / 64; ++i) r = op == 0 ? r + red[i] : (op == 1 ? fmax(r, red[i]) : fmin(r, red[i]));
+    for (int i = 1; i < QP_THREADS / 64; ++i) r = red_op(r, red[i], op);
     __syncthreads();
     return r;
 }
@@ -342,21 +342,21 @@ __device__ void mission_constants(const QpDims& d, const double* T, QpWs& w) {
             for (int a = 0; a < 3; ++a)
                 for (int b = 0; b < 3; ++b) {
                     double s = 0;
-                    for (int c = 0; c < 3; ++c) s += c_Qbase[6 * (3 + a) + 3 + c] * sl * L[3 * c + b];
+                    for (int c = 0; c < 3; ++c) s += Qbase[6 * (3 + a) + 3 + c] * sl * L[3 * c + b];
                     QL[3 * a + b] = s;
                 }
             for (int a = 0; a < 3; ++a)
                 for (int b = 0; b < 3; ++b) {
                     double s = 0;
                     for (int c = 0; c < 3; ++c) s += L[3 * c + a] * QL[3 * c + b];
-                    D[3 * a + b] = 2 * (s + c_Qbase[6 * a + b] * sr);
+                    D[3 * a + b] = 2 * (s + Qbase[6 * a + b] * sr);
                 }
             if (j + 1 < M) {
                 const double* Ln = w.Lk + 9 * (j + 1);
                 for (int a = 0; a < 3; ++a)
                     for (int b = 0; b < 3; ++b) {
                         double s = 0;
-                        for (int c = 0; c < 3; ++c) s += c_Qbase[6 * a + 3 + c] * sr * Ln[3 * c + b];
+                        for (int c = 0; c < 3; ++c) s += Qbase[6 * a + 3 + c] * sr * Ln[3 * c + b];
                         E[3 * a + b] = 2 * s;  // rows u_j, cols u_{j+1}
                     }
             }
@@ -417,15 +417,6 @@ struct RowCtx {
     const double* radius;  // [N]
 };
 
-// 1/x for the row arithmetic of the sweeps: v_rcp_f64 plus two Newton steps (relative error ~1e-16 for normal x > 0).
-// An IEEE division costs three times as many instructions (div_scale, div_fmas, div_fixup).
-__device__ __forceinline__ double fast_rcp(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    r = fma(fma(-x, r, 1.0), r, r);
-    r = fma(fma(-x, r, 1.0), r, r);
-    return r;
-}
-
 // 1/sqrt(x): v_rsq_f64 plus two Newton steps (full double precision for normal x > 0); an IEEE sqrt followed by an IEEE
 // division is ~6x the instructions and sits on the dependent chain of every Cholesky column
 __device__ __forceinline__ double fast_rsqrt(double x) {
@@ -440,76 +431,47 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
 // ga = g . dx_aff, gd = g . dx.  cw = 1 for rows that count in the sums, 0 for the second copy of a pair row.  Returns the
 // Newton weight wgt, the right-hand-side scalar v and the multiplier zo where the pass defines them.  Step-length limits are
 // tracked as io.vmax = max(-ds/s, -dz/z) (the caller takes the reciprocal), which needs no data-dependent division.
-// The corrector term cc = ds_aff dz_aff and the step (ds, dz) are functions of (s, z, ga, gd): the STEP and UPBUILD sweeps
-// recompute them instead of reading them back (three stored arrays fewer, see the note above QpWs).
-// PRE: (s, z) of the row were fetched by the caller (the prefetch ring of the frozen-row stream, QP_ROW_PF)
+// Three steps per pass: fetch (s, z), the row's arithmetic (common/ipm_rows.h), store and reduce.  The corrector term and the step
+// (ds, dz) are functions of (s, z, ga, gd): the STEP and UPBUILD sweeps recompute them instead of reading them back (three stored
+// arrays fewer, see the note above QpWs).
+// PRE: (s, z) of the row were fetched by the caller (the prefetch ring / the blocks of the frozen-row stream, QP_ROW_PF / QP_ROW_BLK)
 template <int PASS, bool PRE = false>
 __device__ __forceinline__ void row_op(double slack, double ga, double gd, size_t r, const QpWs& w, PassIO& io, double cw, double& wgt,
                                        double& v, double& zo, double s_in = 0.0, double z_in = 0.0) {
+    constexpr bool rd_sz = PASS == PASS_BUILD || PASS == PASS_AFF || PASS == PASS_STEP || PASS == PASS_UPBUILD || PASS == PASS_CAND;
+    double s = 0.0, z = 0.0;
+    if (rd_sz) s = PRE ? s_in : QGC(w.s)[r], z = PRE ? z_in : QGC(w.z)[r];
     if (PASS == PASS_INIT) {
-        const double s = slack < io.s_floor ? io.s_floor : slack;
-        w.s[r] = s;
-        w.z[r] = io.mu0 / s;
+        const double s0 = slack < io.s_floor ? io.s_floor : slack;
+        w.s[r] = s0;
+        w.z[r] = io.mu0 / s0;
     } else if (PASS == PASS_BUILD) {
-        const double s = PRE ? s_in : QGC(w.s)[r], z = PRE ? z_in : QGC(w.z)[r];
-        const double rg = s - slack;
-        wgt = z * fast_rcp(s + io.dreg * z);  // = 1 / (s/z + dreg)
-        v = -wgt * (rg - s);                  // predictor: rc / z = s
-        zo = z;
+        const Build b = build(s, z, slack, io.dreg);
+        wgt = b.wgt, v = b.v, zo = z;
         io.sum0 += cw * s * z;
-        io.vmax = fmax(io.vmax, fabs(rg));
+        io.vmax = fmax(io.vmax, fabs(b.rg));
     } else if (PASS == PASS_AFF) {
-        const double s = PRE ? s_in : QGC(w.s)[r], z = PRE ? z_in : QGC(w.z)[r];
-        const double rg = s - slack;
-        const double iz = fast_rcp(z), is = fast_rcp(s);
-        wgt = z * fast_rcp(s + io.dreg * z);
-        const double dza = wgt * (ga + rg - s);
-        const double dsa = -s - s * dza * iz;  // (-s z - s dza) / z
-        const double cc = dsa * dza;
-        io.vmax = fmax(io.vmax, fmax(-dsa * is, -dza * iz));
-        io.sum0 += cw * s * z, io.sum1 += cw * (s * dza + z * dsa), io.sum2 += cw * cc;
-        // the corrector's right-hand side is affine in sigma*mu, which is only known after this sweep's reductions:
-        //   v_corr = -wgt (rg - (s z + cc - sigma mu) / z) = v - sigma mu * wgt / z.   Both parts are accumulated here, so
-        // the corrector needs no sweep of its own (out: v, and wgt := wgt / z)
-        v = -wgt * (rg - s - cc * iz);
-        wgt = wgt * iz;
+        const Affine a = affine(s, z, slack, ga, io.dreg);
+        io.vmax = fmax(io.vmax, a.lim);
+        io.sum0 += cw * s * z, io.sum1 += cw * (s * a.dza + z * a.dsa), io.sum2 += cw * a.cc;
+        v = a.v, wgt = a.wz;  // the two parts of the corrector's right-hand side: it needs no sweep of its own
     } else if (PASS == PASS_STEP) {
-        const double s = PRE ? s_in : QGC(w.s)[r], z = PRE ? z_in : QGC(w.z)[r];
-        const double rg = s - slack;
-        const double iz = fast_rcp(z), is = fast_rcp(s);
-        wgt = z * fast_rcp(s + io.dreg * z);
-        const double dza = wgt * (ga + rg - s);
-        const double cc = (-s - s * dza * iz) * dza;
-        const double rcc = s * z + cc - io.sigma_mu;
-        const double dz = wgt * (gd + rg - rcc * iz);
-        const double ds = -(rcc + s * dz) * iz;
-        io.vmax = fmax(io.vmax, fmax(-ds * is, -dz * iz));
+        const Dir d = direction(s, z, slack, ga, gd, io.dreg, io.sigma_mu, 0.0);
+        io.vmax = fmax(io.vmax, step_limit(s, z, d.ds, d.dz));
     } else if (PASS == PASS_UPBUILD) {
         // old state (s, z) at the old point: slack_old = slack + alpha * gd
-        const double s = PRE ? s_in : QGC(w.s)[r], z = PRE ? z_in : QGC(w.z)[r];
-        const double rg = s - (slack + io.alpha * gd);
-        const double iz = fast_rcp(z);
-        const double w0 = z * fast_rcp(s + io.dreg * z);
-        const double dza = w0 * (ga + rg - s);
-        const double cc = (-s - s * dza * iz) * dza;
-        const double rcc = s * z + cc - io.sigma_mu;
-        const double dz = w0 * (gd + rg - rcc * iz);
-        const double ds = -(rcc + s * dz) * iz;
-        const double sn = s + io.alpha * ds, zn = z + io.alpha * dz;
-        QG(w.s2)[r] = sn, QG(w.z2)[r] = zn;
-        io.vmin = fmin(io.vmin, sn * zn);  // wide-neighbourhood test of the step just applied
+        const State n = step_state(s, z, direction(s, z, slack + io.alpha * gd, ga, gd, io.dreg, io.sigma_mu, 0.0), io.alpha);
+        QG(w.s2)[r] = n.s, QG(w.z2)[r] = n.z;
+        io.vmin = fmin(io.vmin, n.sz);  // wide-neighbourhood test of the step just applied
         // ... and the next iteration's weights / residuals at the new point
-        const double rgn = sn - slack;
-        wgt = zn * fast_rcp(sn + io.dreg * zn);
-        v = -wgt * (rgn - sn);
-        zo = zn;
-        io.sum0 += cw * sn * zn;
-        io.vmax = fmax(io.vmax, fabs(rgn));
+        const Build b = build(n.s, n.z, slack, io.dreg);
+        wgt = b.wgt, v = b.v, zo = n.z;
+        io.sum0 += cw * n.s * n.z;
+        io.vmax = fmax(io.vmax, fabs(b.rg));
     } else if (PASS == PASS_PRESOLVE) {
         io.vmax = fmax(io.vmax, -slack);  // violation of a pinned (constant) row
     } else if (PASS == PASS_CAND) {
-        const double s = PRE ? s_in : QGC(w.s)[r], z = PRE ? z_in : QGC(w.z)[r];
-        wgt = (z > s || s < 1e-6) ? fmax(z / s, 1e-300) : 0.0;  // candidate for the active set; the value orders the warm start
+        wgt = cand_strength(s, z);
         QG(w.cc)[r] = wgt;
         v = slack;
     } else if (PASS == PASS_CAND_GEO) {
@@ -523,7 +485,7 @@ __device__ __forceinline__ void row_op(double slack, double ga, double gd, size_
         const double sn = slack - gd;  // slack at x + dx
         QG(w.ds)[r] = sn;
         io.vmax = fmax(io.vmax, -sn);
-        if (sn < -1e-11 && QGC(w.cc)[r] == 0.0) {  // violated row that is not a candidate yet
+        if (sn < VERIFY_TOL && QGC(w.cc)[r] == 0.0) {  // violated row that is not a candidate yet
             QG(w.cc)[r] = 1.0;
             wgt = 1.0;
         }
@@ -641,45 +603,27 @@ __device__ void row_pass(const RowCtx& c, PassIO& io, int wi0 = threadIdx.x, int
                 }
             }
         }
+        // a row with coefficient sg * n of this control point joins its accumulators
+        auto accumulate = [&](double wgt, double v, double zo, double sg, double n0, double n1, double n2) {
+            if (build) acc_build(S, yv, gz, wgt, v, zo, sg, n0, n1, n2);
+            else if (aff) acc_aff(S, v, wgt, sg, n0, n1, n2);
+        };
         // ---- in-batch pair rows (idx 6 .. 6 + nb - 2): canonical orientation n . (x_hi - x_lo) >= rr, so that the copy in the
-        // other agent's column sees bit-identical inputs
+        // other agent's column sees bit-identical inputs (pair_slack)
         auto pair_row = [&](auto pre_tag, int pb, double n0, double n1, double n2, const double (&xb)[3], const double (&fa)[3], const double (&fd)[3],
                             double rsum, double s_in, double z_in) {
             constexpr bool PRE_P = decltype(pre_tag)::value;
             const int b = pb < a ? pb : pb + 1;
             const bool a_lo = a < b;
             const size_t r = base + (size_t)(6 + pb) * 64;
-            double gab = 0, gdb = 0;
-            // e = x_hi - x_lo ; the G row is  n . x_lo - n . x_hi <= -rr
-            const double e0 = a_lo ? xb[0] - xa[0] : xa[0] - xb[0], e1 = a_lo ? xb[1] - xa[1] : xa[1] - xb[1],
-                         e2 = a_lo ? xb[2] - xa[2] : xa[2] - xb[2];
-            const double slack = n0 * e0 + n1 * e1 + n2 * e2 - rsum;
-            if (need_da) {
-                const double f0 = fa[0], f1 = fa[1], f2 = fa[2];
-                gab = a_lo ? n0 * (da[0] - f0) + n1 * (da[1] - f1) + n2 * (da[2] - f2) : n0 * (f0 - da[0]) + n1 * (f1 - da[1]) + n2 * (f2 - da[2]);
-            }
-            if (need_dd) {
-                const double f0 = fd[0], f1 = fd[1], f2 = fd[2];
-                gdb = a_lo ? n0 * (dd[0] - f0) + n1 * (dd[1] - f1) + n2 * (dd[2] - f2) : n0 * (f0 - dd[0]) + n1 * (f1 - dd[1]) + n2 * (f2 - dd[2]);
-            }
+            const double slack = pair_slack(a_lo, n0, n1, n2, xa[0], xa[1], xa[2], xb[0], xb[1], xb[2], rsum);
+            const double gab = need_da ? pair_dot(a_lo, n0, n1, n2, da[0], da[1], da[2], fa[0], fa[1], fa[2]) : 0.0;
+            const double gdb = need_dd ? pair_dot(a_lo, n0, n1, n2, dd[0], dd[1], dd[2], fd[0], fd[1], fd[2]) : 0.0;
             double wgt = 0, v = 0, zo = 0;
             row_op<PASS, PRE_P>(slack, gab, gdb, r, w, io, a_lo ? 1.0 : 0.0, wgt, v, zo, s_in, z_in);
             if (cand && wgt != 0 && a_lo) emit_cand(d, w, *c.pw, r, j6, a, b, n0, n1, n2, slack, -1, 0.0, wgt);
-            if (accum) {
-                const double sg = a_lo ? 1.0 : -1.0;  // coefficient of x_a in the row is sg * n
-                if (build) {
-                    if (a_lo) w.pwgt[(size_t)(a * nb - a * (a + 1) / 2 + (b - a - 1)) * oq + j6] = wgt;
-                    S[0] += wgt * n0 * n0, S[1] += wgt * n0 * n1, S[2] += wgt * n0 * n2;
-                    S[3] += wgt * n1 * n1, S[4] += wgt * n1 * n2, S[5] += wgt * n2 * n2;
-                    const double zz = sg * zo, vv = sg * v;
-                    gz[0] += zz * n0, gz[1] += zz * n1, gz[2] += zz * n2;
-                    yv[0] += vv * n0, yv[1] += vv * n1, yv[2] += vv * n2;
-                } else {
-                    const double vv = sg * v, ww = sg * wgt;
-                    S[0] += vv * n0, S[1] += vv * n1, S[2] += vv * n2;
-                    S[3] += ww * n0, S[4] += ww * n1, S[5] += ww * n2;
-                }
-            }
+            if (build && a_lo) w.pwgt[(size_t)(a * nb - a * (a + 1) / 2 + (b - a - 1)) * oq + j6] = wgt;
+            accumulate(wgt, v, zo, pair_sign(a_lo), n0, n1, n2);
         };
         if (pre_b && nb <= 4) {
             // (QP_ROW_BLK) up to three pair rows: everything they read -- normal, the other agent's point and directions, radii, (s, z) -- is
@@ -769,17 +713,7 @@ __device__ void row_pass(const RowCtx& c, PassIO& io, int wi0 = threadIdx.x, int
                             double wgt = 0, v = 0, zo = 0;
                             row_op<PASS, rd_sz>(slack, n0 * da[0] + n1 * da[1] + n2 * da[2], n0 * dd[0] + n1 * dd[1] + n2 * dd[2], r, w, io, 1.0, wgt, v, zo, cs[u], cz[u]);
                             if (cand && wgt != 0) emit_cand(d, w, *c.pw, r, j6, a, -1, n0, n1, n2, slack, -1, 0.0, wgt);
-                            if (accum) {
-                                if (build) {
-                                    S[0] += wgt * n0 * n0, S[1] += wgt * n0 * n1, S[2] += wgt * n0 * n2;
-                                    S[3] += wgt * n1 * n1, S[4] += wgt * n1 * n2, S[5] += wgt * n2 * n2;
-                                    gz[0] += zo * n0, gz[1] += zo * n1, gz[2] += zo * n2;
-                                    yv[0] += v * n0, yv[1] += v * n1, yv[2] += v * n2;
-                                } else {
-                                    S[0] += v * n0, S[1] += v * n1, S[2] += v * n2;
-                                    S[3] += wgt * n0, S[4] += wgt * n1, S[5] += wgt * n2;
-                                }
-                            }
+                            accumulate(wgt, v, zo, 1.0, n0, n1, n2);
                         }
                     }
                 }
@@ -834,17 +768,7 @@ __device__ void row_pass(const RowCtx& c, PassIO& io, int wi0 = threadIdx.x, int
             double wgt = 0, v = 0, zo = 0;
             row_op<PASS, rd_sz>(slack, n0 * da[0] + n1 * da[1] + n2 * da[2], n0 * dd[0] + n1 * dd[1] + n2 * dd[2], r, w, io, 1.0, wgt, v, zo, s_in, z_in);
             if (cand && wgt != 0) emit_cand(d, w, *c.pw, r, j6, a, -1, n0, n1, n2, slack, -1, 0.0, wgt);
-            if (accum) {
-                if (build) {
-                    S[0] += wgt * n0 * n0, S[1] += wgt * n0 * n1, S[2] += wgt * n0 * n2;
-                    S[3] += wgt * n1 * n1, S[4] += wgt * n1 * n2, S[5] += wgt * n2 * n2;
-                    gz[0] += zo * n0, gz[1] += zo * n1, gz[2] += zo * n2;
-                    yv[0] += v * n0, yv[1] += v * n1, yv[2] += v * n2;
-                } else {
-                    S[0] += v * n0, S[1] += v * n1, S[2] += v * n2;
-                    S[3] += wgt * n0, S[4] += wgt * n1, S[5] += wgt * n2;
-                }
-            }
+            accumulate(wgt, v, zo, 1.0, n0, n1, n2);
         }
 #else
 #pragma unroll QP_ROW_UNROLL
@@ -859,17 +783,7 @@ __device__ void row_pass(const RowCtx& c, PassIO& io, int wi0 = threadIdx.x, int
             double wgt = 0, v = 0, zo = 0;
             row_op<PASS>(slack, n0 * da[0] + n1 * da[1] + n2 * da[2], n0 * dd[0] + n1 * dd[1] + n2 * dd[2], r, w, io, 1.0, wgt, v, zo);
             if (cand && wgt != 0) emit_cand(d, w, *c.pw, r, j6, a, -1, n0, n1, n2, slack, -1, 0.0, wgt);
-            if (accum) {
-                if (build) {
-                    S[0] += wgt * n0 * n0, S[1] += wgt * n0 * n1, S[2] += wgt * n0 * n2;
-                    S[3] += wgt * n1 * n1, S[4] += wgt * n1 * n2, S[5] += wgt * n2 * n2;
-                    gz[0] += zo * n0, gz[1] += zo * n1, gz[2] += zo * n2;
-                    yv[0] += v * n0, yv[1] += v * n1, yv[2] += v * n2;
-                } else {
-                    S[0] += v * n0, S[1] += v * n1, S[2] += v * n2;
-                    S[3] += wgt * n0, S[4] += wgt * n1, S[5] += wgt * n2;
-                }
-            }
+            accumulate(wgt, v, zo, 1.0, n0, n1, n2);
         }
 #endif
         }
@@ -949,7 +863,7 @@ __device__ void rbase_from_acc(const RowCtx& c, double& dmax, double& gmax) {
             const double* xs = xb + 6 * m;
             double gv = 0;
 #pragma unroll
-            for (int jj = 0; jj < 6; ++jj) gv += c_Qbase[6 * i + jj] * xs[jj];
+            for (int jj = 0; jj < 6; ++jj) gv += Qbase[6 * i + jj] * xs[jj];
             gv *= 2 * w.segsc[m];
             gv += w.cpacc[(size_t)(9 + k) * (d.nb * oq) + (size_t)a * oq + j6];  // G'z of ALL rows of this control point (bounds, pairs, frozen)
             g[q] = -gv;
@@ -1318,12 +1232,6 @@ __device__ void assemble_blocks(const RowCtx& c, double* lds) {
 // (Round 3: the cross-lane traffic of the factorisation goes through LDS broadcasts instead, see knot_lds.inc; v_readlane is
 // left for the pivots.)  The substitutions stage the knots' M_j through LDS (prefetched by the otherwise idle waves).
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double rl(double v, int lane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
 // TWISTED ("burn at both ends") factorisation: wave 0 eliminates blocks 0 .. mid-1 upwards, wave 1 eliminates blocks
 // nj-1 .. mid+1 downwards, concurrently on two SIMDs; the middle block collects both Schur complements.  It halves the
 // length of the dependent chain (factor and substitutions alike) at no extra arithmetic.
@@ -3270,7 +3178,7 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
         const double* xs = ctrl + ((size_t)(first + a) * 3 + k) * d.oq + 6 * m;
         double q = 0;
         for (int i = 0; i < 6; ++i)
-            for (int jj = 0; jj < 6; ++jj) q += c_Qbase[6 * i + jj] * xs[i] * xs[jj];
+            for (int jj = 0; jj < 6; ++jj) q += Qbase[6 * i + jj] * xs[i] * xs[jj];
         obj += q * sc;
     }
     obj = block_reduce(obj, 0, red);

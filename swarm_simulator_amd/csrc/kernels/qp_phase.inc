@@ -297,7 +297,7 @@ __global__ __launch_bounds__(QP_THREADS, QP_WAVES_PER_EU) void ph_advance(DevSes
             const double* xs = ctrl + ((size_t)(first + a) * 3 + k) * d.oq + 6 * m;
             double q = 0;
             for (int i = 0; i < 6; ++i)
-                for (int jj = 0; jj < 6; ++jj) q += c_Qbase[6 * i + jj] * xs[i] * xs[jj];
+                for (int jj = 0; jj < 6; ++jj) q += Qbase[6 * i + jj] * xs[i] * xs[jj];
             obj += q * sc;
         }
         obj = block_reduce(obj, 0, red);

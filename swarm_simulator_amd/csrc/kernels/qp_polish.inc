@@ -34,26 +34,7 @@ struct PolishWs {
         __builtin_amdgcn_wave_barrier();                    \
     } while (0)
 
-// Wave-wide reductions (result in every lane).  Inside a row of 16 lanes by DPP (quad permutes, half-row and row mirrors: VALU
-// latency), across the four rows through readlane: ~300 cycles, where six butterfly steps of ds_bpermute pairs took ~1000 -- and
-// every Lawson-Hanson step has two or three of them on its dependent path.
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double red_op(double a, double b, int op) { return op == 0 ? a + b : (op == 1 ? fmax(a, b) : fmin(a, b)); }
-__device__ __forceinline__ double rl_const(double v, int lane) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-__device__ __forceinline__ double wave_red(double v, int op /*0 sum,1 max,2 min*/) {
-    v = red_op(v, dpp_f64<0xB1>(v), op);   // quad_perm [1,0,3,2]
-    v = red_op(v, dpp_f64<0x4E>(v), op);   // quad_perm [2,3,0,1]
-    v = red_op(v, dpp_f64<0x141>(v), op);  // row_half_mirror
-    v = red_op(v, dpp_f64<0x140>(v), op);  // row_mirror: every lane of a row holds the row's result
-    return red_op(red_op(rl_const(v, 0), rl_const(v, 16), op), red_op(rl_const(v, 32), rl_const(v, 48), op), op);
-}
+// (wave_red, the wave-wide reduction of a double, is qp.hip's; the same steps for an int)
 __device__ __forceinline__ int wave_min_int(int v) {
     v = min(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false));
     v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false));
@@ -139,29 +120,8 @@ __device__ void k0_factor3(const QpDims& d, const QpWs& w, double* f3, int* flag
     if (threadIdx.x == 0) {
         int ok = 1;
         double Bp[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int jj = 0; jj < d.nj; ++jj) {
-            double* f = f3 + 18 * jj;
-            double A[9], Ej[9];
-            for (int e = 0; e < 9; ++e) A[e] = f[e], Ej[e] = f[9 + e];
-            if (jj > 0)
-                for (int r = 0; r < 3; ++r)
-                    for (int c = 0; c < 3; ++c) A[3 * r + c] -= Bp[3 * r] * Bp[3 * c] + Bp[3 * r + 1] * Bp[3 * c + 1] + Bp[3 * r + 2] * Bp[3 * c + 2];
-            if (!(A[0] > 0)) ok = 0;
-            const double l00 = sqrt(A[0]), l10 = A[3] / l00, l20 = A[6] / l00;
-            const double d11 = A[4] - l10 * l10;
-            if (!(d11 > 0)) ok = 0;
-            const double l11 = sqrt(d11), l21 = (A[7] - l20 * l10) / l11;
-            const double d22 = A[8] - l20 * l20 - l21 * l21;
-            if (!(d22 > 0)) ok = 0;
-            const double l22 = sqrt(d22);
-            // the diagonal slots hold the RECIPROCAL pivots: the little solves (one thread per chain, 35 knots deep) multiply
-            f[0] = 1.0 / l00, f[1] = 0, f[2] = 0, f[3] = l10, f[4] = 1.0 / l11, f[5] = 0, f[6] = l20, f[7] = l21, f[8] = 1.0 / l22;
-            for (int r = 0; r < 3; ++r) {
-                const double o0 = Ej[r], o1 = Ej[3 + r], o2 = Ej[6 + r];  // T_{j+1,j}[r][c] = Ek[9j + 3c + r]  (zero behind the last knot)
-                const double x0 = o0 / l00, x1 = (o1 - x0 * l10) / l11, x2 = (o2 - x0 * l20 - x1 * l21) / l22;
-                f[9 + 3 * r] = Bp[3 * r] = x0, f[10 + 3 * r] = Bp[3 * r + 1] = x1, f[11 + 3 * r] = Bp[3 * r + 2] = x2;
-            }
-        }
+        for (int jj = 0; jj < d.nj; ++jj)
+            if (!k0_factor_step(f3 + 18 * jj, Bp, jj == 0)) ok = 0;
         *flag = !ok;
     }
     __syncthreads();
@@ -179,7 +139,7 @@ __device__ __forceinline__ void k0_solve3(const double* f3g, int nj, int nk, dou
     gdb* y = QG(col) + sub * 3;
     constexpr int B = K0_BLK;
     double cur[B][3], nxt[B][3];
-    double p0 = 0, p1 = 0, p2 = 0;
+    double p[3] = {0, 0, 0};
 #pragma unroll
     for (int u = 0; u < B; ++u) {
         const int jx = u < nj ? u : nj - 1;
@@ -197,18 +157,8 @@ __device__ __forceinline__ void k0_solve3(const double* f3g, int nj, int nk, dou
         for (int u = 0; u < B; ++u) {
             const int jj = j0 + u;
             if (jj < nj) {
-                const kl_lds* f = f3 + 18 * jj;
-                double y0 = cur[u][0], y1 = cur[u][1], y2 = cur[u][2];
-                if (jj > 0) {
-                    const kl_lds* Bm = f - 9;
-                    y0 -= Bm[0] * p0 + Bm[1] * p1 + Bm[2] * p2;
-                    y1 -= Bm[3] * p0 + Bm[4] * p1 + Bm[5] * p2;
-                    y2 -= Bm[6] * p0 + Bm[7] * p1 + Bm[8] * p2;
-                }
-                y0 = y0 * f[0];
-                y1 = (y1 - f[3] * y0) * f[4];
-                y2 = (y2 - f[6] * y0 - f[7] * y1) * f[8];
-                y[(size_t)jj * nk] = p0 = y0, y[(size_t)jj * nk + 1] = p1 = y1, y[(size_t)jj * nk + 2] = p2 = y2;
+                k0_forward_step(f3 + 18 * jj, jj > 0, cur[u], p);
+                y[(size_t)jj * nk] = p[0] = cur[u][0], y[(size_t)jj * nk + 1] = p[1] = cur[u][1], y[(size_t)jj * nk + 2] = p[2] = cur[u][2];
             }
         }
 #pragma unroll
@@ -234,18 +184,8 @@ __device__ __forceinline__ void k0_solve3(const double* f3g, int nj, int nk, dou
         for (int u = 0; u < B; ++u) {
             const int jj = jt - u;
             if (jj >= 0) {
-                const kl_lds* f = f3 + 18 * jj;
-                double y0 = cur[u][0], y1 = cur[u][1], y2 = cur[u][2];
-                if (jj + 1 < nj) {
-                    const kl_lds* Bm = f + 9;  // y_jj -= B_jj' y_{jj+1}
-                    y0 -= Bm[0] * p0 + Bm[3] * p1 + Bm[6] * p2;
-                    y1 -= Bm[1] * p0 + Bm[4] * p1 + Bm[7] * p2;
-                    y2 -= Bm[2] * p0 + Bm[5] * p1 + Bm[8] * p2;
-                }
-                y2 = y2 * f[8];
-                y1 = (y1 - f[7] * y2) * f[4];
-                y0 = (y0 - f[3] * y1 - f[6] * y2) * f[0];
-                y[(size_t)jj * nk] = p0 = y0, y[(size_t)jj * nk + 1] = p1 = y1, y[(size_t)jj * nk + 2] = p2 = y2;
+                k0_backward_step(f3 + 18 * jj, jj + 1 < nj, cur[u], p);
+                y[(size_t)jj * nk] = p[0] = cur[u][0], y[(size_t)jj * nk + 1] = p[1] = cur[u][1], y[(size_t)jj * nk + 2] = p[2] = cur[u][2];
             }
         }
 #pragma unroll
@@ -580,7 +520,7 @@ __device__ __forceinline__ int polish_qp(RowCtx& c, PassIO& io, const PolishWs& 
                 const int i = (it % d.oq) % 6;
                 double g = 0;
 #pragma unroll
-                for (int jj = 0; jj < 6; ++jj) g += c_Qbase[6 * i + jj] * xq[q][jj];
+                for (int jj = 0; jj < 6; ++jj) g += Qbase[6 * i + jj] * xq[q][jj];
                 w.cvec[it] = 2 * sc4[q] * g;
             }
         }
