@@ -561,7 +561,7 @@ __device__ __forceinline__ void v_normalize(float* a) {
 
 __global__ __launch_bounds__(256) void rsfc_kernel(DevSession s) {
     const int MS = s.M, PS = MS + 1, N = s.N;  // slot strides
-    const long long per_mission = (long long)s.npair * MS;
+    const long long per_mission = (long long)(s.npair > 0 ? s.npair : 1) * MS;  // (a single agent has no pair: row 0 only writes the times)
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= per_mission * s.K) return;
     const int mission = (int)(gid / per_mission);
@@ -569,11 +569,12 @@ __global__ __launch_bounds__(256) void rsfc_kernel(DevSession s) {
     const long long r = gid % per_mission;
     const int pair = (int)(r / MS), seg = (int)(r % MS);
     if (seg >= M) return;
+    if (pair == 0) s.rsfc_time[(size_t)mission * MS + seg] = s.T[(size_t)mission * PS + seg + 1];  // :390 (every shard)
+    if (pair >= s.npair) return;
     // invert pair index -> (qi, qj), qi < qj, qi-major (rbp_corridor.hpp:342-344)
     int qi = 0, rem = pair;
     while (rem >= N - 1 - qi) rem -= N - 1 - qi, qi++;
     const int qj = qi + 1 + rem;
-    if (pair == 0) s.rsfc_time[(size_t)mission * MS + seg] = s.T[(size_t)mission * PS + seg + 1];  // :390 (every shard)
     if (qi < s.agent_begin || qi >= s.agent_end) return;  // pair rows of another shard
     const float* ti = s.init_traj + (size_t)mission * N * PS * 3 + (size_t)qi * P * 3 + 3 * seg;
     const float* tj = s.init_traj + (size_t)mission * N * PS * 3 + (size_t)qj * P * 3 + 3 * seg;
@@ -639,7 +640,7 @@ int launch_corridor(const DevSession& s, hipStream_t st) {
         return rbp_set_error(RBP_ERR_HIP, "sfc_kernel: the dynamic LDS it needs was refused by the device");
     if (groups > 0) hipLaunchKernelGGL(mask_kernel, dim3(SFC_MASK_BLOCKS, s.K), dim3(256), 0, st, s);
     if (groups > 0) hipLaunchKernelGGL(sfc_kernel, dim3(s.K * groups), dim3(64 * SFC_WAVES), lds, st, s, apw);
-    const long long total = (long long)s.K * s.npair * s.M;
+    const long long total = (long long)s.K * (s.npair > 0 ? s.npair : 1) * s.M;  // rbp_plan.rsfc_time = T[1..M] for a single agent too
     if (total > 0) hipLaunchKernelGGL(rsfc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, s);
     return RBP_OK;
 }
