@@ -625,15 +625,17 @@ __device__ void row_pass(const RowCtx& c, PassIO& io, int wi0 = threadIdx.x, int
             if (build && a_lo) w.pwgt[(size_t)(a * nb - a * (a + 1) / 2 + (b - a - 1)) * oq + j6] = wgt;
             accumulate(wgt, v, zo, pair_sign(a_lo), n0, n1, n2);
         };
-        if (pre_b && nb <= 4) {
+        if (pre_b && nb > 1 && nb <= 4) {
             // (QP_ROW_BLK) up to three pair rows: everything they read -- normal, the other agent's point and directions, radii, (s, z) -- is
-            // requested for all of them before the first is worked on (each cost two trips to memory, one after the other)
+            // requested for all of them before the first is worked on (each cost two trips to memory, one after the other).
+            // A batch of one agent has no pair row, no slot 6 in its tile and, where it is the whole mission, no normal at all: it takes
+            // the loop below, which then runs no round and loads nothing.
             float pn[3][3];
             double pxb[3][3], pfa[3][3], pfd[3][3], prs[3], pps[3], ppz[3];
 #pragma unroll
             for (int pb = 0; pb < 3; ++pb) {
-                const int pq = pb < nb - 1 ? pb : 0;  // (a row that does not exist reads row 0's operands and is not worked on; nb = 1: nothing is)
-                const int b = nb > 1 ? (pq < a ? pq : pq + 1) : 0;
+                const int pq = pb < nb - 1 ? pb : 0;  // (a row that does not exist reads row 0's operands -- nb > 1: that row exists -- and is not worked on)
+                const int b = nb > 1 ? (pq < a ? pq : pq + 1) : 0;  // (nb > 1 holds here; spelt out, the register allocation is the one it was)
                 const bool a_lo = a < b;
                 const int qb = d.first + b;
                 const size_t r = base + (size_t)(6 + pq) * 64;
