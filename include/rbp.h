@@ -420,6 +420,34 @@ int rbp_dev_worlds_ecbs_plan(const rbp_dev_worlds* ws, int32_t K, const int32_t*
                              const rbp_mission* missions, const rbp_param* param,
                              int64_t max_high_level_nodes, rbp_ecbs_out* out);
 
+/* ---- the search's plans handed to a session without a host trip --------------------------------
+ * rbp_dev_worlds_ecbs_search is the search of rbp_dev_worlds_ecbs_plan -- same argument checks (max_M is an argument here, there is no
+ * rbp_ecbs_out to fill), same refusals with RBP_ERR_BAD_ARGUMENT before a device is looked for, same capacities, same statuses 0 / 1 /
+ * 2 / 3 -- whose results STAY in HBM, owned by the handle: per mission the status, the path lengths, the packed paths, both expansion
+ * counters, and the missions' start, goal, radius, max_vel and max_acc, COPIED once as packed arrays [K][N][...] (the caller's mission
+ * arrays are not needed after the call; max_vel / max_acc may be null for a search that is only downloaded).  Only status, lengths
+ * and counters return to the host, K x (N + 3) words.  The handle REFERENCES the set of worlds: `ws` must outlive it.
+ * rbp_dev_ecbs_download fills a caller's rbp_ecbs_out (out->max_M must be the search's) with exactly what rbp_dev_worlds_ecbs_plan returns
+ * for the same arguments, bit for bit, the zeros beyond index M and of missions without a result included.  out->T and out->init_traj
+ * may be NULL: then only the per-mission scalars are filled and nothing is computed; otherwise both are written on the device
+ * (kernels/handoff.hip) and copied back once. */
+typedef struct rbp_dev_ecbs rbp_dev_ecbs;
+int  rbp_dev_worlds_ecbs_search(const rbp_dev_worlds* ws, int32_t K, const int32_t* world_index, const rbp_mission* missions,
+                                const rbp_param* param, int64_t max_high_level_nodes, int32_t max_M, rbp_dev_ecbs** out);
+int  rbp_dev_ecbs_count(const rbp_dev_ecbs* e);   /* K of the search (0 for a null handle) */
+int  rbp_dev_ecbs_download(const rbp_dev_ecbs* e, rbp_ecbs_out* out);
+void rbp_dev_ecbs_destroy(rbp_dev_ecbs* e);
+/* A session of the missions of `e` whose status is 0, in ascending order, on the device of the search: slot_of[k] (slot_of may be NULL;
+ * [rbp_dev_ecbs_count(e)]) receives mission k's index in the session, or -1.  No mission with status 0: RBP_ERR_BAD_ARGUMENT.  Every
+ * mission keeps its own M; max_boxes <= 0 means each mission's M.  T, init_traj and the five mission arrays are written into the session's
+ * arena by two kernels from what the handle holds: nothing of them passes through the host, everything is COPIED, and the handle may be
+ * destroyed as soon as the call has returned.  The worlds are the resident grids of the handle's set, REFERENCED in place like any device
+ * grid of rbp_world: the set of worlds must outlive the session.  T is the search's (i * time_step of the param the SEARCH was given);
+ * `param` here is the plan's, and keeping the two consistent is the caller's business.  The session has no corridor inputs; run,
+ * run_async, download, reset, device_arrays, set_solver_opts ... work as on a session of rbp_session_create.  A search whose missions
+ * came without max_vel / max_acc is refused. */
+int  rbp_session_create_from_ecbs(rbp_session** out, const rbp_dev_ecbs* e, const rbp_param* param, int32_t max_boxes, int32_t* slot_of);
+
 const char* rbp_last_error(void);
 int rbp_device_count(void);
 

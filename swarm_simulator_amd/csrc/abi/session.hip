@@ -183,6 +183,139 @@ static int check_solver_opts(const rbp_solver_opts* o) {
 
 static size_t al(size_t n) { return ((n + 255) & ~size_t(255)) + 256; }
 
+// ---- what rbp_session_create and rbp_session_create_from_ecbs share: one set of parameter checks, one arena layout ----------------------
+static int check_session_param(const rbp_param* param) {
+    if (param->n != 5 || param->phi != 3) return fail(RBP_ERR_UNSUPPORTED_DEGREE, "RBPPlanner: n should be 5, phi 3");
+    if (param->timescale_rule != RBP_TIMESCALE_ALL_REAL_ROOTS && param->timescale_rule != RBP_TIMESCALE_FIRST_EIGENVALUES)
+        return fail(RBP_ERR_BAD_ARGUMENT, "rbp_param.timescale_rule must be RBP_TIMESCALE_ALL_REAL_ROOTS (0) or RBP_TIMESCALE_FIRST_EIGENVALUES (1)");
+    // the SFC kernel caches at most SFC_MAXS sample keys per axis (isObstacleInBox walks the box on the box_res lattice,
+    // rbp_corridor.hpp:47-63): reject worlds / resolutions that would be truncated instead of growing boxes through obstacles
+    if (!(param->box_xy_res > 0) || !(param->box_z_res > 0)) return fail(RBP_ERR_BAD_ARGUMENT, "box/xy_res and box/z_res must be positive");
+    for (int a = 0; a < 3; ++a) {
+        const double res = a < 2 ? param->box_xy_res : param->box_z_res;
+        const double ext = param->world_max[a] - param->world_min[a];
+        if (!(ext >= 0) || std::ceil(ext / res) + 3 > SFC_MAXS)
+            return fail(RBP_ERR_BAD_ARGUMENT, "world extent / box resolution exceeds the SFC sample cache (" + std::to_string(SFC_MAXS - 3) + " steps per axis)");
+    }
+    return RBP_OK;
+}
+
+// bytes of a session's arena: the grids it uploads (none for grids referenced in place) and every array session_carve takes
+static size_t session_arena_bytes(size_t grid_bytes, int K, int N, int M, int MB) {
+    const int P = M + 1, npair = N * (N - 1) / 2, oq = 6 * M;
+    return grid_bytes + al(sizeof(DevWorld) * K) + 2 * al(sizeof(int) * K) + al(sizeof(float) * (size_t)K * N * P * 3) +
+                         al(sizeof(double) * K * P) + 2 * al(sizeof(double) * (size_t)K * N * 9) + al(sizeof(double) * K * N) +
+                         2 * al(sizeof(double) * (size_t)K * N * 3) + al(sizeof(int) * K * N) + al(sizeof(unsigned) * (size_t)K * SFC_MASK_WORDS) +
+                         al(sizeof(double) * (size_t)K * N * MB * 6) + al(sizeof(double) * (size_t)K * N * MB) +
+                         al(sizeof(float) * (size_t)K * npair * M * 3 + 16) + al(sizeof(double) * K * M) +
+                         2 * al(sizeof(double) * (size_t)K * N * 3 * oq) + al(sizeof(int) * K) + al(sizeof(double) * K * SC_N) +
+                         al(sizeof(unsigned long long) * K * CT_N) + al(sizeof(int) * K) + al(sizeof(unsigned long long) * K) + 4096;
+}
+
+// the arena of `total` bytes, the session's own or its context's, cleared before anything is written into it
+static int session_reserve_arena(rbp_session* s, rbp_ctx* ctx, int device, size_t total) {
+    if (ctx) {
+        if (ctx->busy) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_ctx: the context's arena is in use by another session");
+        if (ctx->device != device) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_ctx: context belongs to another device");
+        if (ctx->cap < total) {  // grow (with headroom, so that a sequence of slightly different plans does not reallocate)
+            if (ctx->base) (void)hipFree(ctx->base);
+            ctx->base = nullptr, ctx->cap = 0;
+            const size_t want = total + total / 4;
+            hipError_t e = hipMalloc((void**)&ctx->base, want);
+            if (e != hipSuccess) return fail(RBP_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+            ctx->cap = want;
+        }
+        s->ctx = ctx, ctx->busy = true;
+        s->arena.base = ctx->base;
+    } else {
+        hipError_t e = hipMalloc((void**)&s->arena.base, total);
+        if (e != hipSuccess) return fail(RBP_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    s->arena.size = total;
+    // synchronous on purpose: small pageable host-to-device copies may be carried out by the CPU ahead of work queued on the
+    // stream, so an asynchronous clear could wipe what the uploads below have just written
+    HIP_TRY(hipMemset(s->arena.base, 0, total));
+    HIP_TRY(hipDeviceSynchronize());
+    return RBP_OK;
+}
+
+// the shapes and parameters of DevSession (everything but its pointers) for K missions on `worlds`, strides M and MB
+static int session_describe(rbp_session* s, int device, const rbp_param* param, const rbp_world* worlds, int K, int N, int M, int MB) {
+    const int npair = N * (N - 1) / 2;
+    DevSession& d = s->d;
+    d.K = K, d.N = N, d.M = M, d.max_boxes = MB, d.npair = npair;
+    d.agent_begin = 0, d.agent_end = N;
+    for (int a = 0; a < 3; ++a) {
+        const double bres = a < 2 ? param->box_xy_res : param->box_z_res;
+        d.sfc_cap[a] = std::min(SFC_MAXS, (int)std::ceil((param->world_max[a] - param->world_min[a]) / bres) + 4);
+    }
+    d.sfc_mask_words = 0;
+    for (int k = 0; k < K; ++k) {
+        const size_t nc = (size_t)worlds[k].dim[0] * worlds[k].dim[1] * worlds[k].dim[2];
+        const size_t words = ((((nc + 63) >> 6) * 2 + 2) + 3) & ~size_t(3);
+        if (words <= SFC_MASK_WORDS) d.sfc_mask_words = std::max(d.sfc_mask_words, (int)words);
+    }
+    {   // sfc_kernel keeps box_log [max_boxes][M + 1] per agent of a workgroup in LDS, beside the mask and the key lists: refuse here, with the
+        // numbers, what the launch would refuse with a generic HIP error (the QP kernels take M <= QP_MAX_M = 128; the corridor's
+        // bound depends on max_boxes, which defaults to M)
+        int lds_max = 160 * 1024;
+        (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
+        const size_t need = corridor_lds_bytes(d);
+        if (need > (size_t)std::max(lds_max, 64 * 1024))
+            return fail(RBP_ERR_BAD_ARGUMENT, "Corridor: " + std::to_string(need) + " bytes of LDS per workgroup for max_boxes = " + std::to_string(MB) +
+                                                  ", M = " + std::to_string(M) + " (box_log is [max_boxes][M + 1] per agent) exceed the device's " +
+                                                  std::to_string(lds_max) + "; pass a smaller plan.max_boxes (the reference's corridors hold ~6-10 boxes per agent)");
+    }
+    for (int a = 0; a < 3; ++a) d.p.world_min[a] = param->world_min[a], d.p.world_max[a] = param->world_max[a];
+    d.p.box_xy_res = param->box_xy_res, d.p.box_z_res = param->box_z_res, d.p.downwash = param->downwash;
+    d.p.sequential = param->sequential, d.p.batch_size = param->batch_size, d.p.batch_iter = param->batch_iter;
+    d.p.iteration = param->iteration, d.p.time_scale = param->time_scale;
+    d.p.timescale_rule = param->timescale_rule;
+    d.p.polish = 1, d.p.far_slack = 0.7;  // (rbp_solver_opts.polish / qp_far_slack of the run)
+    return RBP_OK;
+}
+
+// The arrays of a session in its arena, after the grids it uploaded: the one layout of both constructors.  The arrays a constructor has to
+// fill come back in `in`; DevSession gets every pointer.
+struct SessionInputs {
+    DevWorld* worlds;
+    int *Mk, *MBk;
+    float* init_traj;
+    double *T, *start, *goal, *radius, *max_vel, *max_acc;
+};
+static int session_carve(rbp_session* s, SessionInputs& in) {
+    Arena& A = s->arena;
+    DevSession& d = s->d;
+    const int K = d.K, N = d.N, M = d.M, MB = d.max_boxes, npair = d.npair, P = M + 1, oq = 6 * M;
+    in.worlds = A.take<DevWorld>(K);
+    in.Mk = A.take<int>(K);
+    in.MBk = A.take<int>(K);
+    in.init_traj = A.take<float>((size_t)K * N * P * 3);
+    in.T = A.take<double>((size_t)K * P);
+    in.start = A.take<double>((size_t)K * N * 9);
+    in.goal = A.take<double>((size_t)K * N * 9);
+    in.radius = A.take<double>((size_t)K * N);
+    in.max_vel = A.take<double>((size_t)K * N * 3);
+    in.max_acc = A.take<double>((size_t)K * N * 3);
+    d.sfc_mask = A.take<unsigned>((size_t)K * SFC_MASK_WORDS);
+    d.sfc_count = A.take<int>((size_t)K * N);
+    d.sfc_box = A.take<double>((size_t)K * N * MB * 6);
+    d.sfc_time = A.take<double>((size_t)K * N * MB);
+    d.rsfc_normal = A.take<float>((size_t)K * npair * M * 3 + 4);
+    d.rsfc_time = A.take<double>((size_t)K * M);
+    d.ctrl = A.take<double>((size_t)K * N * 3 * oq);
+    d.coef = A.take<double>((size_t)K * N * 3 * oq);
+    d.status = A.take<int>(K);
+    d.scalars = A.take<double>((size_t)K * SC_N);
+    d.counters = A.take<unsigned long long>((size_t)K * CT_N);
+    d.qp_order = A.take<int>(K);
+    d.qp_cost = A.take<unsigned long long>(K);
+    if (A.off > A.size) return fail(RBP_ERR_HIP, "arena overflow (internal sizing error)");
+    d.worlds = in.worlds, d.Mk = in.Mk, d.MBk = in.MBk;
+    d.init_traj = in.init_traj, d.T = in.T, d.start = in.start, d.goal = in.goal, d.radius = in.radius, d.max_vel = in.max_vel, d.max_acc = in.max_acc;
+    return RBP_OK;
+}
+
 static int session_create_impl(rbp_session** out, int device, int K, const rbp_world* worlds, const rbp_mission* missions,
                                const rbp_param* param, const rbp_plan* plans, rbp_ctx* ctx) {
     if (!out || K <= 0 || !worlds || !missions || !param || !plans) return fail(RBP_ERR_BAD_ARGUMENT, "null argument");
@@ -203,18 +336,7 @@ static int session_create_impl(rbp_session** out, int device, int K, const rbp_w
             return fail(RBP_ERR_BAD_ARGUMENT, "plan.T / plan.init_traj / world.dist must be set");
         M = std::max(M, (int)plans[k].M), MB = std::max(MB, (int)plans[k].max_boxes);
     }
-    if (param->n != 5 || param->phi != 3) return fail(RBP_ERR_UNSUPPORTED_DEGREE, "RBPPlanner: n should be 5, phi 3");
-    if (param->timescale_rule != RBP_TIMESCALE_ALL_REAL_ROOTS && param->timescale_rule != RBP_TIMESCALE_FIRST_EIGENVALUES)
-        return fail(RBP_ERR_BAD_ARGUMENT, "rbp_param.timescale_rule must be RBP_TIMESCALE_ALL_REAL_ROOTS (0) or RBP_TIMESCALE_FIRST_EIGENVALUES (1)");
-    // the SFC kernel caches at most SFC_MAXS sample keys per axis (isObstacleInBox walks the box on the box_res lattice,
-    // rbp_corridor.hpp:47-63): reject worlds / resolutions that would be truncated instead of growing boxes through obstacles
-    if (!(param->box_xy_res > 0) || !(param->box_z_res > 0)) return fail(RBP_ERR_BAD_ARGUMENT, "box/xy_res and box/z_res must be positive");
-    for (int a = 0; a < 3; ++a) {
-        const double res = a < 2 ? param->box_xy_res : param->box_z_res;
-        const double ext = param->world_max[a] - param->world_min[a];
-        if (!(ext >= 0) || std::ceil(ext / res) + 3 > SFC_MAXS)
-            return fail(RBP_ERR_BAD_ARGUMENT, "world extent / box resolution exceeds the SFC sample cache (" + std::to_string(SFC_MAXS - 3) + " steps per axis)");
-    }
+    if (int rc = check_session_param(param)) return rc;
     const BatchSchedule sched = batch_schedule(param->sequential, param->batch_size, param->batch_iter, N);
     const int bs = sched.bs, biter = sched.biter;
 
@@ -229,7 +351,7 @@ static int session_create_impl(rbp_session** out, int device, int K, const rbp_w
     s->param = *param;
     s->Mk.resize(K), s->MBk.resize(K);
     for (int k = 0; k < K; ++k) s->Mk[k] = plans[k].M, s->MBk[k] = plans[k].max_boxes;
-    const int P = M + 1, npair = N * (N - 1) / 2, oq = 6 * M;
+    const int P = M + 1, npair = N * (N - 1) / 2;
     s->bs = bs, s->biter = biter;
     if (ctx) s->opts = ctx->opts;
     {
@@ -268,66 +390,9 @@ static int session_create_impl(rbp_session** out, int device, int K, const rbp_w
     size_t grid_bytes = 0;
     for (int k = 0; k < K; ++k)
         if (grid_of[k] == k && !on_device[k]) grid_bytes += al(sizeof(float) * (size_t)worlds[k].dim[0] * worlds[k].dim[1] * worlds[k].dim[2]);
-    const size_t total = grid_bytes + al(sizeof(DevWorld) * K) + 2 * al(sizeof(int) * K) + al(sizeof(float) * (size_t)K * N * P * 3) +
-                         al(sizeof(double) * K * P) + 2 * al(sizeof(double) * (size_t)K * N * 9) + al(sizeof(double) * K * N) +
-                         2 * al(sizeof(double) * (size_t)K * N * 3) + al(sizeof(int) * K * N) + al(sizeof(unsigned) * (size_t)K * SFC_MASK_WORDS) +
-                         al(sizeof(double) * (size_t)K * N * MB * 6) + al(sizeof(double) * (size_t)K * N * MB) +
-                         al(sizeof(float) * (size_t)K * npair * M * 3 + 16) + al(sizeof(double) * K * M) +
-                         2 * al(sizeof(double) * (size_t)K * N * 3 * oq) + al(sizeof(int) * K) + al(sizeof(double) * K * SC_N) +
-                         al(sizeof(unsigned long long) * K * CT_N) + al(sizeof(int) * K) + al(sizeof(unsigned long long) * K) + 4096;
-    if (ctx) {
-        if (ctx->busy) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_ctx: the context's arena is in use by another session");
-        if (ctx->device != device) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_ctx: context belongs to another device");
-        if (ctx->cap < total) {  // grow (with headroom, so that a sequence of slightly different plans does not reallocate)
-            if (ctx->base) (void)hipFree(ctx->base);
-            ctx->base = nullptr, ctx->cap = 0;
-            const size_t want = total + total / 4;
-            hipError_t e = hipMalloc((void**)&ctx->base, want);
-            if (e != hipSuccess) return fail(RBP_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-            ctx->cap = want;
-        }
-        s->ctx = ctx, ctx->busy = true;
-        s->arena.base = ctx->base;
-    } else {
-        hipError_t e = hipMalloc((void**)&s->arena.base, total);
-        if (e != hipSuccess) return fail(RBP_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    s->arena.size = total;
-    // synchronous on purpose: small pageable host-to-device copies may be carried out by the CPU ahead of work queued on the
-    // stream, so an asynchronous clear could wipe what the uploads below have just written
-    HIP_TRY(hipMemset(s->arena.base, 0, total));
-    HIP_TRY(hipDeviceSynchronize());
-    DevSession& d = s->d;
-    d.K = K, d.N = N, d.M = M, d.max_boxes = MB, d.npair = npair;
-    d.agent_begin = 0, d.agent_end = N;
-    for (int a = 0; a < 3; ++a) {
-        const double bres = a < 2 ? param->box_xy_res : param->box_z_res;
-        d.sfc_cap[a] = std::min(SFC_MAXS, (int)std::ceil((param->world_max[a] - param->world_min[a]) / bres) + 4);
-    }
-    d.sfc_mask_words = 0;
-    for (int k = 0; k < K; ++k) {
-        const size_t nc = (size_t)worlds[k].dim[0] * worlds[k].dim[1] * worlds[k].dim[2];
-        const size_t words = ((((nc + 63) >> 6) * 2 + 2) + 3) & ~size_t(3);
-        if (words <= SFC_MASK_WORDS) d.sfc_mask_words = std::max(d.sfc_mask_words, (int)words);
-    }
-    {   // sfc_kernel keeps box_log [max_boxes][M + 1] per agent of a workgroup in LDS, beside the mask and the key lists: refuse here, with the
-        // numbers, what the launch would refuse with a generic HIP error (the QP kernels take M <= QP_MAX_M = 128; the corridor's
-        // bound depends on max_boxes, which defaults to M)
-        int lds_max = 160 * 1024;
-        (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
-        const size_t need = corridor_lds_bytes(d);
-        if (need > (size_t)std::max(lds_max, 64 * 1024))
-            return fail(RBP_ERR_BAD_ARGUMENT, "Corridor: " + std::to_string(need) + " bytes of LDS per workgroup for max_boxes = " + std::to_string(MB) +
-                                                  ", M = " + std::to_string(M) + " (box_log is [max_boxes][M + 1] per agent) exceed the device's " +
-                                                  std::to_string(lds_max) + "; pass a smaller plan.max_boxes (the reference's corridors hold ~6-10 boxes per agent)");
-    }
-    for (int a = 0; a < 3; ++a) d.p.world_min[a] = param->world_min[a], d.p.world_max[a] = param->world_max[a];
-    d.p.box_xy_res = param->box_xy_res, d.p.box_z_res = param->box_z_res, d.p.downwash = param->downwash;
-    d.p.sequential = param->sequential, d.p.batch_size = param->batch_size, d.p.batch_iter = param->batch_iter;
-    d.p.iteration = param->iteration, d.p.time_scale = param->time_scale;
-    d.p.timescale_rule = param->timescale_rule;
-    d.p.polish = 1, d.p.far_slack = 0.7;  // (rbp_solver_opts.polish / qp_far_slack of the run)
-
+    const size_t total = session_arena_bytes(grid_bytes, K, N, M, MB);
+    if (int rc = session_reserve_arena(s, ctx, device, total)) return rc;
+    if (int rc = session_describe(s, device, param, worlds, K, N, M, MB)) return rc;
     Arena& A = s->arena;
     s->worlds_h.resize(K);
 #define UP(dst, src, bytes) HIP_TRY(hipMemcpy((void*)(dst), (src), (bytes), hipMemcpyHostToDevice))
@@ -347,35 +412,13 @@ static int session_create_impl(rbp_session** out, int device, int K, const rbp_w
         w.res = worlds[k].res;
         w.dist = g;
     }
-    DevWorld* dw = A.take<DevWorld>(K);
-    UP(dw, s->worlds_h.data(), sizeof(DevWorld) * K);
-    d.worlds = dw;
-    int* dMk = A.take<int>(K);
-    int* dMBk = A.take<int>(K);
-    UP(dMk, s->Mk.data(), sizeof(int) * K);
-    UP(dMBk, s->MBk.data(), sizeof(int) * K);
-    d.Mk = dMk, d.MBk = dMBk;
-    float* traj = A.take<float>((size_t)K * N * P * 3);
-    double* T = A.take<double>((size_t)K * P);
-    double* start = A.take<double>((size_t)K * N * 9);
-    double* goal = A.take<double>((size_t)K * N * 9);
-    double* radius = A.take<double>((size_t)K * N);
-    double* mv = A.take<double>((size_t)K * N * 3);
-    double* ma = A.take<double>((size_t)K * N * 3);
-    d.sfc_mask = A.take<unsigned>((size_t)K * SFC_MASK_WORDS);
-    d.sfc_count = A.take<int>((size_t)K * N);
-    d.sfc_box = A.take<double>((size_t)K * N * MB * 6);
-    d.sfc_time = A.take<double>((size_t)K * N * MB);
-    d.rsfc_normal = A.take<float>((size_t)K * npair * M * 3 + 4);
-    d.rsfc_time = A.take<double>((size_t)K * M);
-    d.ctrl = A.take<double>((size_t)K * N * 3 * oq);
-    d.coef = A.take<double>((size_t)K * N * 3 * oq);
-    d.status = A.take<int>(K);
-    d.scalars = A.take<double>((size_t)K * SC_N);
-    d.counters = A.take<unsigned long long>((size_t)K * CT_N);
-    d.qp_order = A.take<int>(K);
-    d.qp_cost = A.take<unsigned long long>(K);
-    if (A.off > A.size) return fail(RBP_ERR_HIP, "arena overflow (internal sizing error)");
+    SessionInputs in;
+    if (int rc = session_carve(s, in)) return rc;
+    UP(in.worlds, s->worlds_h.data(), sizeof(DevWorld) * K);
+    UP(in.Mk, s->Mk.data(), sizeof(int) * K);
+    UP(in.MBk, s->MBk.data(), sizeof(int) * K);
+    float* traj = in.init_traj;
+    double *T = in.T, *start = in.start, *goal = in.goal, *radius = in.radius, *mv = in.max_vel, *ma = in.max_acc;
     bool have_corr = true;
     for (int k = 0; k < K; ++k)
         have_corr = have_corr && plans[k].sfc_count && plans[k].sfc_box && plans[k].sfc_time && plans[k].rsfc_normal && plans[k].rsfc_time;
@@ -408,7 +451,6 @@ static int session_create_impl(rbp_session** out, int device, int K, const rbp_w
             memcpy(&s->rsfc_time0[(size_t)k * M], plans[k].rsfc_time, sizeof(double) * Mq);
         }
     }
-    d.init_traj = traj, d.T = T, d.start = start, d.goal = goal, d.radius = radius, d.max_vel = mv, d.max_acc = ma;
 #undef UP
     int rc = rbp_session_reset(s, nullptr);
     if (rc) return rc;
@@ -427,6 +469,76 @@ int rbp_session_create_in(rbp_ctx* ctx, rbp_session** out, int K, const rbp_worl
                           const rbp_param* param, const rbp_plan* plans) {
     if (!ctx) return fail(RBP_ERR_BAD_ARGUMENT, "null context");
     return session_create_impl(out, ctx->device, K, worlds, missions, param, plans, ctx);
+}
+
+// A session of the missions a device search solved (rbp_dev_ecbs, kernels/ecbs.hip), built where its results lie: the worlds are the
+// resident grids of the search's set, referenced in place like any device grid above; T, init_traj and the mission arrays are written
+// into the arena by the two kernels of kernels/handoff.hip.  Checks, arena and layout are session_create_impl's.
+int rbp_session_create_from_ecbs(rbp_session** out, const rbp_dev_ecbs* e, const rbp_param* param, int32_t max_boxes, int32_t* slot_of) {
+    const char* who = "rbp_session_create_from_ecbs: ";
+    if (out) *out = nullptr;
+    if (!out || !e || !param) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "need out, the search's handle and param");
+    if (!e->have_limits) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "the search's missions came without max_vel / max_acc");
+    const int N = e->N, device = e->device;
+    std::vector<int> src;  // the missions the session holds
+    for (int k = 0; k < e->K; ++k) {
+        if (slot_of) slot_of[k] = e->status_h[k] == 0 ? (int)src.size() : -1;
+        if (e->status_h[k] == 0) src.push_back(k);
+    }
+    const int K = (int)src.size();
+    if (K == 0) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "no mission of the search has status 0");
+    int M = 0, MB = 0;  // session maxima = slot strides
+    std::vector<rbp_world> worlds(K);
+    std::vector<int> Mk(K), MBk(K);
+    for (int j = 0; j < K; ++j) {
+        Mk[j] = e->M_h[src[j]], MBk[j] = max_boxes > 0 ? max_boxes : Mk[j];
+        M = std::max(M, Mk[j]), MB = std::max(MB, MBk[j]);
+        if (int rc = rbp_dev_worlds_get(e->ws, e->world_index[src[j]], &worlds[j])) return rc;
+    }
+    if (int rc = check_session_param(param)) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const BatchSchedule sched = batch_schedule(param->sequential, param->batch_size, param->batch_iter, N);
+
+    struct Guard {  // every error path below releases the session (and with it the arena)
+        rbp_session* s;
+        ~Guard() {
+            if (s) rbp_session_destroy(s);
+        }
+    } guard{new rbp_session()};
+    rbp_session* s = guard.s;
+    s->device = device;
+    s->param = *param;
+    s->Mk = Mk, s->MBk = MBk;
+    s->bs = sched.bs, s->biter = sched.biter;
+    {
+        hipDeviceProp_t prop;
+        s->n_cu = hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 256;
+    }
+    if (int rc = session_reserve_arena(s, nullptr, device, session_arena_bytes(0, K, N, M, MB))) return rc;  // (cleared, and the clear complete)
+    if (int rc = session_describe(s, device, param, worlds.data(), K, N, M, MB)) return rc;
+    s->worlds_h.resize(K);
+    for (int j = 0; j < K; ++j) {
+        DevWorld& w = s->worlds_h[j];
+        for (int a = 0; a < 3; ++a) w.dim[a] = worlds[j].dim[a], w.key_min[a] = worlds[j].key_min[a];
+        w.res = worlds[j].res;
+        w.dist = worlds[j].dist;  // referenced in place: the set of worlds outlives the session (include/rbp.h)
+    }
+    SessionInputs in;
+    if (int rc = session_carve(s, in)) return rc;
+    HIP_TRY(hipMemcpy(in.worlds, s->worlds_h.data(), sizeof(DevWorld) * K, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(in.Mk, s->Mk.data(), sizeof(int) * K, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(in.MBk, s->MBk.data(), sizeof(int) * K, hipMemcpyHostToDevice));
+    DeviceBuffers b;  // the source list, freed when the kernels below have completed
+    const int* d_src = b.upload(src);
+    HIP_TRY(b.err);
+    if (int rc = launch_ecbs_plan_write(*e, K, d_src, in.Mk, M + 1, true, in.T, in.init_traj, nullptr)) return rc;
+    if (int rc = launch_ecbs_mission_gather(*e, K, d_src, in.start, in.goal, in.radius, in.max_vel, in.max_acc, nullptr)) return rc;
+    s->have_corridor_inputs = false;
+    if (int rc = rbp_session_reset(s, nullptr)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    guard.s = nullptr;
+    *out = s;
+    return RBP_OK;
 }
 
 // T, the SFC end times and the RSFC times are never rescaled on the device (timescale_kernel only records the factor and

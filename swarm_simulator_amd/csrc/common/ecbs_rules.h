@@ -1,6 +1,7 @@
 // ecbs_rules.h — the rules of the ECBS front-end that decide its bits, each stated once for the host search (host/ecbs.cpp, g++) and the
-// device search (kernels/ecbs.hip, kernels/edt.hip, hipcc): the planning lattice, position -> cell, the lattice samples of the obstacle
-// mask, the two conflict predicates and the writer of T / init_traj.  Everything else in either search is integer arithmetic on queues.
+// device search (kernels/ecbs.hip, kernels/edt.hip, kernels/handoff.hip, hipcc): the planning lattice, position -> cell, the lattice samples
+// of the obstacle mask, the two conflict predicates and the writer of T / init_traj, per element and as the host's loop.  Everything else
+// in either search is integer arithmetic on queues.
 // Plain C++17, no HIP runtime include.  ECBS_RULE functions are host + device functions under hipcc and inline functions under g++.
 //
 // Floating point, said here and nowhere else: both sides must round every operation of these rules alike, one IEEE double operation at
@@ -105,25 +106,34 @@ inline int plan_segments(int N, LenOf len_of, int32_t* makespan, int32_t* sum_co
     return *makespan + 2;
 }
 
-// T[0..M] and init_traj[N][stride][3], stride >= M + 1: per agent the start, its waypoints (in double, then octomap::point3d's float) and
-// the goal up to index M.  start / goal: the mission's [N][9] states.
+// One element of what write_plan writes, for the host loop below and for the kernel that writes a plan where the search left its paths
+// (kernels/handoff.hip).  The time of waypoint i:
+ECBS_RULE double plan_time(int i, double time_step) { return i * time_step; }
+
+// Coordinate `axis` of waypoint n of an agent whose path has `len` cells (path_cell(p): its cell p): waypoint 0 is the start state,
+// 1..len are the path cells (in double, then octomap::point3d's float), everything after them is the goal.  start / goal: the agent's [9] states.
+template <class PathCell>
+ECBS_RULE float plan_waypoint(int n, int axis, int len, PathCell path_cell, const double* start, const double* goal, const double gmin[3],
+                              const double gres[3]) {
+    if (n == 0) return (float)start[axis];
+    if (n > len) return (float)goal[axis];
+    const auto c = path_cell(n - 1);
+    const int ci = axis == 0 ? c.x() : axis == 1 ? c.y() : c.z();
+    return (float)(ci * gres[axis] + gmin[axis]);
+}
+
+// T[0..M] and init_traj[N][stride][3], stride >= M + 1: per agent the start, its waypoints and the goal up to index M.
+// start / goal: the mission's [N][9] states.
 template <class LenOf, class CellAt>
 inline void write_plan(int M, int N, LenOf len_of, CellAt cell_at, const double* start, const double* goal, const double gmin[3],
                        const double gres[3], double time_step, size_t stride, double* T, float* init_traj) {
-    for (int i = 0; i <= M; ++i) T[i] = i * time_step;
+    for (int i = 0; i <= M; ++i) T[i] = plan_time(i, time_step);
     for (int a = 0; a < N; ++a) {
         float* tr = init_traj + (size_t)a * stride * 3;
-        int n = 0;
-        auto push = [&](double x, double y, double z) {
-            tr[3 * n] = (float)x, tr[3 * n + 1] = (float)y, tr[3 * n + 2] = (float)z;
-            ++n;
-        };
-        push(start[9 * a], start[9 * a + 1], start[9 * a + 2]);
-        for (int p = 0; p < len_of(a); ++p) {
-            const auto c = cell_at(a, p);
-            push(c.x() * gres[0] + gmin[0], c.y() * gres[1] + gmin[1], c.z() * gres[2] + gmin[2]);
-        }
-        while (n <= M) push(goal[9 * a], goal[9 * a + 1], goal[9 * a + 2]);
+        const int len = len_of(a);
+        auto path_cell = [&](int p) { return cell_at(a, p); };
+        for (int n = 0; n <= M; ++n)
+            for (int axis = 0; axis < 3; ++axis) tr[3 * n + axis] = plan_waypoint(n, axis, len, path_cell, start + 9 * a, goal + 9 * a, gmin, gres);
     }
 }
 

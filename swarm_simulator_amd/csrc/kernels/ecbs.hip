@@ -88,16 +88,9 @@ struct Slot {  // what one wave works on
     int *len, *owner;
 };
 
-__host__ __device__ __forceinline__ int cx(unsigned c) { return (int)(c & 1023u); }
-__host__ __device__ __forceinline__ int cy(unsigned c) { return (int)((c >> 10) & 1023u); }
-__host__ __device__ __forceinline__ int cz(unsigned c) { return (int)(c >> 20); }
-struct PackedCell {  // a packed cell as the conflict rules and the plan writer of common/ecbs_rules.h read one
-    unsigned c;
-    __host__ __device__ int x() const { return cx(c); }
-    __host__ __device__ int y() const { return cy(c); }
-    __host__ __device__ int z() const { return cz(c); }
-    __host__ __device__ bool operator==(const PackedCell& o) const { return c == o.c; }
-};
+__host__ __device__ __forceinline__ int cx(unsigned c) { return PackedCell{c}.x(); }
+__host__ __device__ __forceinline__ int cy(unsigned c) { return PackedCell{c}.y(); }
+__host__ __device__ __forceinline__ int cz(unsigned c) { return PackedCell{c}.z(); }
 __device__ __forceinline__ unsigned pack_cell(int x, int y, int z) { return (unsigned)x | ((unsigned)y << 10) | ((unsigned)z << 20); }
 
 __device__ __forceinline__ int wave_min(int v) {
@@ -524,7 +517,14 @@ int ecbs_check_arguments(const char* who, int32_t K, const int32_t* dim_in, cons
     if (K <= 0 || !missions || !param || !out) return bad("need K > 0, missions, param and out");
     if (!out->status || !out->M || !out->makespan || !out->sum_cost || !out->high_level_expanded || !out->low_level_expanded || !out->T || !out->init_traj)
         return bad("every array of rbp_ecbs_out must be given");
-    if (out->max_M < 2 || out->max_M > ECBS_MAX_SEGMENTS) return bad("max_M must be 2..4096");
+    return ecbs_check_search(who, K, dim_in, missions, param, max_high_level_nodes, out->max_M, dim);
+}
+
+int ecbs_check_search(const char* who, int32_t K, const int32_t* dim_in, const rbp_mission* missions, const rbp_param* param,
+                      int64_t max_high_level_nodes, int32_t max_M, int32_t dim[3]) {
+    auto bad = [&](const char* what) { return rbp_set_error(RBP_ERR_BAD_ARGUMENT, (std::string(who) + ": " + what).c_str()); };
+    if (K <= 0 || !missions || !param) return bad("need K > 0, missions and param");
+    if (max_M < 2 || max_M > ECBS_MAX_SEGMENTS) return bad("max_M must be 2..4096");
     if (max_high_level_nodes < 1 || max_high_level_nodes > ECBS_MAX_HL_BUDGET) return bad("max_high_level_nodes must be 1..512 on the device");
     const int N = missions[0].N;
     if (N < 1 || N > ECBS_MAX_AGENTS) return bad("N must be 1..256");
@@ -536,24 +536,21 @@ int ecbs_check_arguments(const char* who, int32_t K, const int32_t* dim_in, cons
     int d[3];
     if (!ecbs_rules::planning_lattice(param, ECBS_MAX_DIM, gmin, gmax, gres, d)) return bad("the planning lattice needs 1..1024 cells per axis");
     if (dim_in && (dim_in[0] != d[0] || dim_in[1] != d[1] || dim_in[2] != d[2])) return bad("dim is not the planning lattice of param");
-    const size_t seen_bytes = (size_t)seen_layers(d, out->max_M) * (((size_t)d[0] * d[1] * d[2] + 31) / 32) * 4;
+    const size_t seen_bytes = (size_t)seen_layers(d, max_M) * (((size_t)d[0] * d[1] * d[2] + 31) / 32) * 4;
     if (seen_bytes > ECBS_MAX_SEEN_BYTES) return bad("lattice x time layers beyond the 16 MB seen bitmap of a wave");
     for (int a = 0; a < 3; ++a) dim[a] = d[a];
     return RBP_OK;
 }
 
-int ecbs_plan_on_device(const char* who, int32_t K, const int32_t dim[3], const unsigned char* d_masks, const unsigned* d_outside,
-                        const rbp_mission* missions, const rbp_param* param, int64_t max_high_level_nodes, rbp_ecbs_out* out) {
-    const int N = missions[0].N, max_M = out->max_M;
-    double gmin[3], gmax[3], gres[3];
+// The search on K masks of the current device, launched and not waited for.  The workspace of the wave slots and the kernel's inputs come
+// from `work`, what the search leaves behind (status, out_len, out_path, out_count) from `results`; gmin / gres receive the lattice.
+static int ecbs_launch(const char* who, int32_t K, const int32_t dim[3], const unsigned char* d_masks, const unsigned* d_outside, const rbp_mission* missions,
+                       const rbp_param* param, int64_t max_high_level_nodes, int max_M, DeviceBuffers& work, DeviceBuffers& results, EcbsDev& d,
+                       double gmin[3], double gres[3]) {
+    const int N = missions[0].N;
+    double gmax[3];
     int gd[3];
     ecbs_rules::planning_lattice(param, ECBS_MAX_DIM, gmin, gmax, gres, gd);
-    // every mission starts as "no result"
-    const size_t t_stride = (size_t)max_M + 1, traj_stride = (size_t)N * t_stride * 3;
-    for (int k = 0; k < K; ++k) out->status[k] = out->M[k] = out->makespan[k] = out->sum_cost[k] = 0, out->high_level_expanded[k] = out->low_level_expanded[k] = 0;
-    memset(out->T, 0, sizeof(double) * K * t_stride);
-    memset(out->init_traj, 0, sizeof(float) * K * traj_stride);
-
     // ecbs_planner.hpp:112-136: the cells of the start and goal positions (anything off the lattice is "occluded")
     std::vector<int> start((size_t)K * N * 3), goal(start.size());
     std::vector<double> radius((size_t)K * N);
@@ -567,7 +564,7 @@ int ecbs_plan_on_device(const char* who, int32_t K, const int32_t dim[3], const 
             }
         }
 
-    EcbsDev d{};
+    d = EcbsDev{};
     d.K = K, d.N = N, d.ncell = dim[0] * dim[1] * dim[2];
     for (int a = 0; a < 3; ++a) d.dim[a] = dim[a];
     d.seen_words = (d.ncell + 31) / 32, d.layers = seen_layers(gd, max_M);
@@ -585,7 +582,7 @@ int ecbs_plan_on_device(const char* who, int32_t K, const int32_t dim[3], const 
     if (e != hipSuccess) return fail(e, "device query");
     const int slots = std::min<int>(K, std::max(cus, 1) * ECBS_WAVES_PER_CU);
     const size_t path_cells = (size_t)N * d.stride;
-    DeviceBuffers b;
+    DeviceBuffers& b = work;
     d.start = b.upload(start), d.goal = b.upload(goal), d.radius = b.upload(radius);
     d.counter = b.get<unsigned>(1, true);
     d.ll_nodes = b.get<uint4>((size_t)slots * ECBS_LL_NODES);
@@ -597,18 +594,37 @@ int ecbs_plan_on_device(const char* who, int32_t K, const int32_t dim[3], const 
     d.root_path = b.get<unsigned>((size_t)slots * path_cells, true);
     d.root_len = b.get<int>((size_t)slots * N);
     d.sol_global = d.sol_in_lds ? nullptr : b.get<unsigned>((size_t)slots * path_cells, true);
-    d.status = b.get<int>(K);
-    d.out_len = b.get<int>((size_t)K * N, true);
-    d.out_path = b.get<unsigned>((size_t)K * path_cells, true);
-    d.out_count = b.get<long long>((size_t)K * 2);
     if (b.err != hipSuccess) return fail(b.err, "workspace");
+    d.status = results.get<int>(K);
+    d.out_len = results.get<int>((size_t)K * N, true);
+    d.out_path = results.get<unsigned>((size_t)K * path_cells, true);
+    d.out_count = results.get<long long>((size_t)K * 2);
+    if (results.err != hipSuccess) return fail(results.err, "workspace");
     hipLaunchKernelGGL(ecbs_kernel, dim3(slots), dim3(64), ecbs_lds_bytes(N, d.stride, d.sol_in_lds), 0, d);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(e, "launch");
+    return RBP_OK;
+}
+
+int ecbs_plan_on_device(const char* who, int32_t K, const int32_t dim[3], const unsigned char* d_masks, const unsigned* d_outside,
+                        const rbp_mission* missions, const rbp_param* param, int64_t max_high_level_nodes, rbp_ecbs_out* out) {
+    const int N = missions[0].N, max_M = out->max_M;
+    // every mission starts as "no result"
+    const size_t t_stride = (size_t)max_M + 1, traj_stride = (size_t)N * t_stride * 3;
+    for (int k = 0; k < K; ++k) out->status[k] = out->M[k] = out->makespan[k] = out->sum_cost[k] = 0, out->high_level_expanded[k] = out->low_level_expanded[k] = 0;
+    memset(out->T, 0, sizeof(double) * K * t_stride);
+    memset(out->init_traj, 0, sizeof(float) * K * traj_stride);
+
+    EcbsDev d{};
+    double gmin[3], gres[3];
+    DeviceBuffers b;
+    if (int rc = ecbs_launch(who, K, dim, d_masks, d_outside, missions, param, max_high_level_nodes, max_M, b, b, d, gmin, gres)) return rc;
+    auto fail = [&](hipError_t e, const char* what) { return rbp_set_error(RBP_ERR_HIP, (std::string(who) + ": " + what + ": " + hipGetErrorString(e)).c_str()); };
+    const size_t path_cells = (size_t)N * d.stride;
     std::vector<int> status(K), len((size_t)K * N);
     std::vector<unsigned> path((size_t)K * path_cells);
     std::vector<long long> count((size_t)K * 2);
-    e = hipMemcpy(status.data(), d.status, sizeof(int) * K, hipMemcpyDeviceToHost);  // (synchronises with the kernel)
+    hipError_t e = hipMemcpy(status.data(), d.status, sizeof(int) * K, hipMemcpyDeviceToHost);  // (synchronises with the kernel)
     if (e == hipSuccess) e = hipMemcpy(len.data(), d.out_len, sizeof(int) * len.size(), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(path.data(), d.out_path, sizeof(unsigned) * path.size(), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(count.data(), d.out_count, sizeof(long long) * count.size(), hipMemcpyDeviceToHost);
@@ -622,6 +638,48 @@ int ecbs_plan_on_device(const char* who, int32_t K, const int32_t dim[3], const 
         out->high_level_expanded[k] = count[2 * (size_t)k], out->low_level_expanded[k] = count[2 * (size_t)k + 1];
         ecbs_rules::write_plan(out->M[k], N, len_of, [&](int a, int p) { return PackedCell{path[((size_t)k * N + a) * d.stride + p]}; }, missions[k].start,
                                missions[k].goal, gmin, gres, param->time_step, t_stride, out->T + k * t_stride, out->init_traj + k * traj_stride);
+    }
+    return RBP_OK;
+}
+
+// The same search with its paths left on the device: only status, path lengths and counters come back, K x (N + 3) words, and the
+// missions' states and limits go up once as packed arrays, for the kernels of kernels/handoff.hip to read beside the paths.
+int ecbs_search_on_device(const char* who, int32_t K, const int32_t dim[3], const unsigned char* d_masks, const unsigned* d_outside,
+                          const rbp_mission* missions, const rbp_param* param, int64_t max_high_level_nodes, int32_t max_M, rbp_dev_ecbs* h) {
+    const int N = missions[0].N;
+    EcbsDev d{};
+    DeviceBuffers work;
+    if (int rc = ecbs_launch(who, K, dim, d_masks, d_outside, missions, param, max_high_level_nodes, max_M, work, h->results, d, h->gmin, h->gres)) return rc;
+    auto fail = [&](hipError_t e, const char* what) { return rbp_set_error(RBP_ERR_HIP, (std::string(who) + ": " + what + ": " + hipGetErrorString(e)).c_str()); };
+    (void)hipGetDevice(&h->device);
+    h->K = K, h->N = N, h->max_M = max_M, h->path_stride = d.stride, h->time_step = param->time_step;
+    h->status = d.status, h->out_len = d.out_len, h->out_path = d.out_path, h->out_count = d.out_count;
+    h->have_limits = true;
+    for (int k = 0; k < K; ++k) h->have_limits = h->have_limits && missions[k].max_vel && missions[k].max_acc;
+    // [K][N][9] start, [K][N][9] goal, [K][N] radius, [K][N][3] max_vel, [K][N][3] max_acc in one upload (limits that were not given stay zero)
+    const size_t kn = (size_t)K * N;
+    std::vector<double> packed(kn * 25, 0.0);
+    double *ps = packed.data(), *pg = ps + kn * 9, *pr = pg + kn * 9, *pv = pr + kn, *pa = pv + kn * 3;
+    for (int k = 0; k < K; ++k) {
+        const size_t o = (size_t)k * N;
+        memcpy(ps + o * 9, missions[k].start, sizeof(double) * N * 9), memcpy(pg + o * 9, missions[k].goal, sizeof(double) * N * 9);
+        memcpy(pr + o, missions[k].radius, sizeof(double) * N);
+        if (h->have_limits) memcpy(pv + o * 3, missions[k].max_vel, sizeof(double) * N * 3), memcpy(pa + o * 3, missions[k].max_acc, sizeof(double) * N * 3);
+    }
+    const double* dp = h->results.upload(packed);
+    if (h->results.err != hipSuccess) return fail(h->results.err, "missions");
+    h->start = dp, h->goal = dp + kn * 9, h->radius = dp + kn * 18, h->max_vel = dp + kn * 19, h->max_acc = dp + kn * 22;
+
+    h->status_h.assign(K, 0), h->len_h.assign(kn, 0), h->count_h.assign((size_t)K * 2, 0);
+    hipError_t e = hipMemcpy(h->status_h.data(), d.status, sizeof(int) * K, hipMemcpyDeviceToHost);  // (synchronises with the kernel)
+    if (e == hipSuccess) e = hipMemcpy(h->len_h.data(), d.out_len, sizeof(int) * kn, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h->count_h.data(), d.out_count, sizeof(long long) * K * 2, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(e, "results");
+    h->M_h.assign(K, 0), h->makespan_h.assign(K, 0), h->sum_cost_h.assign(K, 0);
+    for (int k = 0; k < K; ++k) {
+        if (h->status_h[k]) continue;
+        auto len_of = [&](int a) { return h->len_h[(size_t)k * N + a]; };
+        h->M_h[k] = ecbs_rules::plan_segments(N, len_of, &h->makespan_h[k], &h->sum_cost_h[k]);  // <= max_M: no path is longer than max_M - 2
     }
     return RBP_OK;
 }
@@ -649,4 +707,44 @@ extern "C" int rbp_dev_ecbs_plan_masks(int device, int32_t K, const int32_t dim_
                                    : rbp_set_error(RBP_ERR_HIP, (std::string("rbp_dev_ecbs_plan_masks: masks: ") + hipGetErrorString(e)).c_str());
     (void)hipFree(d_masks);
     return rc;
+}
+
+// ---- rbp_dev_ecbs: what a search left on the device (the search itself: rbp_dev_worlds_ecbs_search, kernels/edt.hip) ----------------------
+extern "C" int rbp_dev_ecbs_count(const rbp_dev_ecbs* e) { return e ? e->K : 0; }
+
+extern "C" void rbp_dev_ecbs_destroy(rbp_dev_ecbs* e) {
+    if (!e) return;
+    DeviceScope scope(e->device);
+    delete e;  // (frees `results` on the handle's device)
+}
+
+extern "C" int rbp_dev_ecbs_download(const rbp_dev_ecbs* e, rbp_ecbs_out* out) {
+    const char* who = "rbp_dev_ecbs_download";
+    auto bad = [&](const char* what) { return rbp_set_error(RBP_ERR_BAD_ARGUMENT, (std::string(who) + ": " + what).c_str()); };
+    if (!e || !out) return bad("need the handle and out");
+    if (!out->status || !out->M || !out->makespan || !out->sum_cost || !out->high_level_expanded || !out->low_level_expanded)
+        return bad("every per-mission array of rbp_ecbs_out must be given (T and init_traj may be null)");
+    if (out->max_M != e->max_M) return bad("out->max_M is not the max_M of the search");
+    const int K = e->K, N = e->N;
+    std::vector<int> Mj(K), src(K);
+    for (int k = 0; k < K; ++k) {
+        const bool ok = e->status_h[k] == 0;
+        out->status[k] = e->status_h[k], out->M[k] = e->M_h[k], out->makespan[k] = e->makespan_h[k], out->sum_cost[k] = e->sum_cost_h[k];
+        out->high_level_expanded[k] = ok ? e->count_h[2 * (size_t)k] : 0, out->low_level_expanded[k] = ok ? e->count_h[2 * (size_t)k + 1] : 0;
+        Mj[k] = ok ? e->M_h[k] : -1, src[k] = k;
+    }
+    if (!out->T && !out->init_traj) return RBP_OK;
+    auto fail = [&](hipError_t err) { return rbp_set_error(RBP_ERR_HIP, (std::string(who) + ": " + hipGetErrorString(err)).c_str()); };
+    DeviceScope scope(e->device);
+    const size_t stride = (size_t)e->max_M + 1, nT = (size_t)K * stride, ntr = (size_t)K * N * stride * 3;
+    DeviceBuffers b;
+    const int *d_M = b.upload(Mj), *d_src = b.upload(src);
+    double* d_T = b.get<double>(nT);
+    float* d_tr = b.get<float>(ntr);
+    if (b.err != hipSuccess) return fail(b.err);
+    if (int rc = launch_ecbs_plan_write(*e, K, d_src, d_M, (int)stride, false, d_T, d_tr, 0)) return rc;
+    hipError_t err = hipSuccess;
+    if (out->T) err = hipMemcpy(out->T, d_T, sizeof(double) * nT, hipMemcpyDeviceToHost);  // (synchronises with the kernel)
+    if (err == hipSuccess && out->init_traj) err = hipMemcpy(out->init_traj, d_tr, sizeof(float) * ntr, hipMemcpyDeviceToHost);
+    return err == hipSuccess ? RBP_OK : fail(err);
 }

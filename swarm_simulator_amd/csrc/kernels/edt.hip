@@ -483,3 +483,29 @@ extern "C" int rbp_dev_worlds_ecbs_plan(const rbp_dev_worlds* ws, int32_t K, con
     if (int rc = ecbs_masks_on_device(who, ws, K, world_index, missions, param, sdim, m)) return rc;
     return ecbs_plan_on_device(who, K, dim, m.mask, m.outside(), missions, param, max_high_level_nodes, out);
 }
+
+// the same search with its results left on the device (rbp_dev_ecbs; kernels/ecbs.hip ecbs_search_on_device): what
+// rbp_session_create_from_ecbs builds a session from and rbp_dev_ecbs_download reads
+extern "C" int rbp_dev_worlds_ecbs_search(const rbp_dev_worlds* ws, int32_t K, const int32_t* world_index, const rbp_mission* missions,
+                                          const rbp_param* param, int64_t max_high_level_nodes, int32_t max_M, rbp_dev_ecbs** out) {
+    const char* who = "rbp_dev_worlds_ecbs_search";
+    auto bad = [&](const char* what) { return rbp_set_error(RBP_ERR_BAD_ARGUMENT, (std::string(who) + ": " + what).c_str()); };
+    if (!out) return bad("null out");
+    *out = nullptr;
+    if (!ws || !world_index) return bad("need the set of worlds and world_index");
+    int32_t dim[3], sdim[3];
+    if (int rc = ecbs_check_search(who, K, nullptr, missions, param, max_high_level_nodes, max_M, dim)) return rc;
+    for (int k = 0; k < K; ++k)
+        if (world_index[k] < 0 || world_index[k] >= (int)ws->desc.size()) return bad("world index out of range");
+    DeviceScope scope(ws->device);
+    EcbsMasks m;
+    if (int rc = ecbs_masks_on_device(who, ws, K, world_index, missions, param, sdim, m)) return rc;
+    rbp_dev_ecbs* e = new rbp_dev_ecbs();
+    e->ws = ws, e->world_index.assign(world_index, world_index + K);
+    if (int rc = ecbs_search_on_device(who, K, dim, m.mask, m.outside(), missions, param, max_high_level_nodes, max_M, e)) {
+        delete e;
+        return rc;
+    }
+    *out = e;
+    return RBP_OK;
+}

@@ -158,6 +158,48 @@ int ecbs_check_arguments(const char* who, int32_t K, const int32_t* dim_in, cons
                          int64_t max_high_level_nodes, const rbp_ecbs_out* out, int32_t dim[3]);
 int ecbs_plan_on_device(const char* who, int32_t K, const int32_t dim[3], const unsigned char* d_masks, const unsigned* d_outside,
                         const rbp_mission* missions, const rbp_param* param, int64_t max_high_level_nodes, rbp_ecbs_out* out);
+// what ecbs_check_arguments checks of a search apart from its rbp_ecbs_out: for the search that fills none (rbp_dev_worlds_ecbs_search)
+int ecbs_check_search(const char* who, int32_t K, const int32_t* dim_in, const rbp_mission* missions, const rbp_param* param,
+                      int64_t max_high_level_nodes, int32_t max_M, int32_t dim[3]);
+
+struct PackedCell {  // a lattice cell of the device search, x | y << 10 | z << 20, as the conflict rules and the plan writer of common/ecbs_rules.h read one
+    unsigned c;
+    __host__ __device__ int x() const { return (int)(c & 1023u); }
+    __host__ __device__ int y() const { return (int)((c >> 10) & 1023u); }
+    __host__ __device__ int z() const { return (int)(c >> 20); }
+    __host__ __device__ bool operator==(const PackedCell& o) const { return c == o.c; }
+};
+
+// rbp_dev_ecbs (include/rbp.h): a search whose results stay where ecbs_kernel left them.  The device arrays belong to `results`; the
+// host keeps the few words the search reports per mission and what a plan's shape is computed from.
+struct rbp_dev_ecbs {
+    const rbp_dev_worlds* ws = nullptr;  // the set the missions were searched on (the caller keeps it alive)
+    int device = 0;
+    int K = 0, N = 0, max_M = 0, path_stride = 0;
+    double gmin[3] = {}, gres[3] = {}, time_step = 0;  // the planning lattice and plan/time_step of the search's param
+    bool have_limits = false;                        // every mission came with max_vel and max_acc (a session needs them)
+    DeviceBuffers results;
+    const int* status = nullptr;          // [K]
+    const int* out_len = nullptr;         // [K][N] cells of each path
+    const unsigned* out_path = nullptr;   // [K][N][path_stride] packed cells
+    const long long* out_count = nullptr; // [K][2]
+    const double *start = nullptr, *goal = nullptr, *radius = nullptr, *max_vel = nullptr, *max_acc = nullptr;  // [K][N][9 9 1 3 3]
+    std::vector<int> world_index, status_h, len_h, M_h, makespan_h, sum_cost_h;  // [K] ([K][N]: len_h)
+    std::vector<long long> count_h;                                               // [K][2]
+};
+// kernels/ecbs.hip: ecbs_plan_on_device up to and without the download of the paths -- fills `e` (but for ws / world_index) on the current device
+int ecbs_search_on_device(const char* who, int32_t K, const int32_t dim[3], const unsigned char* d_masks, const unsigned* d_outside,
+                          const rbp_mission* missions, const rbp_param* param, int64_t max_high_level_nodes, int32_t max_M, rbp_dev_ecbs* e);
+
+// kernels/handoff.hip: T / init_traj from the resident paths of `e`, written where a consumer wants them.  Destination slot j takes
+// mission src[j] of the search; Mj[j] is its segment count (< 0: no plan, the slot is written as zeros); both are device arrays [n].
+// T [n][stride], init_traj [n][N][stride][3], stride > every Mj; compact: inside its slot mission j is [N][Mj[j] + 1][3], a session's
+// layout (above).  Everything beyond a mission's own M is written as zero.
+int launch_ecbs_plan_write(const rbp_dev_ecbs& e, int n, const int* src, const int* Mj, int stride, bool compact, double* T, float* init_traj,
+                           hipStream_t st);
+// the five mission arrays [n][N][9 9 1 3 3] gathered from the packed copies of `e` by the same source list
+int launch_ecbs_mission_gather(const rbp_dev_ecbs& e, int n, const int* src, double* start, double* goal, double* radius, double* max_vel,
+                               double* max_acc, hipStream_t st);
 
 // launchers (defined in the .hip files)
 int launch_corridor(const DevSession& s, hipStream_t st);

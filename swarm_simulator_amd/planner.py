@@ -123,6 +123,12 @@ def lib():
             L.rbp_dev_ecbs_plan_masks.argtypes = [C.c_int, C.c_int32, P(C.c_int32), P(P(C.c_uint8)), P(A.rbp_mission), P(A.rbp_param), C.c_int64,
                                                   P(A.rbp_ecbs_out)]
             L.rbp_dev_worlds_ecbs_plan.argtypes = [C.c_void_p, C.c_int32, A.c_int32_p, P(A.rbp_mission), P(A.rbp_param), C.c_int64, P(A.rbp_ecbs_out)]
+            L.rbp_dev_worlds_ecbs_search.argtypes = [C.c_void_p, C.c_int32, A.c_int32_p, P(A.rbp_mission), P(A.rbp_param), C.c_int64, C.c_int32, P(C.c_void_p)]
+            L.rbp_dev_ecbs_count.argtypes = [C.c_void_p]
+            L.rbp_dev_ecbs_download.argtypes = [C.c_void_p, P(A.rbp_ecbs_out)]
+            L.rbp_dev_ecbs_destroy.argtypes = [C.c_void_p]
+            L.rbp_dev_ecbs_destroy.restype = None
+            L.rbp_session_create_from_ecbs.argtypes = [P(C.c_void_p), C.c_void_p, P(A.rbp_param), C.c_int32, A.c_int32_p]
         except AttributeError:
             if not os.environ.get("RBP_HIP_LIB"):
                 raise
@@ -158,6 +164,7 @@ EXPORTED_SYMBOLS = [
     "rbp_edt_dims", "rbp_edt_build",
     "rbp_dev_worlds_create", "rbp_dev_worlds_count", "rbp_dev_worlds_get", "rbp_dev_worlds_download", "rbp_dev_worlds_destroy",
     "rbp_dev_worlds_ecbs_obstacles", "rbp_dev_ecbs_plan_masks", "rbp_dev_worlds_ecbs_plan",
+    "rbp_dev_worlds_ecbs_search", "rbp_dev_ecbs_count", "rbp_dev_ecbs_download", "rbp_dev_ecbs_destroy", "rbp_session_create_from_ecbs",
 ]
 
 
@@ -288,6 +295,36 @@ class Session:
             raise RuntimeError(f"rbp_session_create failed rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
         if opts is not None:
             self.set_solver_opts(opts)
+
+    @classmethod
+    def from_ecbs(cls, dev_ecbs, param: Param, max_boxes=None, opts=None):
+        """the session of the missions a device search solved (ecbs_search_batch), built on the device from what the search left there
+        (rbp_session_create_from_ecbs): no trajectory comes to the host.  `slot_of[k]` is mission k's index in the session, -1 for a
+        mission without a plan; `plans` are empty PlanResults of each mission's shape for download().  The DeviceEcbs may be closed
+        right away; the DeviceWorlds it searched must outlive the session.  `param` is the plan's: its time_step should be the search's."""
+        import numpy as np
+        if not isinstance(dev_ecbs, DeviceEcbs):
+            raise TypeError("Session.from_ecbs takes a DeviceEcbs")
+        if not dev_ecbs._h:
+            raise RuntimeError("DeviceEcbs is closed")
+        self = cls.__new__(cls)
+        self._p = param.c_struct()
+        self._h = C.c_void_p()
+        slot_of = np.zeros(dev_ecbs.K, np.int32)
+        rc = lib().rbp_session_create_from_ecbs(C.byref(self._h), dev_ecbs._h, C.byref(self._p), int(max_boxes or 0), A.ptr(slot_of, A.c_int32_p))
+        if rc == A.RBP_ERR_BAD_ARGUMENT:
+            raise ValueError(f"rbp_session_create_from_ecbs rc={rc}: {last_error()}")
+        if rc:
+            raise RuntimeError(f"rbp_session_create_from_ecbs failed rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+        self.slot_of = slot_of
+        N = dev_ecbs.N
+        self.plans = [PlanResult(np.zeros((N, int(M) + 1, 3), np.float32), np.zeros(int(M) + 1), max_boxes) for M, st in zip(dev_ecbs.M, dev_ecbs.status) if st == 0]
+        self.K, self.param, self.device = len(self.plans), param, dev_ecbs.device
+        self._keep = (dev_ecbs._worlds,)
+        self._pl = (A.rbp_plan * self.K)(*[p.c_struct() for p in self.plans])
+        if opts is not None:
+            self.set_solver_opts(opts)
+        return self
 
     def set_solver_opts(self, opts=None, **kw):
         """rbp_solver_opts of this session (before its next run): Session.set_solver_opts(qp_schedule=2) or an object from solver_opts()"""
@@ -643,3 +680,63 @@ def ecbs_plan_batch(dev_worlds: DeviceWorlds, world_indices, missions, param: Pa
     ps, oc = param.c_struct(), out.c_struct()
     rc = lib().rbp_dev_worlds_ecbs_plan(dev_worlds._h, len(missions), A.ptr(idx, A.c_int32_p), ms, C.byref(ps), int(max_nodes), C.byref(oc))
     return _ecbs_finish("rbp_dev_worlds_ecbs_plan", rc, out)
+
+
+class DeviceEcbs:
+    """rbp_dev_ecbs (include/rbp.h): a device search whose results stay in HBM.  `status`, `M` and `ecbs_stats` (per mission, None where the
+    status is not 0) are what came back to the host; download() fetches the plans, Session.from_ecbs plans from them where they are."""
+
+    def __init__(self, handle, dev_worlds, K, N, max_M):
+        self._h, self._worlds, self.K, self.N, self.max_M, self.device = handle, dev_worlds, K, N, max_M, dev_worlds.device
+        self._scalars = self._fetch(False)
+        o = self._scalars
+        self.status, self.M = o.status, o.M
+        self.ecbs_stats = [None if o.status[k] else dict(makespan=int(o.makespan[k]), sum_cost=int(o.sum_cost[k]), high_level=int(o.high_level[k]),
+                                                          low_level=int(o.low_level[k])) for k in range(K)]
+
+    def _fetch(self, trajectories):
+        if not self._h:
+            raise RuntimeError("DeviceEcbs is closed")
+        out = EcbsOut(self.K, self.N, self.max_M)
+        oc = out.c_struct()
+        if not trajectories:
+            oc.T, oc.init_traj = None, None
+        rc = lib().rbp_dev_ecbs_download(self._h, C.byref(oc))
+        if rc:
+            raise RuntimeError(f"rbp_dev_ecbs_download rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+        return out
+
+    def download(self):
+        """the EcbsPlans ecbs_plan_batch returns for the same arguments, T / init_traj written on the device and copied back once"""
+        return _ecbs_finish("rbp_dev_ecbs_download", 0, self._fetch(True))
+
+    def close(self):
+        if self._h:
+            lib().rbp_dev_ecbs_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ecbs_search_batch(dev_worlds: DeviceWorlds, world_indices, missions, param: Param, max_nodes=A.RBP_ECBS_MAX_HIGH_LEVEL_NODES, max_M=64):
+    """ecbs_plan_batch whose results stay on the device (rbp_dev_worlds_ecbs_search): returns a DeviceEcbs.  The DeviceWorlds must outlive it."""
+    import numpy as np
+    if not isinstance(dev_worlds, DeviceWorlds):
+        raise TypeError("planner.ecbs_search_batch takes a DeviceWorlds")
+    if not dev_worlds._h:
+        raise RuntimeError("DeviceWorlds is closed")
+    missions, ms = _ecbs_missions(missions)
+    idx = np.ascontiguousarray(world_indices, np.int32)
+    if idx.shape != (len(missions),):
+        raise ValueError("need one world index per mission")
+    ps, h = param.c_struct(), C.c_void_p()
+    rc = lib().rbp_dev_worlds_ecbs_search(dev_worlds._h, len(missions), A.ptr(idx, A.c_int32_p), ms, C.byref(ps), int(max_nodes), int(max_M), C.byref(h))
+    if rc == A.RBP_ERR_BAD_ARGUMENT:
+        raise ValueError(f"rbp_dev_worlds_ecbs_search rc={rc}: {last_error()}")
+    if rc:
+        raise RuntimeError(f"rbp_dev_worlds_ecbs_search rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+    return DeviceEcbs(h, dev_worlds, len(missions), missions[0].qn, int(max_M))
