@@ -195,12 +195,12 @@ typedef struct rbp_solver_opts {
                                       two pivot tiles per pass over a knot's matrix (half the HBM traffic of the update; pays only with
                                       hundreds of resident missions: DESIGN.md 3.5) */
     int32_t qp_schedule;           /* batch QPs of the sequential schedule: 0 automatic; 1: one workgroup per mission runs everything
-                                      (qp_batch_kernel); 2: phase split -- chip-wide row sweeps as kernels of their own
-                                      (kernels/qp_phase.inc) */
+                                      (qp_batch_kernel).  2 was the phase split (chip-wide row sweeps as kernels of their own):
+                                      retired, it lost every comparison (docs/HISTORY.md r05); accepted here, refused by a PLANNER run */
     int32_t qp_variant;            /* qp_schedule 1: 0 automatic; 2: 512 threads, one workgroup per CU; 4: 256 threads, two per CU */
     int32_t qp_block_order;        /* qp_schedule 1: 1 = a session that is run again starts its longest missions first; 0 = plain order */
-    int32_t qp_groups;             /* qp_schedule 2: streams the missions are spread over (0 automatic, at most 8) */
-    int32_t qp_rounds;             /* qp_schedule 2: round budget (0 automatic: 48 per batch QP of the schedule) */
+    int32_t qp_groups;             /* reserved (a knob of the retired qp_schedule 2): >= 0, otherwise ignored */
+    int32_t qp_rounds;             /* reserved (a knob of the retired qp_schedule 2): >= 0, otherwise ignored */
     double qp_far_slack;           /* qp_schedule 1, first Gauss-Seidel pass, polish on: 0.7 [m].  The interior-point phase of a batch QP leaves
                                       out the frozen-neighbour rows whose slack at the starting point exceeds this for a whole (agent, segment)
                                       group; the polish verifies EVERY row, and a batch QP that does not end polished on the reduced set is

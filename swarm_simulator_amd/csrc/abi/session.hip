@@ -97,12 +97,6 @@ struct rbp_session {
     bool have_corridor_inputs = false;
     bool joint_wide = false;  // the joint QP (plan/sequential = false) runs on the grid-wide solver (kernels/jqp.hip): decided per PLANNER run
     JointStats joint_stats{};
-    // phase-split schedule of the batch QPs (kernels/qp_phase.inc): the session's missions run as up to QP_MAX_GROUPS groups on streams
-    // of their own, forked from / joined into the caller's stream by events (created on first use)
-    static constexpr int QP_MAX_GROUPS = 8;
-    hipStream_t gstream[QP_MAX_GROUPS] = {};
-    hipEvent_t gevent[QP_MAX_GROUPS + 1] = {};
-    int n_gstream = 0;
     int last_stages = 0;      // stages of the last rbp_session_run (time_scale only concerns a run that included the planner)
     // rbp_session_run_async of a grid-wide joint session: the solver's host loop (one synchronisation per interior-point round) runs on a
     // thread and a stream of the session's own; every later call on the session joins it first (join_worker)
@@ -709,24 +703,11 @@ static int run_impl(rbp_session* s, int stages, void* stream, bool async) {
         if (rc == RBP_ERR_EXCHANGE) return rc;  // (kernels/jqp.hip has recorded which exchange failed and why)
         if (rc) return fail(rc, "joint QP: HIP error");
         launch_planner_epilogue(s->d, st);
-    } else if ((stages & RBP_STAGE_PLANNER) && o.qp_schedule == 2 && !planner_has_phase_split()) {
-        return fail(RBP_ERR_BAD_ARGUMENT, "rbp_solver_opts.qp_schedule = 2: the phase-split schedule is not part of the release library (it loses everywhere: DESIGN.md 3.3); "
-                                          "the developer build lib/librbp_hip_dev.so (`make dev`) carries it");
     } else if ((stages & RBP_STAGE_PLANNER) && o.qp_schedule == 2) {
-        // phase split (kernels/qp_phase.inc): chip-wide row sweeps, one workgroup per mission for the chains; the missions are spread over a
-        // few streams whose rounds overlap
-        int G = o.qp_groups > 0 ? o.qp_groups : (s->d.K >= 1024 ? 2 : 1);
-        G = std::max(1, std::min(G, std::min((int)rbp_session::QP_MAX_GROUPS, s->d.K)));
-        while (s->n_gstream < G) {
-            const int g = s->n_gstream;
-            if (g == 0) HIP_TRY(hipEventCreateWithFlags(&s->gevent[0], hipEventDisableTiming));
-            HIP_TRY(hipStreamCreateWithFlags(&s->gstream[g], hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&s->gevent[1 + g], hipEventDisableTiming));
-            s->n_gstream++;
-        }
-        launch_planner_phased(s->d, s->qp_ws, s->qp_ws_per_mission, st, s->gstream, s->gevent, G, o.qp_rounds);
+        return fail(RBP_ERR_BAD_ARGUMENT, "rbp_solver_opts.qp_schedule = 2: the phase-split schedule was retired because it lost every comparison with one workgroup "
+                                          "per mission (docs/HISTORY.md, r05)");
     } else if (stages & RBP_STAGE_PLANNER) {
-        // one workgroup per mission (qp_batch_kernel; the default: see DESIGN.md 3.3 for the A/B against the phase split).  Two workgroups
+        // one workgroup per mission (qp_batch_kernel; docs/HISTORY.md r05 has the A/B against the retired phase split).  Two workgroups
         // per CU (the 256-thread build) pay off as soon as there are more missions than CUs: the 512-thread build would need a second round
         // (measured at 300/400/500 missions: +17-21 %)
         const bool w4 = o.qp_variant ? o.qp_variant == 4 : s->d.K > s->n_cu;
@@ -921,11 +902,6 @@ void rbp_session_destroy(rbp_session* s) {
         (void)hipSetDevice(s->device);
         (void)hipStreamDestroy(s->jstream);
         (void)hipEventDestroy(s->jev_in);
-    }
-    if (s->n_gstream > 0) {
-        (void)hipSetDevice(s->device);
-        (void)hipEventDestroy(s->gevent[0]);
-        for (int g = 0; g < s->n_gstream; ++g) (void)hipStreamDestroy(s->gstream[g]), (void)hipEventDestroy(s->gevent[1 + g]);
     }
     if (s->ws_own) {
         (void)hipSetDevice(s->device);

@@ -1,5 +1,5 @@
 // ipm_rows.h — the arithmetic of ONE inequality row g . x <= h of the primal-dual interior-point method, stated once for the batch QP
-// (kernels/qp.hip, qp_polish.inc, qp_phase.inc) and the grid-wide joint QP (kernels/jqp.hip, jqp_polish.inc): the Newton weight, the
+// (kernels/qp.hip, qp_polish.inc) and the grid-wide joint QP (kernels/jqp.hip, jqp_polish.inc): the Newton weight, the
 // predictor / affine / corrected (Mehrotra, Gondzio) pieces of a row, its accumulation into a control point's packed 3x3, the two copies of
 // a pair row, the polish's candidate rule, and the 3x3-block tridiagonal K0 chain of the polish.  Pure functions of scalars and small
 // arrays: where (s, z) come from, where results go and what is reduced stays with the sweeps.  Plain C++17, no HIP runtime include.

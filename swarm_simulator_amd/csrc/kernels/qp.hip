@@ -216,16 +216,7 @@ __host__ __device__ inline size_t ws_int_count(int N, int M, int nbmax) {
            3 * (size_t)nbmax * M * N /*nrm (floats)*/ + 8;
 }
 
-// PHASE-SPLIT PATH (round 5, see ph_advance): per mission a state record and the partial reductions of the chip-wide row sweeps live behind
-// the workspace proper (offset ws_core_doubles rounded up to four doubles)
-#define PH_STATE_DOUBLES 32  // >= sizeof(PhState) / 8
-__host__ __device__ inline int ph_nwg(int nb, int M) { return (nb * 6 * M + 255) / 256; }  // workgroups of a chip-wide sweep over one batch QP
-__host__ __device__ inline size_t ph_extra_doubles(int M, int nbmax) { return PH_STATE_DOUBLES + 8 * (size_t)ph_nwg(nbmax, M) + 8; }
-__host__ __device__ inline size_t ws_core_doubles(int N, int M, int nbmax);
-__host__ __device__ inline size_t ph_state_offset(int N, int M, int nbmax) { return (ws_core_doubles(N, M, nbmax) + 3) & ~size_t(3); }
-__host__ __device__ inline size_t ws_doubles(int N, int M, int nbmax) { return ph_state_offset(N, M, nbmax) + ph_extra_doubles(M, nbmax); }
-
-__host__ __device__ inline size_t ws_core_doubles(int N, int M, int nbmax) {
+__host__ __device__ inline size_t ws_doubles(int N, int M, int nbmax) {
     QpDims d = make_dims(N, M, 0, nbmax);
     size_t n = 7 * d.nslot_max + 12 * (size_t)nbmax * d.oq + (size_t)(d.npb ? d.npb : 1) * d.oq + 3 * (size_t)nbmax * 3 * d.oq +
                2 * (size_t)d.nj * d.nk + (size_t)d.nj * d.ldb * d.ldb + 2 * (size_t)d.nj * (d.nk < 36 ? d.nk : 36) * (d.nk < 36 ? d.nk : 36) +
@@ -498,10 +489,10 @@ __device__ __forceinline__ void row_op(double slack, double ga, double gd, size_
 //   frozen  (a,f,j6):       sg * n . x_a <= -rr + sg * n . dummy_f        :645-666   sg = +1 if a < f else -1
 // Control points j6 < 3 and j6 >= 6M-3 are pinned by the end-state equalities: their rows are constants and are only checked
 // once (presolve).  Work item = one free control point of one batch agent with ALL its rows (see the note above QpWs).
-// wi0 / wi_end / stride: the control points this thread takes (default: the whole batch QP on one workgroup; the chip-wide sweeps of the
-// phase-split path hand every workgroup a range of tiles, see ph_sweep)
+// The whole batch QP runs on one workgroup: a thread takes the control points threadIdx.x, threadIdx.x + QP_THREADS, ... below nb * oq.
 template <int PASS>
-__device__ void row_pass(const RowCtx& c, PassIO& io, int wi0 = threadIdx.x, int wi_end = 1 << 30, int stride = QP_THREADS) {
+__device__ void row_pass(const RowCtx& c, PassIO& io) {
+    const int wi0 = threadIdx.x;
     const QpDims& d = c.d;
     const QpWs& w = c.w;
     const int oq = d.oq, N = d.N, M = d.M, nb = d.nb;
@@ -513,10 +504,12 @@ __device__ void row_pass(const RowCtx& c, PassIO& io, int wi0 = threadIdx.x, int
     constexpr bool need_da = (PASS == PASS_AFF || PASS == PASS_STEP || PASS == PASS_UPBUILD);
     constexpr bool need_dd = (PASS == PASS_STEP || PASS == PASS_VERIFY || PASS == PASS_UPBUILD);
     const int ncp = nb * oq;
-    const int wi_stop = wi_end < ncp ? wi_end : ncp;
     // tiles are ranked by falling row count and handed to the waves round robin
+    // (the clamp never binds -- ncp <= QP_MAX_NB * oq -- but the compiler cannot know that and uses the bound wi < 2^30 it is given, like
+    // the signed wi0: without either the sweeps and qp_batch_kernel compile to other code than the one that was measured)
+    const int wi_stop = (1 << 30) < ncp ? (1 << 30) : ncp;
     for (int rnd = 0;; ++rnd) {
-        const int wi = wi0 + rnd * stride;
+        const int wi = wi0 + rnd * QP_THREADS;
         if (wi >= wi_stop) break;
         constexpr bool blk_pass = QP_ROW_BLK > 0 && pass_in_blocks(PASS);  // passes that take the round-6 prologue (LDS look-ups, global loads, blocks)
         constexpr bool pre_b = blk_pass && (PASS == PASS_BUILD || PASS == PASS_AFF || PASS == PASS_STEP || PASS == PASS_UPBUILD);
@@ -971,34 +964,7 @@ __device__ __forceinline__ void assemble_item(const AsmArgs& A, const double* Ss
     assemble_store(A, j, a, b, k, l, Sv, lower_only);
 }
 
-// All knot blocks' needed halves at once (the 256-thread build, before the factorisation): the 3x3 tiles (A, B) = (3a + k, 3b + l) with
-// A <= B are enumerated directly (no idle threads), and ASM_ILP tiles per thread are in flight at a time -- a tile is six dependent-free
-// loads, a few dozen flops and up to nine stores, so one tile at a time is a chain of memory round trips.
-constexpr int ASM_ILP = 6;  // (A/B on one box: 6 is 0.3 % ahead of 3)
-__device__ void assemble_needed_halves(const AsmArgs& A, int nj) {
-    const int n3 = 3 * A.nb, per = n3 * (n3 + 1) / 2, total = nj * per;
-    for (int base = threadIdx.x; base < total; base += ASM_ILP * QP_THREADS) {
-        double Sv[ASM_ILP][6];
-        int jj[ASM_ILP], ta[ASM_ILP], tb[ASM_ILP];
-#pragma unroll
-        for (int u = 0; u < ASM_ILP; ++u) {
-            const int it = base + u * QP_THREADS, itc = it < total ? it : total - 1;
-            const int j = itc / per, t = itc - j * per;
-            // row Ai of the upper-triangular enumeration: start(Ai) = Ai * n3 - Ai (Ai - 1) / 2 <= t
-            int Ai = (int)(((2 * n3 + 1) - sqrtf((float)((2 * n3 + 1) * (2 * n3 + 1) - 8 * t))) * 0.5f);
-            if (Ai * n3 - Ai * (Ai - 1) / 2 > t) Ai--;
-            if ((Ai + 1) * n3 - (Ai + 1) * Ai / 2 <= t) Ai++;
-            const int Bi = Ai + t - (Ai * n3 - Ai * (Ai - 1) / 2);
-            jj[u] = j + 1, ta[u] = Ai, tb[u] = Bi;
-            assemble_load(A, nullptr, j + 1, Ai / 3, Bi / 3, Ai % 3, Bi % 3, Sv[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < ASM_ILP; ++u)
-            if (base + u * QP_THREADS < total) assemble_store(A, jj[u], ta[u] / 3, tb[u] / 3, ta[u] % 3, tb[u] % 3, Sv[u], true);
-    }
-}
-
-// The same through the LDS, one wave per knot (r03): a knot's inputs -- the weight sums of its six control points for every batch agent,
+// The knot blocks through the LDS, one wave per knot (r03): a knot's inputs -- the weight sums of its six control points for every batch agent,
 // the pair weights, the pairs' normals of the two segments -- are fetched with coalesced loads into the wave's LDS scratch, the tiles are
 // computed from there into a symmetric LDS image of the block, and the image leaves as whole rows (16 bytes per lane, 1 KB per store
 // instruction).  Tile by tile from / to global memory a knot costs ~10^4 scattered 8-byte transactions, this way ~10^2 line requests --
@@ -2095,7 +2061,6 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
 //   two workgroup barriers per tile column.  L_jj overwrites the lower triangle of Td[j], L_{j+1,j} overwrites To[j].
 //   substitutions: block matvecs by the whole workgroup, the triangular solves by wave 0 tile by tile.
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ d4 ld4(const double* p) { return *reinterpret_cast<const d4*>(p); }
 // memory helpers of the tiled path: LDS = true turns the generic pointer into an LDS one (ds_read/ds_write instead of flat)
 #define AS_LDS __attribute__((address_space(3)))
 template <bool LDS>
@@ -3310,12 +3275,6 @@ __global__ __launch_bounds__(256) void qp_order_kernel(DevSession S) {
         S.qp_order[k] = k;
 }
 
-// the phase-split schedule (round 5: built, measured, loses everywhere -- DESIGN.md 3.3) is NOT part of the release library: `make dev`
-// (-DRBP_PHASE_SPLIT) compiles it into lib/librbp_hip_dev.so, where rbp_solver_opts.qp_schedule = 2 selects it (tests/test_gpu_phase.py)
-#if QP_THREADS == 256 && defined(RBP_PHASE_SPLIT)
-#include "qp_phase.inc"
-#endif
-
 }  // namespace
 
 // This file is compiled twice (csrc/Makefile), both with 256 VGPRs per lane: QP_THREADS=512 (one workgroup per CU: the fastest single
@@ -3372,68 +3331,3 @@ void QP_CAT(launch_planner, QP_SUFFIX)(const DevSession& s, void* qp_ws, size_t 
 #endif
     launch_planner_epilogue(s, st);
 }
-
-#if QP_THREADS == 256 && !defined(RBP_PHASE_SPLIT)
-void launch_planner_phased(const DevSession&, void*, size_t, hipStream_t, hipStream_t*, hipEvent_t*, int, int) {}  // (never reached: abi/session.hip refuses qp_schedule = 2)
-bool planner_has_phase_split() { return false; }
-#endif
-#if QP_THREADS == 256 && defined(RBP_PHASE_SPLIT)
-bool planner_has_phase_split() { return true; }
-// The PHASE-SPLIT schedule (kernels/qp_phase.inc): a fixed budget of rounds is enqueued on G streams (one group of missions each, forked
-// from and joined back into the caller's stream by events), nothing is synchronised.  rounds <= 0: the default budget of
-// QP_ROUNDS_PER_QP rounds per batch QP of the schedule (a batch QP takes ~18 interior-point iterations = rounds).
-#ifndef QP_ROUNDS_PER_QP
-#define QP_ROUNDS_PER_QP 48
-#endif
-void launch_planner_phased(const DevSession& s, void* qp_ws, size_t ws_bytes_per_mission, hipStream_t st, hipStream_t* gs, hipEvent_t* gev, int G,
-                           int rounds) {
-    const int N = s.N, M = s.M, K = s.K;
-    const BatchSchedule sched = batch_schedule(s.p.sequential, s.p.batch_size, s.p.batch_iter, N);
-    const int bs = sched.bs, biter = sched.biter;
-    launch_planner_prologue(s, st);
-    if (biter > 0 && s.p.iteration > 0) {
-        if (bs > QP_MAX_NB) {
-            (void)rbp_set_error(RBP_ERR_BAD_ARGUMENT, "launch_planner: batch wider than the QP kernel supports");
-            return;
-        }
-        const size_t lds = qp_lds_bytes(bs, M);
-        const int lds_doubles = (int)(lds / sizeof(double)) - 2;
-        (void)hipFuncSetAttribute((const void*)ph_advance, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)ph_corr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        double* ws = (double*)qp_ws;
-        const size_t stride = ws_bytes_per_mission / sizeof(double), st_off = ph_state_offset(N, M, bs);
-        if (rounds <= 0) rounds = s.p.iteration * biter * QP_ROUNDS_PER_QP + 8;
-        hipLaunchKernelGGL(ph_init, dim3((K + 255) / 256), dim3(256), 0, st, s, ws, stride, st_off);
-        if (G < 1) G = 1;
-        if (G > K) G = K;
-        const bool fork = G > 1 || gs[0] != st;
-        if (fork) {
-            (void)hipEventRecord(gev[0], st);
-            for (int g = 0; g < G; ++g) (void)hipStreamWaitEvent(gs[g], gev[0], 0);
-        }
-        const int nwg = ph_nwg(bs, M);
-        for (int r = 0; r < rounds; ++r)
-            for (int g = 0; g < G; ++g) {
-                const int m0 = (int)((long long)K * g / G), kg = (int)((long long)K * (g + 1) / G) - m0;
-                hipStream_t q = gs[g];
-                hipLaunchKernelGGL(ph_advance, dim3(kg), dim3(QP_THREADS), lds, q, s, ws, stride, st_off, m0, s.p.iteration, biter, bs, lds_doubles);
-                hipLaunchKernelGGL(ph_sweep<PASS_AFF>, dim3(nwg, kg), dim3(256), 0, q, s, ws, stride, st_off, m0, bs);
-                hipLaunchKernelGGL(ph_corr, dim3(kg), dim3(QP_THREADS), lds, q, s, ws, stride, st_off, m0, bs, lds_doubles);
-                hipLaunchKernelGGL(ph_sweep<PASS_STEP>, dim3(nwg, kg), dim3(256), 0, q, s, ws, stride, st_off, m0, bs);
-                hipLaunchKernelGGL(ph_ctrl, dim3(kg), dim3(QP_THREADS), 0, q, s, ws, stride, st_off, m0, bs, 0);
-                hipLaunchKernelGGL(ph_sweep<PASS_UPBUILD>, dim3(nwg, kg), dim3(256), 0, q, s, ws, stride, st_off, m0, bs);
-                for (int rep = 0; rep < 2; ++rep) {
-                    hipLaunchKernelGGL(ph_ctrl, dim3(kg), dim3(QP_THREADS), 0, q, s, ws, stride, st_off, m0, bs, 1);
-                    hipLaunchKernelGGL(ph_sweep<PASS_UPBUILD>, dim3(nwg, kg), dim3(256), 0, q, s, ws, stride, st_off, m0, bs);
-                }
-            }
-        if (fork)
-            for (int g = 0; g < G; ++g) {
-                (void)hipEventRecord(gev[1 + g], gs[g]);
-                (void)hipStreamWaitEvent(st, gev[1 + g], 0);
-            }
-        hipLaunchKernelGGL(ph_finish, dim3((K + 255) / 256), dim3(256), 0, st, s, ws, stride, st_off);
-    }
-    launch_planner_epilogue(s, st);
-}
-#endif

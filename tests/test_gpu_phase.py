@@ -1,9 +1,6 @@
-"""The PHASE-SPLIT schedule of the batch QPs (kernels/qp_phase.inc, rbp_solver_opts.qp_schedule = 2; since round 6 in the developer build
-lib/librbp_hip_dev.so only -- the release library refuses it -- so its cases, tests/phase_split_cases.py, run in a process of their own): chip-wide row sweeps as kernels of
-their own, one workgroup per mission for chains and polish, a fixed budget of rounds enqueued without synchronisation.  Same device
-functions as qp_batch_kernel (one workgroup per mission for everything, the default); only the block reductions of a sweep are summed in a
-different order (and the monolith's interior-point phase works on the reduced row set of QP_FAR_SLACK in the first pass, the phase split on
-every row): both schedules land on the same KKT-certified optimum.  Needs an MI355X."""
+"""The reduced row set of the batch QPs' interior-point phase (rbp_solver_opts.qp_far_slack, kernels/qp.hip QP_FAR_SLACK) on both builds of
+qp_batch_kernel, and the refusal of rbp_solver_opts.qp_schedule = 2: the phase-split schedule (chip-wide row sweeps as kernels of their
+own) lost every comparison and left the tree, see docs/HISTORY.md r05.  Needs an MI355X."""
 import numpy as np
 import pytest
 
@@ -15,43 +12,16 @@ from tests import oracle_lib as O
 pytestmark = pytest.mark.gpu
 
 
-def _run(worlds, missions, p, inits, times=1, **opts):
-    plans = [g.clone_inputs() for g in inits]
-    sess = planner.Session(worlds, missions, p, plans, opts=planner.solver_opts(**opts))
-    outs = []
-    for _ in range(times):
-        sess.reset()
-        sess.run(A.RBP_STAGE_ALL)
-        assert sess.download() == [0] * len(plans)
-        outs.append([g.ctrl.copy() for g in plans])
-    sess.close()
-    return plans, outs
-
-
-def test_release_library_refuses_the_phase_split_schedule():
-    """kernels/qp_phase.inc lost every comparison and is compiled by `make dev` only: the release library says so, before any launch"""
+def test_the_retired_phase_split_schedule_is_refused():
+    """the phase-split schedule lost every comparison (docs/HISTORY.md r05) and was retired: a PLANNER run with qp_schedule = 2 says so, before any launch"""
     p = Param.test_sweep()
     m = host.load_mission("mission_8agents_15.json")
     w = host.load_world("map5.bt", p)
     g = host.ecbs_plan(w, m, p)
     sess = planner.Session([w], [m], p, [g], opts=planner.solver_opts(qp_schedule=2))
-    with pytest.raises(RuntimeError, match="phase-split schedule is not part of the release library"):
+    with pytest.raises(RuntimeError, match="phase-split schedule was retired because it lost every comparison"):
         sess.run(A.RBP_STAGE_ALL)
     sess.close()
-
-
-def test_phase_split_cases_in_the_developer_build():
-    """tests/phase_split_cases.py against lib/librbp_hip_dev.so: the two schedules agree to 2e-7 m, solve and polish the same QPs, two groups of
-    missions give the same bits as one; a round budget that does not finish a mission is RBP_ERR_QP_FAILED"""
-    import os
-    import subprocess
-    import sys
-    dev = os.path.join(A.LIB_DIR, "librbp_hip_dev.so")
-    assert os.path.exists(dev), "lib/librbp_hip_dev.so is missing: __graft_entry__.build() (make dev) builds it"
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-m", "pytest", "tests/phase_split_cases.py", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider"], cwd=root,
-                       env={**os.environ, "RBP_HIP_LIB": dev}, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
 
 def test_reduced_row_set_is_the_same_optimum_for_any_radius():

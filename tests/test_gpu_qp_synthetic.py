@@ -14,15 +14,12 @@ kernel's own ctrl.
   test_solo_sessions...               each case in a session of its own (slot strides M and P in place of the session's maxima): same bits
   test_grid_wide_joint_solver[N]      N = 2, 3, 7, 16 as joint QPs on kernels/jqp.hip (its outcome stands apart from the batch kernel's)
   test_both_kernel_builds[variant]    the N = 7 sessions on the 512-thread and the 256-thread build of qp_batch_kernel
-  test_developer_build                the N = 7 sessions through lib/librbp_hip_dev.so, whose 256-thread build of the kernel has the plain row
-                                      loops (QP_ROW_BLK = 0), in a process of its own as tests/test_gpu_phase.py runs its cases
   test_time_step_end_to_end           plan/time_step = 0.5, 1, 1.7 from the ECBS front end on: T = arange(M + 1) * time_step, certified,
                                       and the same optimum (it does not depend on a uniform scale)
   test_one_shot_route[N]              Corridor + RBPPlanner for one N = 1 and one N = 3 case; N = 1 hands over a zero-length rsfc_normal
 """
 import functools
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -152,18 +149,6 @@ def test_both_kernel_builds(variant):
     for si in (0, 1):
         st, plans = ragged(7, si, variant=variant)
         check_session(7, si, st, plans, f"qp_variant {variant}")
-
-
-def test_developer_build():
-    """lib/librbp_hip_dev.so compiles the 256-thread build of qp_batch_kernel without the blocked prologue of a control point (-DQP_ROW_BLK=0;
-    its 512-thread build is the release library's): the N = 7 sessions with qp_variant = 4 there"""
-    dev = os.path.join(A.LIB_DIR, "librbp_hip_dev.so")
-    assert os.path.exists(dev), "lib/librbp_hip_dev.so is missing: __graft_entry__.build() (make dev) builds it"
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_qp_synthetic.py::test_both_kernel_builds[4]", "-x", "-q", "-s", "-m", "gpu",
-                        "-p", "no:cacheprovider"], cwd=root, env={**os.environ, "RBP_HIP_LIB": dev}, capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0 and "1 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
 
 def test_time_step_end_to_end():

@@ -12,8 +12,7 @@ import argparse, concurrent.futures, glob, os, re, subprocess, sys
 
 BASE = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off --cuda-device-only -S -o -".split()
 W2, W4 = "-DQP_WAVES_PER_EU=2 -DQP_ROW_PF=4 -DQP_SUFFIX=_w2".split(), "-DQP_THREADS=256 -DQP_WAVES_PER_EU=2 -DQP_SUFFIX=_w4".split()
-QP_VARIANTS = {"_w2": W2, "_w4": W4, "prof _w2": ["-DQP_PROFILE"] + W2, "prof _w4": ["-DQP_PROFILE"] + W4,
-               "dev _w4": ["-DRBP_PHASE_SPLIT", "-DQP_ROW_BLK=0"] + W4}
+QP_VARIANTS = {"_w2": W2, "_w4": W4, "prof _w2": ["-DQP_PROFILE"] + W2, "prof _w4": ["-DQP_PROFILE"] + W4}
 LOCAL = re.compile(r"\.(LBB|Ltmp|LJTI|Lfunc_begin|Lfunc_end)[0-9]+(_[0-9]+)?")
 
 
