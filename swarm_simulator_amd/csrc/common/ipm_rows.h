@@ -180,37 +180,85 @@ IPM_ROW double pair_dot(bool a_lo, double n0, double n1, double n2, double d0, d
 }
 
 // ---- the K0 chain of the polish ------------------------------------------------------------------------------------------
-// K0 = F'(2Q)F per (agent, dim): block tridiagonal with 3x3 blocks D_j and T_{j+1,j} = E_j'.  Its factor, 18 doubles per knot:
+// K0 = F'(2Q)F per (agent, dim): block tridiagonal with 3x3 blocks D_j and T_{j+1,j} = E_j'.  Its factor, 18 values per knot:
 //   f[0..8] = L_jj (lower, row-major) with RECIPROCAL pivots in the diagonal slots (the solves multiply),  f[9..17] = B_jj = T_{j+1,j} L_jj^-T
+// The chain is written for a value type T: double for the factor the polish solves its gradient column with, dd (below) for the table of
+// the inverse, whose entries must be good to the last bit of a double.
+//
+// dd: an unevaluated sum h + l of two doubles, |l| <= ulp(h) / 2 (Dekker; error-free sums and fma products, ~106 bits)
+struct dd {
+    double h, l;
+    IPM_ROW dd() : h(0), l(0) {}
+    IPM_ROW dd(double x) : h(x), l(0) {}
+    IPM_ROW dd(double hh, double ll) : h(hh), l(ll) {}
+};
+IPM_ROW dd dd_quick(double a, double b) {  // |a| >= |b|
+    const double s = a + b;
+    return dd(s, b - (s - a));
+}
+IPM_ROW dd dd_sum(double a, double b) {
+    const double s = a + b, bb = s - a;
+    return dd(s, (a - (s - bb)) + (b - bb));
+}
+IPM_ROW dd operator+(dd a, dd b) {
+    dd s = dd_sum(a.h, b.h);
+    const dd t = dd_sum(a.l, b.l);
+    s = dd_quick(s.h, s.l + t.h);
+    return dd_quick(s.h, s.l + t.l);
+}
+IPM_ROW dd operator-(dd a) { return dd(-a.h, -a.l); }
+IPM_ROW dd operator-(dd a, dd b) { return a + (-b); }
+IPM_ROW dd operator*(dd a, dd b) {
+    const double p = a.h * b.h;
+    return dd_quick(p, fma(a.h, b.h, -p) + (a.h * b.l + a.l * b.h));
+}
+IPM_ROW dd operator/(dd a, dd b) {
+    const double q1 = a.h / b.h;
+    dd r = a - b * dd(q1);
+    const double q2 = r.h / b.h;
+    r = r - b * dd(q2);
+    const double q3 = r.h / b.h;
+    return dd_quick(q1, q2) + dd(q3);
+}
+IPM_ROW dd& operator-=(dd& a, dd b) { return a = a - b; }
+IPM_ROW bool operator>(dd a, dd b) { return a.h > b.h || (a.h == b.h && a.l > b.l); }
+IPM_ROW double k0_sqrt(double a) { return sqrt(a); }
+IPM_ROW dd k0_sqrt(dd a) {  // one Newton step on the double's root (a > 0)
+    const double x = 1.0 / sqrt(a.h), ax = a.h * x;
+    return dd_sum(ax, (a - dd(ax) * dd(ax)).h * (x * 0.5));
+}
+
 // k0_factor_step: on entry f = (D_j, E_j) (E_j zero behind the last knot) and Bp = B_{j-1} (zero in front of the first); on exit the
 // factor of the knot in f and B_j in Bp.  Returns false when a pivot is not positive.
-IPM_ROW bool k0_factor_step(double* f, double (&Bp)[9], bool first) {
+template <class T>
+IPM_ROW bool k0_factor_step(T* f, T (&Bp)[9], bool first) {
     bool ok = true;
-    double A[9], Ej[9];
+    T A[9], Ej[9];
     for (int e = 0; e < 9; ++e) A[e] = f[e], Ej[e] = f[9 + e];
     if (!first)
         for (int r = 0; r < 3; ++r)
             for (int c = 0; c < 3; ++c) A[3 * r + c] -= Bp[3 * r] * Bp[3 * c] + Bp[3 * r + 1] * Bp[3 * c + 1] + Bp[3 * r + 2] * Bp[3 * c + 2];
-    if (!(A[0] > 0)) ok = false;
-    const double l00 = sqrt(A[0]), l10 = A[3] / l00, l20 = A[6] / l00;
-    const double d11 = A[4] - l10 * l10;
-    if (!(d11 > 0)) ok = false;
-    const double l11 = sqrt(d11), l21 = (A[7] - l20 * l10) / l11;
-    const double d22 = A[8] - l20 * l20 - l21 * l21;
-    if (!(d22 > 0)) ok = false;
-    const double l22 = sqrt(d22);
-    f[0] = 1.0 / l00, f[1] = 0, f[2] = 0, f[3] = l10, f[4] = 1.0 / l11, f[5] = 0, f[6] = l20, f[7] = l21, f[8] = 1.0 / l22;
+    const T zero = T(0.0), one = T(1.0);
+    if (!(A[0] > zero)) ok = false;
+    const T l00 = k0_sqrt(A[0]), l10 = A[3] / l00, l20 = A[6] / l00;
+    const T d11 = A[4] - l10 * l10;
+    if (!(d11 > zero)) ok = false;
+    const T l11 = k0_sqrt(d11), l21 = (A[7] - l20 * l10) / l11;
+    const T d22 = A[8] - l20 * l20 - l21 * l21;
+    if (!(d22 > zero)) ok = false;
+    const T l22 = k0_sqrt(d22);
+    f[0] = one / l00, f[1] = zero, f[2] = zero, f[3] = l10, f[4] = one / l11, f[5] = zero, f[6] = l20, f[7] = l21, f[8] = one / l22;
     for (int r = 0; r < 3; ++r) {
-        const double o0 = Ej[r], o1 = Ej[3 + r], o2 = Ej[6 + r];  // T_{j+1,j}[r][c] = E_j[3c + r]
-        const double x0 = o0 / l00, x1 = (o1 - x0 * l10) / l11, x2 = (o2 - x0 * l20 - x1 * l21) / l22;
+        const T o0 = Ej[r], o1 = Ej[3 + r], o2 = Ej[6 + r];  // T_{j+1,j}[r][c] = E_j[3c + r]
+        const T x0 = o0 / l00, x1 = (o1 - x0 * l10) / l11, x2 = (o2 - x0 * l20 - x1 * l21) / l22;
         f[9 + 3 * r] = Bp[3 * r] = x0, f[10 + 3 * r] = Bp[3 * r + 1] = x1, f[11 + 3 * r] = Bp[3 * r + 2] = x2;
     }
     return ok;
 }
 // one knot of L y = b (forward) and of L' x = y (backward): y holds the knot's three values on entry and the result on exit, p the result
 // of the knot before (forward) / behind (backward), link whether there is one.  f: the knot's factor (a pointer of any address space).
-template <class F>
-IPM_ROW void k0_forward_step(F f, bool link, double (&y)[3], const double (&p)[3]) {
+template <class F, class T>
+IPM_ROW void k0_forward_step(F f, bool link, T (&y)[3], const T (&p)[3]) {
     if (link) {
         const F Bm = f - 9;  // B_{j-1}
         y[0] -= Bm[0] * p[0] + Bm[1] * p[1] + Bm[2] * p[2];
@@ -221,8 +269,8 @@ IPM_ROW void k0_forward_step(F f, bool link, double (&y)[3], const double (&p)[3
     y[1] = (y[1] - f[3] * y[0]) * f[4];
     y[2] = (y[2] - f[6] * y[0] - f[7] * y[1]) * f[8];
 }
-template <class F>
-IPM_ROW void k0_backward_step(F f, bool link, double (&y)[3], const double (&p)[3]) {
+template <class F, class T>
+IPM_ROW void k0_backward_step(F f, bool link, T (&y)[3], const T (&p)[3]) {
     if (link) {
         const F Bm = f + 9;  // y_j -= B_j' y_{j+1}
         y[0] -= Bm[0] * p[0] + Bm[3] * p[1] + Bm[6] * p[2];
@@ -232,6 +280,76 @@ IPM_ROW void k0_backward_step(F f, bool link, double (&y)[3], const double (&p)[
     y[2] = y[2] * f[8];
     y[1] = (y[1] - f[7] * y[2]) * f[4];
     y[0] = (y[0] - f[3] * y[1] - f[6] * y[2]) * f[0];
+}
+
+// ---- G = K0^-1, formed once per mission ------------------------------------------------------------------------------------
+// K0 depends on the segment times alone, and everything the polish wants from K0^-1 J' is a contraction of a row's three coefficients with
+// 3x3 blocks of G.  Stored: the lower block triangle, block (ja, jb) with ja >= jb row-major at k0g_block(ja, jb); G[jb][ja] = G[ja][jb]'.
+IPM_ROW size_t k0g_block(int ja, int jb) { return 9 * ((size_t)ja * (ja + 1) / 2 + jb); }
+IPM_ROW size_t k0g_doubles(int nj) { return k0g_block(nj, 0); }
+// element (3 ja + r, 3 jb + c) of G, any ja and jb
+template <class P>
+IPM_ROW double k0g_at(P G, int ja, int r, int jb, int c) {
+    return ja >= jb ? G[k0g_block(ja, jb) + 3 * r + c] : G[k0g_block(jb, ja) + 3 * c + r];
+}
+// t_a' G[ja][jb] t_b, any ja and jb; blk: the stored block of the pair (the larger knot first)
+template <class P>
+IPM_ROW double k0g_bilinear(P blk, bool a_first, const double (&ta)[3], const double (&tb)[3]) {
+    const double (&tr)[3] = a_first ? ta : tb;  // rows of the stored block belong to the larger knot
+    const double (&tc)[3] = a_first ? tb : ta;
+    return tr[0] * (blk[0] * tc[0] + blk[1] * tc[1] + blk[2] * tc[2]) + tr[1] * (blk[3] * tc[0] + blk[4] * tc[1] + blk[5] * tc[2]) +
+           tr[2] * (blk[6] * tc[0] + blk[7] * tc[1] + blk[8] * tc[2]);
+}
+// Column c of block column jb, rows ja >= jb, solved in place in the table (f: the dd factor of k0_factor_step, G: the table, lo: a
+// second array of the table's shape that holds the low halves between the two passes).  The right-hand side is a unit vector: the
+// forward pass starts at knot jb (everything in front of it stays zero) and only stores; the backward pass stops at knot jb and fetches
+// its knots in blocks of K0_BLK, the next block requested before the current one is worked on, so that a column costs a handful of trips
+// to memory and not one per knot.
+// Why dd: K0's condition number is 1e10 .. 1e11 at 35 knots.  A column solved in double has a small residual K0 g - e, but its entries
+// are only good to ~1e-8 of the largest, and a SYMMETRIC table takes the part above the diagonal from other columns: assembled from
+// double solves its residual max|K0 G - I| came out a thousand times that of the columns themselves (3e-5 against 3e-8, unit times).
+// With the chain in dd every stored entry is the correctly rounded one, and the table's residual is that of the rounding alone.
+constexpr int K0_BLK = 6;
+template <class F, class P>
+IPM_ROW void k0_inverse_column(F f, int nj, int jb, int c, P G, P lo) {
+    dd p[3];
+    for (int ja = jb; ja < nj; ++ja) {
+        dd y[3];
+        if (ja == jb) y[0] = dd(c == 0 ? 1.0 : 0.0), y[1] = dd(c == 1 ? 1.0 : 0.0), y[2] = dd(c == 2 ? 1.0 : 0.0);
+        k0_forward_step(f + 18 * ja, ja > jb, y, p);
+        const size_t o = k0g_block(ja, jb) + c;
+        for (int e = 0; e < 3; ++e) p[e] = y[e], G[o + 3 * e] = y[e].h, lo[o + 3 * e] = y[e].l;
+    }
+    constexpr int B = K0_BLK;
+    dd cur[B][3], nxt[B][3];
+    for (int u = 0; u < B; ++u) {
+        const int jx = nj - 1 - u >= jb ? nj - 1 - u : jb;
+        const size_t o = k0g_block(jx, jb) + c;
+        for (int e = 0; e < 3; ++e) cur[u][e] = dd(G[o + 3 * e], lo[o + 3 * e]);
+    }
+    for (int jt = nj - 1; jt >= jb; jt -= B) {
+        for (int u = 0; u < B; ++u) {
+            const int jx = jt - B - u >= jb ? jt - B - u : jb;
+            const size_t o = k0g_block(jx, jb) + c;
+            for (int e = 0; e < 3; ++e) nxt[u][e] = dd(G[o + 3 * e], lo[o + 3 * e]);
+        }
+        for (int u = 0; u < B; ++u) {
+            const int jj = jt - u;
+            if (jj >= jb) {
+                k0_backward_step(f + 18 * jj, jj + 1 < nj, cur[u], p);
+                const size_t o = k0g_block(jj, jb) + c;
+                for (int e = 0; e < 3; ++e) p[e] = cur[u][e], G[o + 3 * e] = cur[u][e].h;
+            }
+        }
+        for (int u = 0; u < B; ++u)
+            for (int e = 0; e < 3; ++e) cur[u][e] = nxt[u][e];
+    }
+}
+// the diagonal blocks are the only entries the table holds twice: both copies get their mean, and the table is symmetric exactly
+template <class P>
+IPM_ROW void k0g_symmetrise(P blk) {
+    const double a = 0.5 * (blk[1] + blk[3]), b = 0.5 * (blk[2] + blk[6]), c = 0.5 * (blk[5] + blk[7]);
+    blk[1] = blk[3] = a, blk[2] = blk[6] = b, blk[5] = blk[7] = c;
 }
 
 }  // namespace ipm

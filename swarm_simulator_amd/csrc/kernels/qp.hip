@@ -116,8 +116,12 @@
                      // workgroups are meant to share a CU's LDS in pairs)
 #define PL_PBIG 192  // second attempt of a polish whose dual solve ran out of capacity: factor in global memory (rare: ~1 batch QP in 800)
 __host__ __device__ inline int polish_pmax(int nk) { return nk <= 36 ? 112 : PL_PMAX; }
-__host__ __device__ inline size_t polish_ws_doubles(int nj, int nk) {  // cand, V, S, counters, big factor
-    return PL_NC * 14 + (size_t)(PL_NC + 1) * nj * nk + PL_NC * PL_NC + 8 + lhp_size(PL_PBIG);
+// polish workspace.  Per mission (mission_tables): the factor of K0 (18 nj, then its failure flag) and the table of K0^-1; per batch QP:
+// cand, S, counters, big factor, the primal step's table of active rows (an entry per row, agent and axis: four doubles), and last the
+// gradient column v0 with the gradient and the primal step's right-hand side behind it, the only part that depends on the batch's nk.  (S also lends its storage to mission_tables: low halves of the table.)
+__host__ __device__ inline size_t polish_s_doubles(int nj) { return std::max((size_t)PL_NC * PL_NC, ipm::k0g_doubles(nj)); }
+__host__ __device__ inline size_t polish_ws_doubles(int nj, int nk) {
+    return 18 * (size_t)nj + 2 + ipm::k0g_doubles(nj) + PL_NC * 14 + polish_s_doubles(nj) + 8 + lhp_size(PL_PBIG) + 4 * 6 * PL_PBIG + 3 * (size_t)nj * nk;
 }
 __host__ __device__ inline int polish_lds_doubles(int nk) {
     const int pm = polish_pmax(nk);
@@ -2570,7 +2574,7 @@ __device__ __forceinline__ bool qp_setup_batch(const DevSession& S, RowCtx& c, d
     const QpDims& d = c.d;
     const QpWs& w = c.w;
     const int M = d.M;
-    mission_constants(d, T, const_cast<QpWs&>(w));
+    // (segsc, Lk, Dk, Ek and the polish's K0 tables are the mission's: mission_tables, once per launch)
     init_block_pads(d, w);
 
     // SFC box of every (batch agent, segment): first box with end time >= T[m+1]  (rbp_planner.hpp:447-453)
@@ -2886,12 +2890,7 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
     const double blk_doubles = d.nk <= 36 ? 5.0 * (d.nk * (d.nk + 1) / 2) + 5.0 * d.nk : 8.0 * d.ldb * d.ldb;
     const double bytes_sweeps = 88.0 * frozen_free_rows + 64.0 * (double)(d.oq - 6) * (6.0 * d.nb + 2.0 * d.npb) + 288.0 * (double)d.nb * (d.oq - 6);
     const double bytes_iter = bytes_sweeps + 8.0 * (double)d.nj * blk_doubles;
-    PolishWs pw;
-    pw.cand = (Cand*)w.polish;
-    pw.V = w.polish + PL_NC * 14;
-    pw.Sg = pw.V + (size_t)(PL_NC + 1) * d.nj * d.nk;
-    pw.ncand = (int*)(pw.Sg + PL_NC * PL_NC);
-    pw.Lbig = pw.Sg + PL_NC * PL_NC + 8;
+    const PolishWs pw = polish_carve(w.polish, d.nj);
     row_pass<PASS_INIT>(c, io);
     __threadfence_block();
     __syncthreads();
@@ -3180,6 +3179,25 @@ __device__ void restore_dummy(const DevSession& s, int mission, int first, int n
     }
 }
 
+// What depends on the mission's segment times alone, once per launch and ahead of its first batch QP: segsc, Lk, Dk, Ek (mission_constants)
+// and the polish's tables of K0 (qp_polish.inc).  carve() places them by nbmax, so every batch of the mission -- a narrower last one, a
+// second attempt from qp_finish_schedule -- finds them where they were written.  Out of line: nothing of it is live in the batch loop.
+__device__ __noinline__ void mission_tables(const DevSession* Sg, double* ws_base, size_t ws_stride, int mission, int nbmax) {
+    const DevSession& S = *Sg;
+    ws_base = uni(ws_base), mission = uni(mission), nbmax = uni(nbmax);
+    if (S.status[mission] != 0) return;
+    const int N = S.N, M = __builtin_amdgcn_readfirstlane(S.Mk[mission]);
+    const QpDims d = make_dims(N, M, 0, min(nbmax, N));
+    QpWs w = carve(ws_base + (size_t)mission * ws_stride, d, nbmax);
+    mission_constants(d, S.T + (size_t)mission * (S.M + 1), w);
+    __threadfence_block();
+    __syncthreads();
+    extern __shared__ __attribute__((aligned(16))) double lds_raw[];
+    k0_mission_tables(d.nj, w, polish_carve(w.polish, d.nj), lds_raw + 32);
+    __threadfence_block();
+    __syncthreads();
+}
+
 // The REST of a mission's schedule from batch (it0, l0) on, whose first attempt on the reduced row set failed (see qp_batch_kernel): that batch
 // again with every row, then the remaining batches and passes.  Sg: the kernel's copy of the session struct in LDS (the body was written for a
 // struct that lives in registers: it gets a private copy).
@@ -3237,9 +3255,10 @@ __global__ __launch_bounds__(QP_THREADS, QP_WAVES_PER_EU) void qp_batch_kernel(D
     // qp_finish_schedule, a stand-alone copy of the body, after the loops.  Measured, 2000 missions resident (profiles/r05_ab_reduced_rows.txt):
     // this 133.8 k agent-trajectories/s; a second attempt called from INSIDE the loop 127.7 .. 129.6 k (state kept across the call site,
     // whichever way the session struct travels), a loop of two attempts around the inlined body ~123 k, a "redo" trip through the batch loop 87 k.
-    __shared__ DevSession S_lds;  // (for qp_finish_schedule only)
+    __shared__ DevSession S_lds;  // (for mission_tables and qp_finish_schedule)
     if (threadIdx.x == 0) S_lds = S;
     __syncthreads();
+    mission_tables(&S_lds, ws_base, ws_stride, mission, nbmax);
     int stop_it = -1, stop_l = 0;
     for (int it = 0; it < passes && stop_it < 0; ++it)
         for (int l = 0; l < biter; ++l) {
@@ -3296,6 +3315,7 @@ static size_t qp_lds_bytes(int bs, int M) {
     const int nkw = std::min(nk, 36);
     size_t lds = sizeof(double) * (2 * (size_t)((nk + 15) & ~15) + QP_THREADS + 32) + 16;
     lds = std::max(lds, sizeof(double) * (size_t)(std::max(polish_lds_doubles(nk), polish_lds_doubles(nkw)) + 18 * (M - 1) + 32) + 16);
+    lds = std::max(lds, sizeof(double) * (size_t)(54 * (M - 1) + 32) + 16);  // k0_mission_tables: the factor in double and in dd
     lds = std::max(lds, sizeof(double) * (16 + (size_t)QP_STAGE_BUFS * 2 * (nkw * KL_LD + KL_I) + (size_t)(M - 1) * nkw + 2 + 6 * KS_VLEN + 2 * 64 + 64));  // solve_staged
     // chain areas + assembly progress counters (+ the assembling waves' LDS scratch in the 512-thread build)
     // (256-thread build: the two companion waves' images of the just-in-time assembly)

@@ -2,10 +2,12 @@
 //
 // Same mathematics as the CPU checker's polish, re-implemented for one workgroup (DESIGN.md "Polish"):
 //   candidates C  = rows with dominant multiplier or slack < 1e-6 at the interior-point iterate
-//   K0            = reduced Hessian F'(2Q)F (block tridiagonal, no barrier terms), factorised once
-//   V             = K0^{-1} [g, J_C']      K0 decouples per (agent, dim): one thread per non-zero 3x3-block chain
-//   dual QP       min 1/2 z'Sz - d'z, z >= 0 with S = J_C V, d = -J_C v0 - slack_C   -> Lawson-Hanson in wave 0
-//   x_new         = x - F (v0 + V z), refined against the actual residuals of the active rows
+//   K0            = reduced Hessian F'(2Q)F (block tridiagonal, no barrier terms; the same for every agent and dim), factorised and
+//                   inverted once per MISSION (k0_mission_tables): it depends on the segment times alone
+//   v0            = K0^{-1} g              one thread per (agent, dim) 3x3-block chain, solved with the mission's factor (only d needs it)
+//   dual QP       min 1/2 z'Sz - d'z, z >= 0 with S = J_C K0^{-1} J_C', d = -J_C v0 - slack_C   -> Lawson-Hanson in wave 0
+//                   (S from the 3x3 blocks of the mission's table G = K0^{-1}: a row touches one knot; no column of K0^{-1} J_C' is formed)
+//   x_new         = x - F K0^{-1} (g + J_P' z): the sum first, then ONE product with G; refined against the actual residuals of the active rows
 // The result is taken only if it satisfies the KKT conditions of the full QP (every row feasible to 1e-9, all
 // multipliers >= 0); otherwise the interior-point answer stands.  It removes the O(sqrt(mu)) bias of the
 // interior-point answer in the weakly curved directions (reduced-Hessian condition number ~1e9).
@@ -22,11 +24,28 @@ struct Cand {
 
 struct PolishWs {
     Cand* cand;    // [PL_NC]
-    double* V;     // [PL_NC + 1][nred]   column 0 = v0
+    double* v0;    // [3][nred]  the gradient column K0^-1 F'(2Qx); then the gradient F'(2Qx) itself and the primal step's g + J_P' z
     double* Sg;    // [PL_NC][PL_NC]
     int* ncand;    // [4] counter, accepted flag, ...
     double* Lbig;  // [PL_PBIG (PL_PBIG + 1) / 2] packed factor of the second, large-capacity attempt (global memory)
+    double* ptab;  // [6 PL_PBIG][4] primal step: the active rows listed per (agent, dim) -- knot and position in P, sgn n_k t[0..2]
+    // the mission's (k0_mission_tables): K0 depends on the segment times alone
+    double* k0f;   // [nj][18] factor of K0 in double (k0_factor_step), then two ints: the double / the dd factor met a pivot that is not positive
+    double* G;     // lower block triangle of K0^-1 (ipm::k0g_block)
 };
+// (the order follows polish_ws_doubles: what moves with the batch's nk comes last)
+__device__ __forceinline__ PolishWs polish_carve(double* p, int nj) {
+    PolishWs pw;
+    pw.k0f = p, p += 18 * (size_t)nj + 2;
+    pw.G = p, p += k0g_doubles(nj);
+    pw.cand = (Cand*)p, p += PL_NC * 14;
+    pw.Sg = p, p += polish_s_doubles(nj);
+    pw.ncand = (int*)p, p += 8;
+    pw.Lbig = p, p += lhp_size(PL_PBIG);
+    pw.ptab = p, p += 4 * 6 * PL_PBIG;
+    pw.v0 = p;
+    return pw;
+}
 
 #define WSYNC()                                             \
     do {                                                    \
@@ -75,27 +94,25 @@ __device__ __forceinline__ void emit_cand(const QpDims& d, const QpWs& w, const 
 }
 
 #else  // part 2: algorithms (needs row_pass, wave_factor, apply_F, apply_FT)
-// g_c . vec  for a reduced vector vec[(knot-1)*nk + (agent*3+k)*3 + e]
-// colmeta: which (agent, dim) subsystems of the column are not identically zero -- agents a | (b + 1) << 8, dims << 16 (cand_meta) --, or
-// -1 for a dense column (the gradient).  The structurally zero parts of a candidate column are NOT stored (never written, stale).
+// which (agent, dim) subsystems of K0 a candidate row lives in: agents a | (b + 1) << 8, dims << 16
 __device__ __forceinline__ int cand_meta(const Cand& c) {
     return c.a | ((c.b + 1) << 8) | ((c.n[0] != 0.0) << 16) | ((c.n[1] != 0.0) << 17) | ((c.n[2] != 0.0) << 18);
 }
-__device__ __forceinline__ bool meta_has(int meta, int agent, int k) {
-    return meta < 0 || ((((meta >> 16) >> k) & 1) && (agent == (meta & 255) || agent == ((meta >> 8) & 255) - 1));
+// sign of the row's coefficient on (agent, dim k): +1 the row's own agent, -1 the other agent of a pair row, 0 not in the row
+__device__ __forceinline__ int meta_sign(int meta, int agent, int k) {
+    if (!(((meta >> 16) >> k) & 1)) return 0;
+    return agent == (meta & 255) ? 1 : (agent == ((meta >> 8) & 255) - 1 ? -1 : 0);
 }
-__device__ __forceinline__ double cand_dot(const Cand& c, const double* vec, int nk, int colmeta = -1) {
+// g_c . vec  for a reduced vector vec[(knot-1)*nk + (agent*3+k)*3 + e]
+__device__ __forceinline__ double cand_dot(const Cand& c, const double* vec, int nk) {
     const double* blk = vec + (size_t)(c.knot - 1) * nk;
     double s = 0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         if (c.n[k] == 0.0) continue;
-        double ta = 0;
-        if (meta_has(colmeta, c.a, k)) {
-            const double* pa = blk + (c.a * 3 + k) * 3;
-            ta = c.t[0] * pa[0] + c.t[1] * pa[1] + c.t[2] * pa[2];
-        }
-        if (c.b >= 0 && meta_has(colmeta, c.b, k)) {
+        const double* pa = blk + (c.a * 3 + k) * 3;
+        double ta = c.t[0] * pa[0] + c.t[1] * pa[1] + c.t[2] * pa[2];
+        if (c.b >= 0) {
             const double* pb = blk + (c.b * 3 + k) * 3;
             ta -= c.t[0] * pb[0] + c.t[1] * pb[1] + c.t[2] * pb[2];
         }
@@ -105,26 +122,48 @@ __device__ __forceinline__ double cand_dot(const Cand& c, const double* vec, int
 }
 
 // K0 = F'(2Q)F does not couple agents or dimensions: for every (agent, dim) it is the SAME block-tridiagonal matrix
-// with 3x3 blocks  D_j = Dk[j]  and  T_{j+1,j} = Ek[j]'  (assemble_blocks without the barrier terms).  Its factor is
-// nj 3x3 Cholesky blocks (thread 0, a few hundred flops), and V = K0^{-1} R splits into independent little solves:
-// one thread per (column, agent, dim) subsystem that is not identically zero.
-//   f3[jj*18 + 0..8]  = L_jj (lower, row-major),  f3[jj*18 + 9..17] = B_jj = T_{jj+1,jj} L_jj^{-T}
-__device__ void k0_factor3(const QpDims& d, const QpWs& w, double* f3, int* flag) {
-    // the inputs (D_j, E_j of every knot) are fetched by all threads into the very slots the factor will occupy: the factorisation is one
-    // thread's chain of nj steps, and with its loads from global memory every step was a trip of its own while the workgroup waited
-    for (int it = threadIdx.x; it < 18 * d.nj; it += QP_THREADS) {
+// with 3x3 blocks  D_j = Dk[j]  and  T_{j+1,j} = Ek[j]'  (assemble_blocks without the barrier terms), and Dk, Ek come from the mission's
+// segment times alone.  So it is factorised and inverted ONCE per mission, here, and not in every polish:
+//   fd[jj*18 + 0..8]  = L_jj (lower, row-major),  fd[jj*18 + 9..17] = B_jj = T_{jj+1,jj} L_jj^{-T}     (k0_factor_step in dd, one thread's chain)
+//   G = K0^-1, lower block triangle, one thread per unit column (k0_inverse_column), then symmetrised
+// A candidate row touches one knot with three coefficients t per (agent, dim) it involves, so every product of K0^-1 with candidate rows
+// -- S = J K0^-1 J', the primal step K0^-1 J_P' z -- is a contraction of t's with 3x3 blocks of G, and the gradient column K0^-1 g is a
+// product of the table with g + J_P' z: no column of K0^-1 J' is ever formed.  The one solve left is the gradient column v0 = K0^-1 g (for
+// d = -J v0 - slack), with the factor in double that is kept beside the table (k0f).
+// (The primal step multiplies the table with the SUM g + J_P' z, which is nearly zero at the interior-point iterate, never with its two
+// parts one after the other: a product with an explicit inverse of condition number 1e10 is only good to eps |G| |g| ~ 1e-6 m, and the
+// two large parts do not share that error.  Measured: v0 from the solve or from the table and the rows' part from the table, added up
+// afterwards, left control points 3e-6 m off the certified optimum on some of the 50 maps, where 2e-6 is the test's tolerance.)
+// lds: 54 nj doubles (both factors).  pw.Sg holds the table's low halves between the two passes (no batch QP is running yet).
+__device__ void k0_mission_tables(int nj, const QpWs& w, const PolishWs& pw, double* lds) {
+    double* f3 = lds;               // the factor in double, as the polish's k0_solve3 wants it
+    dd* fd = (dd*)(lds + 18 * nj);  // the factor in dd, for the table
+    for (int it = threadIdx.x; it < 18 * nj; it += QP_THREADS) {
         const int jj = it / 18, e = it % 18, j = jj + 1;
-        f3[it] = e < 9 ? w.Dk[9 * j + e] : (jj + 1 < d.nj ? w.Ek[9 * j + (e - 9)] : 0.0);
+        const double v = e < 9 ? w.Dk[9 * j + e] : (jj + 1 < nj ? w.Ek[9 * j + (e - 9)] : 0.0);
+        f3[it] = v, fd[it] = dd(v);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         int ok = 1;
         double Bp[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int jj = 0; jj < d.nj; ++jj)
+        for (int jj = 0; jj < nj; ++jj)
             if (!k0_factor_step(f3 + 18 * jj, Bp, jj == 0)) ok = 0;
-        *flag = !ok;
+        *(int*)(pw.k0f + 18 * (size_t)nj) = !ok;
+    }
+    if (threadIdx.x == 64) {  // (a wave of its own: the two chains run side by side)
+        int ok = 1;
+        dd Bd[9];
+        for (int jj = 0; jj < nj; ++jj)
+            if (!k0_factor_step(fd + 18 * jj, Bd, jj == 0)) ok = 0;
+        *((int*)(pw.k0f + 18 * (size_t)nj) + 1) = !ok;  // (the polish looks at both words)
     }
     __syncthreads();
+    for (int it = threadIdx.x; it < 18 * nj; it += QP_THREADS) pw.k0f[it] = f3[it];
+    for (int col = threadIdx.x; col < 3 * nj; col += QP_THREADS) k0_inverse_column((const dd*)fd, nj, col / 3, col % 3, pw.G, pw.Sg);
+    __threadfence_block();
+    __syncthreads();
+    for (int jj = threadIdx.x; jj < nj; jj += QP_THREADS) k0g_symmetrise(pw.G + k0g_block(jj, jj));
 }
 
 // one (column, agent*3+dim) subsystem:  y <- K0^{-1} y,  y_j at col[jj*nk + sub*3 + e]
@@ -132,7 +171,6 @@ __device__ void k0_factor3(const QpDims& d, const QpWs& w, double* f3, int* flag
 // per knot, every one of the 2 nj steps paid a trip to memory (the next knot's load may not pass this knot's store), 70 trips of 3-5 us under
 // load for a few dozen multiply-adds each.  Now the knots travel in BLOCKS of K0_BLK: the next block is requested before the current one is
 // worked on (second register set, first touched after the block), results leave per block -- a dozen trips.  Same arithmetic, same order.
-constexpr int K0_BLK = 6;
 __device__ __forceinline__ void k0_solve3(const double* f3g, int nj, int nk, double* col, int sub) {
     typedef __attribute__((address_space(1))) double gdb;
     const kl_lds* f3 = (const kl_lds*)f3g;  // (the factor is in LDS)
@@ -195,31 +233,73 @@ __device__ __forceinline__ void k0_solve3(const double* f3g, int nj, int nk, dou
     }
 }
 
-// V columns: the gradient column (if with_grad) and the candidate columns [c0, c1)
+// the gradient column v0 = K0^-1 F'(2Qx): one thread per (agent, dim) subsystem, with the mission's factor (in LDS)
 // (a function of its own since round 6: the blocked recurrence wants ~40 registers the polish around it does not have to spare)
-__device__ __noinline__ void col_solve3_fn(int nj_v, int nk_v, int nb_v, double* V_v, const Cand* cand_v, const double* f3_v, int with_grad_v, int c0_v, int c1_v) {
+__device__ __noinline__ void v0_solve3_fn(int nj_v, int nk_v, int nb_v, double* v0_v, const double* f3_v) {
     const int nj = __builtin_amdgcn_readfirstlane(nj_v), nk = __builtin_amdgcn_readfirstlane(nk_v), nb = __builtin_amdgcn_readfirstlane(nb_v);
-    const int with_grad = __builtin_amdgcn_readfirstlane(with_grad_v), c0 = __builtin_amdgcn_readfirstlane(c0_v), c1 = __builtin_amdgcn_readfirstlane(c1_v);
-    double* V = uni(V_v);
-    const Cand* cand = uni(cand_v);
+    double* v0 = uni(v0_v);
     const double* f3 = uni(f3_v);
-    const int nred = nj * nk, ng = with_grad ? nb * 3 : 0;
-    for (int it = threadIdx.x; it < ng + (c1 - c0) * 6; it += QP_THREADS) {
-        if (it < ng) {
-            k0_solve3(f3, nj, nk, V, it);
-            continue;
+    for (int it = threadIdx.x; it < nb * 3; it += QP_THREADS) k0_solve3(f3, nj, nk, v0, it);
+}
+
+// out = -K0^-1 u from the table, u dense: a thread owns the three values of one (knot jj, agent, dim) and adds G[jj][kb] u_kb over all knots
+// kb -- independent loads, PB blocks per trip, no recurrence.  (A function of its own: ~100 registers the polish does not have to spare.)
+__device__ __noinline__ void table_product_fn(int nj_v, int nk_v, int nb_v, const double* G_v, const double* u_v, double* out_v) {
+    typedef __attribute__((address_space(1))) const double gcd;
+    const int nj = __builtin_amdgcn_readfirstlane(nj_v), nk = __builtin_amdgcn_readfirstlane(nk_v), nsub = 3 * __builtin_amdgcn_readfirstlane(nb_v);
+    gcd* G = QGC(uni(G_v));
+    gcd* uv = QGC(uni(u_v));
+    double* out = uni(out_v);
+    constexpr int PB = 4;
+    for (int it = threadIdx.x; it < nj * nsub; it += QP_THREADS) {
+        const int jj = it / nsub, sub = it % nsub;
+        double acc[3] = {0, 0, 0};
+        for (int k0 = 0; k0 < nj; k0 += PB) {
+            double g[PB][9], x[PB][3];
+#pragma unroll
+            for (int u = 0; u < PB; ++u) {
+                const int kb = k0 + u < nj ? k0 + u : nj - 1;
+                gcd* blk = G + (jj >= kb ? k0g_block(jj, kb) : k0g_block(kb, jj));
+#pragma unroll
+                for (int e = 0; e < 9; ++e) g[u][e] = blk[e];
+#pragma unroll
+                for (int e = 0; e < 3; ++e) x[u][e] = uv[(size_t)kb * nk + sub * 3 + e];
+            }
+#pragma unroll
+            for (int u = 0; u < PB; ++u) {
+                if (k0 + u >= nj) continue;
+                if (jj >= k0 + u) {  // the stored block is G[jj][kb]
+                    acc[0] += g[u][0] * x[u][0] + g[u][1] * x[u][1] + g[u][2] * x[u][2];
+                    acc[1] += g[u][3] * x[u][0] + g[u][4] * x[u][1] + g[u][5] * x[u][2];
+                    acc[2] += g[u][6] * x[u][0] + g[u][7] * x[u][1] + g[u][8] * x[u][2];
+                } else {  // G[jj][kb] = G[kb][jj]'
+                    acc[0] += g[u][0] * x[u][0] + g[u][3] * x[u][1] + g[u][6] * x[u][2];
+                    acc[1] += g[u][1] * x[u][0] + g[u][4] * x[u][1] + g[u][7] * x[u][2];
+                    acc[2] += g[u][2] * x[u][0] + g[u][5] * x[u][1] + g[u][8] * x[u][2];
+                }
+            }
         }
-        const int ci = c0 + (it - ng) / 6, side = ((it - ng) % 6) / 3, k = (it - ng) % 3;
-        const Cand& cd = cand[ci];
-        const int ag = side == 0 ? cd.a : cd.b;
-        if (ag < 0 || cd.n[k] == 0.0) continue;  // that part of the column is identically zero
-        k0_solve3(f3, nj, nk, V + (size_t)(1 + ci) * nred, ag * 3 + k);
+        const size_t i = (size_t)jj * nk + sub * 3;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) out[i + e] = -acc[e];
     }
 }
-__device__ __forceinline__ void col_solve3(const QpDims& d, const PolishWs& pw, const double* f3, bool with_grad, int c0, int c1) {
-    col_solve3_fn(d.nj, d.nk, d.nb, pw.V, pw.cand, f3, with_grad ? 1 : 0, c0, c1);
-    __threadfence_block();
-    __syncthreads();
+
+// S_ab = J_a K0^-1 J_b' of two candidate rows from the table: the bilinear form t_a' G[knot_a][knot_b] t_b is the same for every
+// (agent, dim) the rows share, so it is formed once and multiplied by  sum_k n_a[k] n_b[k]  and by the agents' signs: + for a/a and b/b, - for
+// a/b.  ma, mb: the rows' cand_meta.  Rows that share no agent, or one agent along different axes, give exactly 0 and load nothing.
+__device__ __forceinline__ double s_from_table(const Cand* cand, const double* G, int ci, int cj, int ma, int mb) {
+    const int aa = ma & 255, ab = ((ma >> 8) & 255) - 1, ba = mb & 255, bb = ((mb >> 8) & 255) - 1;
+    const int sg = (aa == ba) - (bb >= 0 && aa == bb) - (ab >= 0 && ab == ba) + (ab >= 0 && ab == bb);
+    bool share = aa == ba || (bb >= 0 && aa == bb) || (ab >= 0 && (ab == ba || ab == bb));
+    // ... nor rows of one agent along different axes (two box faces)
+    if (share && ab < 0 && bb < 0) share = ((ma & mb) >> 16) != 0;
+    if (!share || sg == 0) return 0.0;
+    const Cand& ca = cand[ci];
+    const Cand& cb = cand[cj];
+    const bool a_first = ca.knot >= cb.knot;
+    const double* blk = G + k0g_block((a_first ? ca.knot : cb.knot) - 1, (a_first ? cb.knot : ca.knot) - 1);
+    return (double)sg * (ca.n[0] * cb.n[0] + ca.n[1] * cb.n[1] + ca.n[2] * cb.n[2]) * k0g_bilinear(blk, a_first, ca.t, cb.t);
 }
 
 // v_readlane of a double; lane: wave-uniform
@@ -450,7 +530,7 @@ __device__ __forceinline__ int polish_qp(RowCtx& c, PassIO& io, const PolishWs& 
     const bool geometric = mode == 1, big = mode == 2;
     const QpDims& d = c.d;
     const QpWs& w = c.w;
-    const int tid = threadIdx.x, NK = d.nk, nred = d.nj * NK;
+    const int tid = threadIdx.x, NK = d.nk;
     double* ctrl = const_cast<double*>(c.ctrl);
     // LDS carve
     const int pmax = big ? PL_PBIG : polish_pmax(NK);    // rows simultaneously active in the dual solve
@@ -497,9 +577,12 @@ __device__ __forceinline__ int polish_qp(RowCtx& c, PassIO& io, const PolishWs& 
     __syncthreads();
     if (pw.ncand[0] > PL_NC) return 1;
 
-    // ---- K0 = reduced Hessian without barrier terms: blockdiag(D_j) + E couplings, one 3x3-block chain for all
-    k0_factor3(d, w, f3, flag);
-    if (*flag) return 2;
+    // ---- K0 = reduced Hessian without barrier terms: blockdiag(D_j) + E couplings, one 3x3-block chain for all: the mission's table
+    {
+        const int* k0bad = (const int*)(pw.k0f + 18 * (size_t)d.nj);  // the double factor's flag, the dd factor's
+        if (k0bad[0] | k0bad[1]) return 2;
+    }
+    for (int it = tid; it < 18 * d.nj; it += QP_THREADS) f3[it] = pw.k0f[it];
 
     // column 0 = K0^{-1} F'(2Qx)
     for (int it0 = tid; it0 < d.nb * 3 * d.oq; it0 += 4 * QP_THREADS) {  // (four entries per thread and round, loads ahead of the stores)
@@ -527,19 +610,29 @@ __device__ __forceinline__ int polish_qp(RowCtx& c, PassIO& io, const PolishWs& 
     }
     __threadfence_block();
     __syncthreads();
-    apply_FT(d, w, w.cvec, pw.V, 1.0);
+    double* gred = pw.v0 + (size_t)d.nj * NK;   // F'(2Qx), kept for the primal step
+    double* usum = gred + (size_t)d.nj * NK;    // g + J_P' z of a refinement round
+    apply_FT(d, w, w.cvec, gred, 1.0);
+    __threadfence_block();
+    __syncthreads();
+    for (int i = tid; i < d.nj * NK; i += QP_THREADS) pw.v0[i] = gred[i];
+    __threadfence_block();
+    __syncthreads();
+    v0_solve3_fn(d.nj, d.nk, d.nb, pw.v0, f3);
     __threadfence_block();
     __syncthreads();
 
     PPROF(0);
     bool accepted = false;
-    int n_done = -1, nP = 0;  // -1: column 0 (the gradient) is still to be solved, together with the first candidates
+    int n_done = 0, nP = 0;
     for (int outer = 0; outer < 8 && !accepted; ++outer) {
         const int n = pw.ncand[0];
         if (n > PL_NC) return 1;
-        const int n_prev = n_done < 0 ? 0 : n_done;  // candidates of the previous round
-        // ---- new columns: J_c' then K0^{-1}
-        const int first_new = n_done < 0 ? 0 : n_done;
+        const int n_prev = n_done;  // candidates of the previous round
+#ifndef QP_PROFILE
+        if (outer > 0 && tid == 0) c.scal[SC_PROF0 + 4] += 1;  // diagnostic: dual solves resumed on a grown candidate set (S extended)
+#endif
+        const int first_new = n_done;
         // The sweeps append candidates with an atomic counter, i.e. in the order the hardware happens to schedule the threads; the
         // dual solve breaks ties by position and rounds in the order it meets the rows, so two runs of the same QP could end 1e-8 m
         // apart (both KKT-certified).  Put the new candidates into a defined order -- ascending row slot, which is unique -- so that
@@ -559,57 +652,21 @@ __device__ __forceinline__ int polish_qp(RowCtx& c, PassIO& io, const PolishWs& 
             __threadfence_block();
             __syncthreads();
         }
-        // which (agent, dim) subsystems a candidate's column lives in, for all candidates (inP is idle until the dual solve); only those
-        // parts of a column are stored -- zeroed here, filled below, solved by col_solve3 -- and every reader skips the rest
+        // which (agent, dim) subsystems a candidate lives in, for all candidates (inP is idle until the dual solve)
         for (int ci = tid; ci < n; ci += QP_THREADS) inP[ci] = cand_meta(pw.cand[ci]);
-        __syncthreads();
-        for (int it = tid; it < (n - first_new) * 6 * d.nj; it += QP_THREADS) {
-            const int ci = first_new + it / (6 * d.nj), rem = it % (6 * d.nj), sk = rem / d.nj, jj = rem % d.nj, side = sk / 3, k = sk % 3;
-            const int meta = inP[ci], ag = side == 0 ? (meta & 255) : ((meta >> 8) & 255) - 1;
-            if (ag < 0 || !(((meta >> 16) >> k) & 1)) continue;
-            double* v3 = pw.V + (size_t)(1 + ci) * nred + (size_t)jj * NK + (ag * 3 + k) * 3;
-            v3[0] = 0.0, v3[1] = 0.0, v3[2] = 0.0;
-        }
-        __threadfence_block();
-        __syncthreads();
-        for (int it = tid; it < (n - first_new) * 18; it += QP_THREADS) {
-            const int ci = first_new + it / 18, e18 = it % 18, side = e18 / 9, k = (e18 / 3) % 3, e = e18 % 3;
-            const Cand& cd = pw.cand[ci];
-            const int ag = side == 0 ? cd.a : cd.b;
-            if (ag < 0 || cd.n[k] == 0.0) continue;
-            const double sgn = side == 0 ? 1.0 : -1.0;
-            pw.V[(size_t)(1 + ci) * nred + (size_t)(cd.knot - 1) * NK + (ag * 3 + k) * 3 + e] = sgn * cd.n[k] * cd.t[e];
-        }
-        __threadfence_block();
-        __syncthreads();
-        if (n_done < 0)
-            col_solve3(d, pw, f3, true, 0, n);  // gradient column + all first-round candidates in one pass
-        else if (n > n_done)
-            col_solve3(d, pw, f3, false, n_done, n);
         n_done = n;
-        __threadfence_block();
         __syncthreads();
-        // ---- S = J V (symmetrised), d = -J v0 - slack
+        // ---- S = J K0^-1 J' from the mission's table (symmetric by construction: one value per pair), d = -J v0 - slack
         // (K0 couples neither agents nor dimensions: S_ij = 0 exactly for rows that share no batch agent, or one agent along different
         // axes -- most pairs of box rows; rounds > 0 only compute what is new)
         for (int it = tid; it < n * n; it += QP_THREADS) {
             const int ci = it / n, cj = it % n;
             if (cj > ci || ci < first_new) continue;
-            const int ma = inP[ci], mb = inP[cj];
-            const int aa = ma & 255, ab = ((ma >> 8) & 255) - 1, ba = mb & 255, bb = ((mb >> 8) & 255) - 1;
-            bool share = aa == ba || (bb >= 0 && aa == bb) || (ab >= 0 && (ab == ba || ab == bb));
-            // ... nor rows of one agent along different axes (two box faces)
-            if (share && ab < 0 && bb < 0) share = ((ma & mb) >> 16) != 0;
-            double sv = 0.0;
-            if (share) {
-                const Cand& ca = pw.cand[ci];
-                const Cand& cb = pw.cand[cj];
-                sv = 0.5 * (cand_dot(ca, pw.V + (size_t)(1 + cj) * nred, NK, mb) + cand_dot(cb, pw.V + (size_t)(1 + ci) * nred, NK, ma));
-            }
+            const double sv = s_from_table(pw.cand, pw.G, ci, cj, inP[ci], inP[cj]);
             pw.Sg[(size_t)ci * PL_NC + cj] = sv;
             pw.Sg[(size_t)cj * PL_NC + ci] = sv;
         }
-        for (int ci = tid; ci < n; ci += QP_THREADS) dv[ci] = -cand_dot(pw.cand[ci], pw.V, NK) - pw.cand[ci].slack;
+        for (int ci = tid; ci < n; ci += QP_THREADS) dv[ci] = -cand_dot(pw.cand[ci], pw.v0, NK) - pw.cand[ci].slack;
         // warm start of the dual solve: first round the rows the interior-point iterate marks as active (strength = z/s); a later round
         // (rows outside the candidate set came out violated and joined it) starts from the active set the previous round ended with --
         // zc still holds it (multiplier > 0) -- instead of from nothing: without it every such round repeated the whole build-up, one gradient pass
@@ -647,54 +704,62 @@ __device__ __forceinline__ int polish_qp(RowCtx& c, PassIO& io, const PolishWs& 
         PPROF(2);
         if (nP < 0) return 3;
         // ---- primal step, refinement against the actual residual of the active rows, verification
+        // The active rows are listed per (agent, dim) subsystem of K0 once per dual solve -- the refinement rounds below change z, not the
+        // active set -- (tv, banned, inP, str are idle outside the dual solve): pmeta[b] the row's agents and axes, off[sub] where a
+        // subsystem's entries start in ptab, in the order of P -- an entry's place is counted, not claimed, so the sums are formed in a
+        // fixed order.  An entry: knot * 1024 + position in P, then sgn n_k t[0..2]; the multiplier joins it per round.
+        int* pmeta = inP;        // [nP]   (the dual solve is over: its membership flags are not needed any more)
+        int* off = banned;       // [3 nb + 1]
+        const int nsub = 3 * d.nb;
+        for (int b = tid; b < nP; b += QP_THREADS) pmeta[b] = cand_meta(pw.cand[P[b]]);
+        __syncthreads();
+        for (int sub = tid; sub < nsub; sub += QP_THREADS) {
+            int cnt = 0;
+            for (int b = 0; b < nP; ++b) cnt += meta_sign(pmeta[b], sub / 3, sub % 3) != 0;
+            ((int*)str)[sub] = cnt;
+        }
+        __syncthreads();
+        for (int sub = tid; sub <= nsub; sub += QP_THREADS) {
+            int o = 0;
+            for (int q = 0; q < sub; ++q) o += ((int*)str)[q];
+            off[sub] = o;
+        }
+        __syncthreads();
+        for (int it = tid; it < nP * 6; it += QP_THREADS) {
+            const int b = it / 6, side = (it % 6) / 3, k = it % 3;
+            const int meta = pmeta[b], ag = side == 0 ? (meta & 255) : ((meta >> 8) & 255) - 1;
+            if (ag < 0 || !(((meta >> 16) >> k) & 1)) continue;
+            int rank = 0;
+            for (int q = 0; q < b; ++q) rank += meta_sign(pmeta[q], ag, k) != 0;
+            const Cand& cd = pw.cand[P[b]];
+            const double sn = side == 0 ? cd.n[k] : -cd.n[k];
+            double* en = pw.ptab + 4 * (size_t)(off[ag * 3 + k] + rank);
+            en[0] = (double)((cd.knot - 1) * 1024 + b), en[1] = sn * cd.t[0], en[2] = sn * cd.t[1], en[3] = sn * cd.t[2];
+        }
+        __threadfence_block();
+        __syncthreads();
         for (int round = 0; round < 4; ++round) {
-            // x-space step -v0 - sum_P z_b v_b: the active rows' multipliers and column offsets are tabulated once (tv: doubles, banned:
-            // ints -- both idle outside the dual solve), so that the inner loop is eight independent global loads per round instead of
-            // four behind two dependent LDS lookups each
-            int* pcol = banned;
-            int* pmeta = inP;  // (the dual solve is over: its membership flags are not needed any more)
-            for (int b = tid; b < nP; b += QP_THREADS) tv[b] = zc[P[b]], pcol[b] = 1 + P[b], pmeta[b] = cand_meta(pw.cand[P[b]]);
+            // x-space step -K0^-1 (g + J_P' z) from the table
+            for (int b = tid; b < nP; b += QP_THREADS) tv[b] = zc[P[b]];
             __syncthreads();
-            // (round 6: POL_IPT entries per thread at a time -- the loop is a chain of trips to memory, eight loads per trip and entry: with one
-            // entry at a time a workgroup made ~50 trips per step, 2-4 us each under load; the sums of an entry are formed exactly as before)
-            constexpr int POL_IPT = 3;
-            for (int i0 = tid; i0 < nred; i0 += POL_IPT * QP_THREADS) {
-                int ii[POL_IPT], ag[POL_IPT], kd[POL_IPT];
-                double q[POL_IPT][8];
-#pragma unroll
-                for (int t = 0; t < POL_IPT; ++t) {
-                    const int i = i0 + t * QP_THREADS;
-                    ii[t] = i < nred ? i : -1;
-                    const int sub = ((i < nred ? i : 0) % NK) / 3;  // this entry's (agent, dim): most columns are zero there
-                    ag[t] = sub / 3, kd[t] = sub % 3;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) q[t][u] = 0.0;  // partial sums (independent chains)
+            // g + J_P' z, the sum first (see k0_mission_tables): a thread owns one (knot, agent, dim) and adds its subsystem's entries on that knot
+            for (int it = tid; it < d.nj * nsub; it += QP_THREADS) {
+                const int kb = it / nsub, sub = it % nsub;
+                const size_t i = (size_t)kb * NK + sub * 3;
+                double u0 = gred[i], u1 = gred[i + 1], u2 = gred[i + 2];
+                for (int o = off[sub]; o < off[sub + 1]; ++o) {
+                    const double* en = pw.ptab + 4 * (size_t)o;
+                    const int key = (int)en[0];
+                    if ((key >> 10) == kb) {
+                        const double zb = tv[key & 1023];
+                        u0 += zb * en[1], u1 += zb * en[2], u2 += zb * en[3];
+                    }
                 }
-                int b = 0;
-                for (; b + 8 <= nP; b += 8) {
-                    double vv[POL_IPT][8];
-#pragma unroll
-                    for (int t = 0; t < POL_IPT; ++t)
-#pragma unroll
-                        for (int u = 0; u < 8; ++u)
-                            vv[t][u] = (ii[t] >= 0 && meta_has(pmeta[b + u], ag[t], kd[t])) ? pw.V[(size_t)pcol[b + u] * nred + ii[t]] : 0.0;
-#pragma unroll
-                    for (int t = 0; t < POL_IPT; ++t)
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) q[t][u] += tv[b + u] * vv[t][u];
-                }
-                for (; b < nP; ++b) {
-                    double vv[POL_IPT];
-#pragma unroll
-                    for (int t = 0; t < POL_IPT; ++t) vv[t] = (ii[t] >= 0 && meta_has(pmeta[b], ag[t], kd[t])) ? pw.V[(size_t)pcol[b] * nred + ii[t]] : 0.0;
-#pragma unroll
-                    for (int t = 0; t < POL_IPT; ++t) q[t][0] += meta_has(pmeta[b], ag[t], kd[t]) ? tv[b] * vv[t] : 0.0;
-                }
-#pragma unroll
-                for (int t = 0; t < POL_IPT; ++t)
-                    if (ii[t] >= 0)
-                        w.rhs[ii[t]] = -pw.V[ii[t]] - (((q[t][0] + q[t][1]) + (q[t][2] + q[t][3])) + ((q[t][4] + q[t][5]) + (q[t][6] + q[t][7])));
+                usum[i] = u0, usum[i + 1] = u1, usum[i + 2] = u2;
             }
+            __threadfence_block();
+            __syncthreads();
+            table_product_fn(d.nj, NK, d.nb, pw.G, usum, w.rhs);
             __threadfence_block();
             __syncthreads();
             apply_F(d, w, w.rhs, w.dx);
