@@ -526,7 +526,7 @@ __device__ __forceinline__ bool kl_knot_panels(TF&& t_entry, LF&& t_loaded, bool
 __host__ __device__ constexpr bool kl_fused_path(int nk) { return KL_FUSED_UPDATE && kl_panel_path(nk); }
 
 // the coefficients of the rows a lane forms: cf[t][q] multiplies row kp_x_group(16 t + li) + q of M; coef(row, q) returns T_next,this[row][group + q]
-// (coupling_coef of qp.hip).  Rows of the padding get zeros: they contribute nothing, and the tiles' padding stays what kl_tiles_load sets.
+// (coupling_coef of qp_wave_factor.inc).  Rows of the padding get zeros: they contribute nothing, and the tiles' padding stays what kl_tiles_load sets.
 template <int NK, class F>
 __device__ __forceinline__ void kl_fused_coef(double (&cf)[KlPanels<NK>::NT][3], int lane, F&& coef) {
     const int li = lane & 15;

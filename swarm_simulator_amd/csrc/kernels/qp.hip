@@ -15,14 +15,15 @@
 //     sweep; step into the ping-pong arrays + neighbourhood test + next iteration's weights);
 //   * per-control-point 3x3 accumulators are expanded into the knot blocks (no atomics) by the six waves that would otherwise
 //     idle behind the factorisation chains, block by block just ahead of them (twisted_factor);
-//   * the block-tridiagonal factorisation: nk <= 36 twisted two-wave chains, L D L' with column images broadcast through LDS (36 x 36 blocks: 4-column panels on the FP64 MFMA, knot_lds.inc)
-//     (knot_lds.inc), the explicit inverse factor M = L^-T by a companion wave, MFMA rank-k updates; wider batches an MFMA-tiled path
+//   * the block-tridiagonal factorisation: nk <= 36 twisted two-wave chains, L D L' with column images broadcast through LDS (36 x 36
+//     blocks: 4-column panels on the FP64 MFMA, knot_lds.inc), the explicit inverse factor M = L^-T by a companion wave, MFMA rank-k updates; wider batches an MFMA-tiled path
 //     (LDS-resident for nk <= 72); substitutions as matrix-vector products with the staged M;
 //   * an active-set polish (qp_polish.inc) turns the interior-point answer into the exact optimum, verified by a full
 //     KKT check; from the second Gauss-Seidel pass on it is tried before any interior-point iteration.
 // Batches of a mission are solved strictly in the reference's order (Gauss-Seidel, :140-148); parallelism comes
 // from the 3*nb coupled blocks inside a batch and from the K missions of a session.  The file is compiled twice
-// (512 / 256 threads per workgroup, see the note above planner_workspace_bytes).
+// (512 / 256 threads per workgroup, see the note above planner_workspace_bytes).  Workspace, reductions and
+// the wave-uniform arguments are qp_base.inc, the wave-register path qp_wave_factor.inc / qp_wave_solve.inc, the polish qp_polish_types.inc (its records) / qp_polish.inc: each included once, where it is needed.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -109,7 +110,7 @@
 #ifndef QP_EARLY_TOL
 #define QP_EARLY_TOL 1e-6
 #endif
-// LDS doubles used by polish_qp<36>: 2 blocks + packed factor + vectors + int arrays (see qp_polish.inc)
+// LDS doubles used by polish_qp: 2 blocks + packed factor + vectors + int arrays (see qp_polish.inc)
 #include "lh_layout.h"
 #define PL_NC 256    // polish: candidate rows
 #define PL_PMAX 160  // polish: rows simultaneously active in the dual solve (wide batches; 112 on the wave path, whose
@@ -131,243 +132,12 @@ __host__ __device__ inline int polish_lds_doubles(int nk) {
 namespace {
 using namespace ipm;
 
-#ifdef QP_PROFILE
-#define PROF_DECL long long prof_t0 = wall_clock64(), prof_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define PROF(i)                                \
-    do {                                       \
-        __syncthreads();                       \
-        long long t_ = wall_clock64();         \
-        prof_acc[i] += t_ - prof_t0;           \
-        prof_t0 = t_;                          \
-    } while (0)
-#define PROF_FLUSH(scal)                                                         \
-    do {                                                                         \
-        if (threadIdx.x == 0)                                                    \
-            for (int i_ = 0; i_ < 12; ++i_) scal[SC_PROF0 + i_] += (double)prof_acc[i_]; \
-    } while (0)
-#else
-#define PROF_DECL
-#define PROF(i)
-#define PROF_FLUSH(scal)
-#endif
+#include "qp_base.inc"          // timers, QpDims / QpWs, reductions, wave-uniform arguments, mission constants
+
+#include "qp_polish_types.inc"  // the polish's records, as far as the sweeps emit them
 
 // ------------------------------------------------------------------------------------------------------------
-// dimensions of one batch QP
-// ------------------------------------------------------------------------------------------------------------
-struct QpDims {
-    int N, M, oq;       // agents, segments, 6M
-    int nb, NF, npb;    // batch agents, frozen agents, in-batch pairs
-    int nk, nj, ld;     // block order 9*nb, knots M-1, padded leading dimension
-    int ldb;            // leading dimension of the knot blocks in global memory: nk (wave path) or nk rounded up to 16 (tiled path)
-    int first;          // first agent of the batch (batches are contiguous: qi / batch_size == l)
-    int ncol0;          // rows every control point of a batch agent has: 6 bound rows + (nb - 1) in-batch pair rows
-    int ntile;          // 64-lane tiles of control points: ceil(nb * oq / 64)
-    size_t nslot_max;   // capacity of the row arrays: ntile * 64 * (ncol0 + NF)
-};
-
-__host__ __device__ inline QpDims make_dims(int N, int M, int first, int nb) {
-    QpDims d;
-    d.N = N, d.M = M, d.oq = 6 * M, d.nb = nb, d.NF = N - nb, d.npb = nb * (nb - 1) / 2;
-    d.nk = 9 * nb, d.nj = M - 1, d.ld = d.nk + 1, d.first = first;
-    d.ldb = d.nk <= 36 ? d.nk : ((d.nk + 15) & ~15);
-    d.ncol0 = 6 + nb - 1, d.ntile = (nb * d.oq + 63) / 64;
-    d.nslot_max = (size_t)d.ntile * 64 * (d.ncol0 + d.NF);
-    return d;
-}
-
-// ROW STORAGE ("sliced ELLPACK", slice = one wavefront).  A sweep hands one control point (agent a, segment, i) of a batch agent
-// to a thread; that thread owns ALL rows that touch its control point:
-//     6 bound rows  |  nb - 1 in-batch pair rows  |  cnt(a, segment) frozen-neighbour rows that survived the presolve
-// Control points are numbered wi = 6 * rank(a, segment) + i with the (a, segment) groups ranked by falling row count, 64
-// consecutive wi form a tile (= the lanes of one wavefront), and row `idx` of control point wi lives in slot
-//     tile_base[wi / 64] + idx * 64 + (wi % 64)
-// so every load/store of a sweep is ONE coalesced 512-byte access per wavefront and array, and consecutive rows of a thread
-// are consecutive 512-byte lines: a pure stream.  (The previous layout kept the rows of a group contiguous: a wavefront then
-// touched eleven 48-byte pieces of different cache lines per array and step, and HBM-side traffic was ~2.5x the bytes used.)
-// A pair row is shared by two control points (one of each agent) and is STORED TWICE, once in each one's column: both copies
-// are updated by the same arithmetic on the same inputs, hence stay bit-identical; reductions count the copy of the lower
-// agent only.  Only (s, z) are stored per row -- the corrector term and the step (ds, dz) are recomputed where they are needed
-// (they are functions of s, z and the two direction vectors), which halves the bytes of a sweep; the step sweep writes the
-// new (s, z) into a second pair of arrays (ping-pong) so that a rejected step can be repeated from the old state.
-struct QpWs {
-    double *s, *z, *s2, *z2;        // row state [nslot]: current / next
-    double *rh;                     // [nslot] frozen-neighbour rows: the constant of slack = rh - n . x_a
-    double *cc, *ds;                // [nslot] polish only: candidate marks / slack at the trial point
-    double *cpacc;                  // [12][nb*oq]: S(6) yv(3) gz(3) per control point, ALL its rows (bounds, pairs, frozen); component-major, so
-                                    // that the passes that read three or six of the twelve (rbase, rhs, assembly) fetch only those
-    double *pwgt;                   // [npb*oq] Newton weight of every in-batch pair row (off-diagonal blocks of the knot matrices)
-    double *dx, *dxa, *cvec;        // [nb*3*oq]
-    double *rbase, *rhs;            // [(M-1)*nk]
-    double *Td, *To;                // [(M-1)][nk*nk], [(M-2)][nk*nk]
-    double *Lf;                     // [(M-1)][2][nk*nk]: L_jj and L_{j+1,j}, both stored [k][r] (element (r,k) at k*nk + r)
-    double *boxlo, *boxhi;          // [nb][M][3]
-    double *Lk, *Dk, *Ek;           // [M+1][9]
-    double *segsc;                  // [M] dt^-5 (build_Q_p :349-351)
-    int *flist, *fcnt, *fbase;      // non-redundant frozen neighbours per (batch agent, segment): [nb][M][NF], [nb][M], [nb][M]
-    int *fnear;                     // (round 5) [nb][M] how many of a group's neighbours are NEAR (they come first in its rows; the far ones sit at
-                                    // the back of its flist): the interior-point sweeps only walk the near rows (see QP_FAR_SLACK)
-    int *fperm, *frank;             // [nb][M]: groups ordered by falling row count (fperm[rank] = group, frank[group] = rank)
-    int *tile_base;                 // [ntile + 1] first slot of each tile
-    int *wi_of;                     // [nb*oq] column (wi) of control point (a, j6)
-    float* nrm;                     // [sum cnt][3] signed normal of frozen row (group, idx): the six rows of a group share it
-    double* polish;                 // PolishWs storage
-    double* prof;                   // QP_PROFILE builds: this mission's diagnostic scalars (chain-side timers), else nullptr
-};
-
-__host__ __device__ inline size_t ws_int_count(int N, int M, int nbmax) {
-    QpDims d = make_dims(N, M, 0, nbmax);
-    return (size_t)nbmax * M * N /*flist*/ + 5 * (size_t)nbmax * M /*fcnt fbase fperm frank fnear*/ + d.ntile + 1 + (size_t)nbmax * d.oq /*wi_of*/ +
-           3 * (size_t)nbmax * M * N /*nrm (floats)*/ + 8;
-}
-
-__host__ __device__ inline size_t ws_doubles(int N, int M, int nbmax) {
-    QpDims d = make_dims(N, M, 0, nbmax);
-    size_t n = 7 * d.nslot_max + 12 * (size_t)nbmax * d.oq + (size_t)(d.npb ? d.npb : 1) * d.oq + 3 * (size_t)nbmax * 3 * d.oq +
-               2 * (size_t)d.nj * d.nk + (size_t)d.nj * d.ldb * d.ldb + 2 * (size_t)d.nj * (d.nk < 36 ? d.nk : 36) * (d.nk < 36 ? d.nk : 36) +
-               (size_t)(d.nj > 1 ? d.nj - 1 : 1) * d.ldb * d.ldb + 4 +
-               2 * (size_t)nbmax * M * 3 + 3 * (size_t)(M + 1) * 9 + M + 64 + (ws_int_count(N, M, nbmax) + 1) / 2 + 2 +
-               /* polish: cand, V, S, counters, big factor */ polish_ws_doubles(d.nj, d.nk);
-    return n;
-}
-
-__device__ inline QpWs carve(double* base, const QpDims& d, int nbmax) {
-    QpDims dm = make_dims(d.N, d.M, 0, nbmax);
-    QpWs w;
-    double* p = base;
-    w.s = p, p += dm.nslot_max;
-    w.z = p, p += dm.nslot_max;
-    w.s2 = p, p += dm.nslot_max;
-    w.z2 = p, p += dm.nslot_max;
-    w.rh = p, p += dm.nslot_max;
-    w.cc = p, p += dm.nslot_max;
-    w.ds = p, p += dm.nslot_max;
-    w.cpacc = p, p += 12 * (size_t)nbmax * d.oq;
-    w.pwgt = p, p += (size_t)(dm.npb ? dm.npb : 1) * d.oq;
-    w.dx = p, p += (size_t)nbmax * 3 * d.oq;
-    w.dxa = p, p += (size_t)nbmax * 3 * d.oq;
-    w.cvec = p, p += (size_t)nbmax * 3 * d.oq;
-    w.rbase = p, p += (size_t)dm.nj * dm.nk;
-    w.rhs = p, p += (size_t)dm.nj * dm.nk;
-    p += (4 - ((p - base) & 3)) & 3;  // 32-byte alignment of the blocks (vector loads of the tiled path)
-    w.Td = p, p += (size_t)dm.nj * dm.ldb * dm.ldb;
-    w.To = p, p += (size_t)(dm.nj > 1 ? dm.nj - 1 : 1) * dm.ldb * dm.ldb;
-    w.Lf = p, p += 2 * (size_t)dm.nj * (dm.nk < 36 ? dm.nk : 36) * (dm.nk < 36 ? dm.nk : 36);  // wave path only (a short last batch)
-    w.boxlo = p, p += (size_t)nbmax * d.M * 3;
-    w.boxhi = p, p += (size_t)nbmax * d.M * 3;
-    w.Lk = p, p += (size_t)(d.M + 1) * 9;
-    w.Dk = p, p += (size_t)(d.M + 1) * 9;
-    w.Ek = p, p += (size_t)(d.M + 1) * 9;
-    w.segsc = p, p += d.M;
-    int* ip = (int*)p;
-    w.flist = ip, ip += (size_t)nbmax * d.M * d.N;
-    w.fnear = ip, ip += (size_t)nbmax * d.M;
-    w.fcnt = ip, ip += (size_t)nbmax * d.M;
-    w.fbase = ip, ip += (size_t)nbmax * d.M;
-    w.fperm = ip, ip += (size_t)nbmax * d.M;
-    w.frank = ip, ip += (size_t)nbmax * d.M;
-    w.tile_base = ip, ip += dm.ntile + 1;
-    w.wi_of = ip, ip += (size_t)nbmax * d.oq;
-    w.nrm = (float*)ip;
-    w.polish = p + (ws_int_count(d.N, d.M, nbmax) + 1) / 2 + 2;
-    w.prof = nullptr;
-    return w;
-}
-
-// ---- reductions ------------------------------------------------------------------------------------------------
-// Wave-wide (result in every lane): inside a row of 16 lanes by DPP (quad permutes, half-row and row mirrors: VALU latency), across the
-// four rows through readlane: ~300 cycles, where six butterfly steps of ds_bpermute pairs took ~1000 of dependent LDS round trips -- an
-// interior-point iteration has ten of these reductions, and every Lawson-Hanson step of the polish two or three on its dependent path.
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double red_op(double a, double b, int op) { return op == 0 ? a + b : (op == 1 ? fmax(a, b) : fmin(a, b)); }
-__device__ __forceinline__ double rl(double v, int lane) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-__device__ __forceinline__ double wave_red(double v, int op /*0 sum,1 max,2 min*/) {
-    v = red_op(v, dpp_f64<0xB1>(v), op);   // quad_perm [1,0,3,2]
-    v = red_op(v, dpp_f64<0x4E>(v), op);   // quad_perm [2,3,0,1]
-    v = red_op(v, dpp_f64<0x141>(v), op);  // row_half_mirror
-    v = red_op(v, dpp_f64<0x140>(v), op);  // row_mirror: every lane of a row holds the row's result
-    return red_op(red_op(rl(v, 0), rl(v, 16), op), red_op(rl(v, 32), rl(v, 48), op), op);
-}
-// Block-wide: the wave reduction, then across the waves through `red`.  Two barriers: the one in front of the write would only protect
-// the previous reduction's readers, which the barrier at ITS end has already let go.
-__device__ inline double block_reduce(double v, int op /*0 sum,1 max,2 min*/, double* red) {
-    v = wave_red(v, op);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    double r = red[0];
-    for (int i = 1; i < QP_THREADS / 64; ++i) r = red_op(r, red[i], op);
-    __syncthreads();
-    return r;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// per-mission constants: L_j (continuity map), D_j = L_j'(2Q22)L_j + 2Q11, E_j = 2 Q12 L_{j+1}
-// Aeq_base rows at knot j (rbp_planner.hpp:390-399):  dl^-i nn_i A_T.row(i) c_{j-1} = dr^-i nn_i A_0.row(i) c_j
-// ------------------------------------------------------------------------------------------------------------
-__device__ void mission_constants(const QpDims& d, const double* T, QpWs& w) {
-    const int M = d.M;
-    for (int m = threadIdx.x; m < M; m += QP_THREADS) w.segsc[m] = pow(T[m + 1] - T[m], -5.0);
-    for (int j = threadIdx.x; j <= M; j += QP_THREADS) {
-        double* L = w.Lk + 9 * j;
-        for (int e = 0; e < 9; ++e) L[e] = 0;
-        if (j >= 1 && j < M) {
-            const double r = (T[j] - T[j - 1]) / (T[j + 1] - T[j]);  // dl / dr
-            // c5 = u0 ; c4 = c5 - r (u1 - u0) ; c3 = 2 c4 - c5 + r^2 (u0 - 2 u1 + u2)   (rows: c3, c4, c5)
-            L[0] = (1 + r) * (1 + r), L[1] = -2 * r * (1 + r), L[2] = r * r;
-            L[3] = 1 + r, L[4] = -r, L[5] = 0;
-            L[6] = 1, L[7] = 0, L[8] = 0;
-        }
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j <= M; j += QP_THREADS) {
-        double* D = w.Dk + 9 * j;
-        double* E = w.Ek + 9 * j;
-        for (int e = 0; e < 9; ++e) D[e] = 0, E[e] = 0;
-        if (j >= 1 && j < M) {
-            const double sl = pow(T[j] - T[j - 1], -5.0), sr = pow(T[j + 1] - T[j], -5.0);  // build_Q_p :349-351
-            const double* L = w.Lk + 9 * j;
-            double QL[9];
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) {
-                    double s = 0;
-                    for (int c = 0; c < 3; ++c) s += Qbase[6 * (3 + a) + 3 + c] * sl * L[3 * c + b];
-                    QL[3 * a + b] = s;
-                }
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) {
-                    double s = 0;
-                    for (int c = 0; c < 3; ++c) s += L[3 * c + a] * QL[3 * c + b];
-                    D[3 * a + b] = 2 * (s + Qbase[6 * a + b] * sr);
-                }
-            if (j + 1 < M) {
-                const double* Ln = w.Lk + 9 * (j + 1);
-                for (int a = 0; a < 3; ++a)
-                    for (int b = 0; b < 3; ++b) {
-                        double s = 0;
-                        for (int c = 0; c < 3; ++c) s += Qbase[6 * a + 3 + c] * sr * Ln[3 * c + b];
-                        E[3 * a + b] = 2 * s;  // rows u_j, cols u_{j+1}
-                    }
-            }
-        }
-    }
-    __syncthreads();
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// row sweeps.  Rows of a batch QP (G x <= h form, as in the oracle):
-//   bound   (a,k,side,j6):  +x <= hi   /  -x <= -lo                       rbp_planner.hpp:626-635
-//   frozen  (a,f,j6):       sg * n . x_a <= -rr + sg * n . dummy_f        :645-666   sg = +1 if a < f else -1
-//   pair    (a<b,j6):       n . x_a - n . x_b <= -rr                      :668-679
-// Control points j6 < 3 and j6 >= 6M-3 are pinned by the end-state equalities: their rows are constants and are
-// only checked once (presolve).  Work item = one free control point of one batch agent (all its bound and frozen
-// rows), then one (pair, control point).
+// row sweeps (the rows of a batch QP and the work item of a sweep: see row_pass)
 // ------------------------------------------------------------------------------------------------------------
 enum { PASS_INIT = 0, PASS_BUILD, PASS_AFF, PASS_STEP, PASS_PRESOLVE, PASS_CAND, PASS_VERIFY, PASS_CAND_GEO,
        PASS_UPBUILD /* step of iteration i (old state -> new state arrays) fused with BUILD of iteration i+1 */ };
@@ -377,6 +147,10 @@ constexpr bool pass_in_blocks(int pass) {
     return pass == PASS_BUILD || pass == PASS_AFF || pass == PASS_STEP || pass == PASS_UPBUILD || pass == PASS_CAND || pass == PASS_VERIFY ||
            pass == PASS_CAND_GEO;
 }
+// the passes that read a row's stored (s, z): the sweeps of the interior-point loop and the polish's candidate search on its iterate
+constexpr bool pass_reads_sz(int pass) {
+    return pass == PASS_BUILD || pass == PASS_AFF || pass == PASS_STEP || pass == PASS_UPBUILD || pass == PASS_CAND;
+}
 
 struct PassIO {
     // inputs
@@ -384,10 +158,6 @@ struct PassIO {
     // outputs (block-reduced by the caller)
     double sum0, sum1, sum2, vmax, vmin;
 };
-
-#define QP_POLISH_PART 1
-#include "qp_polish.inc"
-#undef QP_POLISH_PART
 
 // (round 6) what a sweep looks up per control point before it can request anything -- its group, the group's row counts and normal offset,
 // its tile's first slot -- copied ONCE per batch QP into LDS (by rank, i.e. already through fperm): in global memory these were two dependent
@@ -433,7 +203,7 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
 template <int PASS, bool PRE = false>
 __device__ __forceinline__ void row_op(double slack, double ga, double gd, size_t r, const QpWs& w, PassIO& io, double cw, double& wgt,
                                        double& v, double& zo, double s_in = 0.0, double z_in = 0.0) {
-    constexpr bool rd_sz = PASS == PASS_BUILD || PASS == PASS_AFF || PASS == PASS_STEP || PASS == PASS_UPBUILD || PASS == PASS_CAND;
+    constexpr bool rd_sz = pass_reads_sz(PASS);
     double s = 0.0, z = 0.0;
     if (rd_sz) s = PRE ? s_in : QGC(w.s)[r], z = PRE ? z_in : QGC(w.z)[r];
     if (PASS == PASS_INIT) {
@@ -552,7 +322,7 @@ __device__ void row_pass(const RowCtx& c, PassIO& io) {
         const float* nr = w.nrm + (size_t)fb * 3;
         const size_t r0 = base + (size_t)d.ncol0 * 64;
         // (QP_ROW_BLK) the first block of the frozen-row stream is requested here, with everything else the control point starts from
-        constexpr bool rd_sz_b = PASS == PASS_BUILD || PASS == PASS_AFF || PASS == PASS_STEP || PASS == PASS_UPBUILD || PASS == PASS_CAND;
+        constexpr bool rd_sz_b = pass_reads_sz(PASS);
         constexpr int BB = QP_ROW_BLK > 0 ? QP_ROW_BLK : 1;
         double cs[BB], cz[BB], ch[BB];
         float cn[BB][3];
@@ -685,7 +455,7 @@ __device__ void row_pass(const RowCtx& c, PassIO& io) {
         // are requested before the current block is worked on, and first touched -- copied -- after it: one trip per block, overlapped with
         // the block's arithmetic.  Rows past the end re-read the last row (same cache lines) and are not used.  Same rows, same order, same
         // arithmetic per row as the plain loop.
-        constexpr bool rd_sz = PASS == PASS_BUILD || PASS == PASS_AFF || PASS == PASS_STEP || PASS == PASS_UPBUILD || PASS == PASS_CAND;
+        constexpr bool rd_sz = pass_reads_sz(PASS);
         constexpr int B = BB;
         if (cnt > 0) {
             double ns[B], nz[B], nh[B];
@@ -730,7 +500,7 @@ __device__ void row_pass(const RowCtx& c, PassIO& io) {
         // more of them costs registers and instruction cache (unroll 4 measured 8 % slower than 2).  A prefetch ring decouples the two:
         // the loads of row idx + QP_ROW_PF -- (s, z), the row constant, the group normal: nine registers -- are issued while row idx is
         // worked on, the arithmetic is not replicated.
-        constexpr bool rd_sz = PASS == PASS_BUILD || PASS == PASS_AFF || PASS == PASS_STEP || PASS == PASS_UPBUILD || PASS == PASS_CAND;
+        constexpr bool rd_sz = pass_reads_sz(PASS);
         double ps[QP_ROW_PF], pz[QP_ROW_PF], ph[QP_ROW_PF];
         float pn[QP_ROW_PF][3];
 #pragma unroll
@@ -921,6 +691,10 @@ struct AsmArgs {
     double* Td;
     int N, M, nb, first, oq, ldb;
 };
+// (arguments of a non-kernel function arrive in vector registers: see BlkArgs)
+__device__ __forceinline__ AsmArgs uni(const AsmArgs& A) {
+    return AsmArgs{uni(A.cpacc), uni(A.pwgt), uni(A.Lk), uni(A.Dk), uni(A.normals), uni(A.Td), uni(A.N), uni(A.M), uni(A.nb), uni(A.first), uni(A.oq), uni(A.ldb)};
+}
 
 // one work item of the block assembly = (knot j, agent a, agent b, dim k, dim l): six 3x3-accumulator entries in, one 3x3 (e,f)
 // tile of T_j out.  r = ((a * nb + b) * 3 + k) * 3 + l.  Ssum: LDS copy of the per-control-point weight sums [nb*oq][6] or nullptr.
@@ -1074,9 +848,6 @@ __device__ __forceinline__ void assemble_knots_lds(const AsmArgs& A, double* scr
 //                issued right after the PREVIOUS block's tiles, they land while the companion follows that block's factorisation;
 //   fasm_tiles   the 3 x 3 tiles from the LDS inputs into the symmetric LDS image the chain reads (the arithmetic of assemble_knots_lds).
 // Scratch layout as in assemble_knots_lds (image | Sin | Pw | Nr), except that Nr holds the normals as the floats they are.
-__device__ __forceinline__ AsmArgs uni(const AsmArgs& A);  // (arguments of a non-kernel function arrive in vector registers: see BlkArgs)
-template <class T>
-__device__ __forceinline__ T* uni(T* p);
 __device__ __noinline__ void fasm_fetch(AsmArgs Av, double* scratch_v, int jv) {
     typedef __attribute__((address_space(1))) const void gvoid;
     typedef __attribute__((address_space(3))) void lvoid;
@@ -1196,861 +967,8 @@ __device__ void assemble_blocks(const RowCtx& c, double* lds) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// wave-register path (nk <= 36, i.e. batches of up to 4 agents): the whole block-tridiagonal Cholesky and the
-// substitutions run in ONE wavefront with matrix rows held in VGPRs (lane r = row r, NK doubles per block) and
-// v_readlane broadcasts instead of LDS traffic: every step of the dependent chains costs a few issue cycles
-// instead of an LDS round trip, and no workgroup barrier is needed inside a knot.
-// (Round 3: the cross-lane traffic of the factorisation goes through LDS broadcasts instead, see knot_lds.inc; v_readlane is
-// left for the pivots.)  The substitutions stage the knots' M_j through LDS (prefetched by the otherwise idle waves).
-// ------------------------------------------------------------------------------------------------------------
-// TWISTED ("burn at both ends") factorisation: wave 0 eliminates blocks 0 .. mid-1 upwards, wave 1 eliminates blocks
-// nj-1 .. mid+1 downwards, concurrently on two SIMDs; the middle block collects both Schur complements.  It halves the
-// length of the dependent chain (factor and substitutions alike) at no extra arithmetic.
-//   Lf[j] = M_j = L_j^-T (row r contiguous, zeros left of the diagonal), then 1 / d_j   (KF_STRIDE doubles per knot)
-__device__ __forceinline__ int twist_mid(int nj) { return nj / 2; }
-
-// Progress counters of the just-in-time block assembly (LDS ints behind the two chain areas): cnt[i] counts the helper waves that
-// have finished the blocks of chain step i; a chain may load its i-th block when all QP_THREADS/64 - 2 of them have.
-// Wave roles of the wave path's factorisation: 0, 1 = the two chains; 2, 3 = their companions (M = L^-T behind the chain, see
-// wave_factor_follow); the 512-thread build has four more waves, which assemble the knot blocks behind the chains (one wave per block,
-// through the LDS: assemble_knots_lds); the 256-thread build assembles all blocks up front (assemble_blocks_lds).
-#define ASM_WAVE0 4                                                        // first assembling wave
-#define ASM_HELPERS (QP_THREADS / 64 > ASM_WAVE0 ? QP_THREADS / 64 - ASM_WAVE0 : 0)   // assembling waves
-// (round 6) 256-thread build: no waves to spare for the assembly -- but the two COMPANION waves (M = L^-T behind the chains) idle between
-// the end of one block's factorisation and the start of the next (while the chain forms the coupling rows and the rank-36 update): each
-// assembles its chain's NEXT block into an LDS image in that gap, just in time, and the chain reads it from there (the Timg path of the
-// 512-thread build).  The up-front assembly phase -- 11 % of a mission's time under load, most of it spent waiting for its own loads and
-// stores: profiles/r06_ab_qp_levers.txt -- and the round trip of every T_j through global memory disappear.
-#ifndef QP_FOLLOW_ASM
-#define QP_FOLLOW_ASM (ASM_HELPERS == 0)
-#endif
-#define ASMF_READY(cnt, h) ((kl_ldsi*)((cnt) + 76 + (h)))  // images the companion of chain h has finished (monotone over a factorisation)
-__device__ __forceinline__ void wait_blocks(int* cnt, int i) {
-    while (__hip_atomic_load(cnt + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < ASM_HELPERS) __builtin_amdgcn_s_sleep(2);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-template <int NK>
-__device__ __forceinline__ bool chol_rows(double (&a)[NK], double& dinv) {  // right-looking; a[c] = L[r][c] for lanes r >= c
-    bool ok = true;                                                           // dinv: 1 / L[r][r] of this lane's row (tiled path)
-    const int r = threadIdx.x & 63;
-    dinv = 1.0;
-#pragma unroll
-    for (int c = 0; c < NK; ++c) {
-        const double dcc = rl(a[c], c);
-        if (!(dcc > 0)) ok = false;
-        const double inv = fast_rsqrt(dcc);
-        dinv = (r == c) ? inv : dinv;
-        a[c] *= inv;
-#pragma unroll
-        for (int k = c + 1; k < NK; ++k) a[k] -= a[c] * rl(a[c], k);
-    }
-    return ok;
-}
-
-// ---- one chain of the twisted factorisation (round 3: knot_lds.inc, cross-lane traffic through LDS broadcasts) --------------------
-// Per knot j of the chain (the chain's previous knot jp = j - dir):
-//   S_j = T_j - X_j D_jp^-1 X_j'          X_j = T_{j,jp} L_jp^-T  (rows of block j), the rank-NK update on v_mfma_f64_16x16x4_f64
-//   S_j = L_j D_j L_j'                    kl_ldl: column images in LDS; NK = 36: kl_ldl_panels, 4 columns per step on the FP64 MFMA, panel images in LDS
-//   M_j = L_j^-T                          explicit (kl_inverse_rows): the substitutions are matrix-vector products with M_j, and
-//   X_jn = Cpl M_j                        the coupling factor towards the next knot costs three multiply-adds per entry
-// What a knot leaves in global memory for the substitutions is M_j (row r contiguous, entries k < r are zeros) and 1 / d_j: 5.5 KB of
-// triangle + diagonal instead of the two full blocks (L_j, X_j: 20.7 KB) of the round-2 formulation; X never leaves the LDS.
-// The 36 x 36 blocks (kl_fused_path(NK)) do not store X at all: the chain forms S_j in the MFMA tiles straight from M_jp (kl_fused_update), each
-// operand element of X_j from three rows of M_jp and the knot's nine coupling coefficients, and the companion announces M_j before its read-back.
-#define KF_STRIDE(NK) ((NK) * (NK) + KL_I)  // doubles per knot in QpWs::Lf: M_j [NK][NK], then 1 / d_j
-
-// coefficients of row rr of the coupling block between knot j and the next knot of the chain: T_{j+dir,j}[rr][3g + q], g = rr / 3
-// (T_{j+1,j} = blockdiag(E_{knot j+1}'), T_{j-1,j} = T_{j,j-1}'; see assemble_blocks)
-__device__ __forceinline__ void coupling_coef(const QpWs& w, int j, int dir, int rr, double& e0, double& e1, double& e2) {
-    // (a GLOBAL load, not a flat one: a flat load also counts on the LDS counter, and the chain's next wait for its own LDS traffic would
-    // wait for this trip to memory as well -- the very latency the early issue is meant to hide)
-    const __attribute__((address_space(1))) double* E = QGC(w.Ek) + 9 * (dir > 0 ? j + 1 : j);
-    e0 = dir > 0 ? E[rr % 3] : E[3 * (rr % 3)], e1 = dir > 0 ? E[3 + rr % 3] : E[3 * (rr % 3) + 1],
-    e2 = dir > 0 ? E[6 + rr % 3] : E[3 * (rr % 3) + 2];
-}
-
-// the diagonal block of one knot: S = T_j (- U) into registers, factorised (1 / d in I; in C the column images of kl_ldl or, for the blocks
-// on the panel path -- kl_panel_path(NK), the 36 x 36 blocks --, the panel images of kl_ldl_panels); P / pbase: see kl_ldl / kl_ldl_panels.
-// Timg != nullptr (512-thread build): T_j is read from the assembling wave's LDS image instead of global memory -- the block never leaves
-// the CU, and the chain does not start every knot with a trip to memory --; when the values have arrived *consumed = consumed_value
-// tells the assembling wave that it may overwrite the image.
-template <int NK>
-__device__ __forceinline__ bool knot_ldl(const QpWs& w, int j, bool minus_u, kl_lds* base, int r, bool act, int rr, kl_ldsi* P, int pbase,
-                                         const kl_lds* Timg = nullptr, kl_ldsi* consumed = nullptr, int consumed_value = 0) {
-    using A = KlArea<NK>;
-    kl_lds *C = base + A::C, *I = base + A::I, *U = base + A::C;
-    if constexpr (kl_panel_path(NK)) {  // S straight into the MFMA tiles of the panel-blocked factorisation (knot_lds.inc, kl_knot_panels)
-        if (Timg)
-            return kl_knot_panels<NK, true>([&](int mx, int mn) { return (double)Timg[mn * KL_LD + mx]; },  // (the images hold both triangles)
-                                      [&] {
-                                          kl_sync();
-                                          if (consumed) kl_publish(consumed, consumed_value);
-                                      },
-                                      minus_u, C, I, r, P, pbase);
-        const double* Tg = w.Td + (size_t)j * NK * NK;
-        return kl_knot_panels<NK, false>([&](int mx, int mn) { return Tg[mn * NK + mx]; }, [] {}, minus_u, C, I, r, P, pbase);
-    }
-    double a[NK];
-    if (Timg) {
-#pragma unroll
-        for (int k = 0; k < NK; ++k) a[k] = Timg[k * KL_LD + rr];
-        kl_sync();
-        if (consumed) kl_publish(consumed, consumed_value);
-    } else {
-        const double* Tg = w.Td + (size_t)j * NK * NK;
-        // T is symmetric: column access = row access; only k <= r was assembled and is used, but whole rows are fetched
-#pragma unroll
-        for (int k = 0; k < NK; ++k) a[k] = Tg[k * NK + rr];
-    }
-    if (minus_u) {
-#pragma unroll
-        for (int k = 0; k < NK; ++k) a[k] -= U[rr * KL_LDU + k];
-        kl_sync();
-    }
-    return kl_ldl<NK>(a, C, I, r, act, P, pbase);
-}
-
-// The fused path (kl_fused_path(NK), knot_lds.inc): the caller has accumulated -X_j D_jp^-1 X_j' in the tiles s (kl_fused_update, straight from
-// M_jp in MX: neither X nor U is stored); T_j is added to them and the block factorised.  Timg, consumed: as above.
-template <int NK>
-__device__ __forceinline__ bool knot_ldl_add(const QpWs& w, int j, kl_d4 (&s)[KlPanels<NK>::TILES], kl_lds* base, int r, kl_ldsi* P, int pbase,
-                                             const kl_lds* Timg = nullptr, kl_ldsi* consumed = nullptr, int consumed_value = 0) {
-    using A = KlArea<NK>;
-    kl_lds *C = base + A::C, *I = base + A::I;
-    if (Timg)
-        return kl_knot_panels_add<NK, true>(s, [&](int mx, int mn) { return (double)Timg[mn * KL_LD + mx]; },  // (the images hold both triangles)
-                                            [&] {
-                                                kl_sync();
-                                                if (consumed) kl_publish(consumed, consumed_value);
-                                            },
-                                            C, I, r, P, pbase);
-    const double* Tg = w.Td + (size_t)j * NK * NK;
-    return kl_knot_panels_add<NK, false>(s, [&](int mx, int mn) { return Tg[mn * NK + mx]; }, [] {}, C, I, r, P, pbase);
-}
-// the coupling coefficients of the rows a lane forms in kl_fused_update, towards the knot after j: coupling_coef for the rows 16 t + (lane & 15)
-template <int NK>
-__device__ __forceinline__ void fused_coupling_coef(const QpWs& w, int j, int dir, int lane, double (&cf)[KlPanels<NK>::NT][3]) {
-    const __attribute__((address_space(1))) double* E = QGC(w.Ek) + 9 * (dir > 0 ? j + 1 : j);  // (global loads, see coupling_coef)
-    kl_fused_coef<NK>(cf, lane, [&](int row, int q) { return dir > 0 ? E[3 * q + row % 3] : E[3 * (row % 3) + q]; });
-}
-
-// M = L^-T of the block just factorised: rows into MX (for the coupling factor) and, with 1 / d, into global memory (for the
-// substitutions).  FOLLOW: run by the chain's companion wave concurrently with knot_ldl of the chain wave (kl_inverse_rows: kl_follow_LinvT a
-// column or two behind the chain, or kl_inverse_panels one panel behind it).
-template <int NK, bool FOLLOW>
-__device__ __forceinline__ void knot_inverse(const QpWs& w, int j, kl_lds* base, int r, bool act, kl_ldsi* P, int pbase, int& seen, kl_ldsi* Mdone,
-                                             int done_value) {
-    using A = KlArea<NK>;
-    kl_lds *C = base + A::C, *MX = base + A::MX, *I = base + A::I;
-    double m[NK];
-    // (kl_inverse_rows announces *Mdone = done_value as soon as the chain may go on: after the read of 1 / d -- its next block overwrites I --, and on
-    // the fused path BEFORE the read-back of the row that the stores below need)
-    const double dinv = kl_inverse_rows<NK, FOLLOW>(m, C, I, MX, r, act, P, pbase, Mdone, done_value);
-    __attribute__((address_space(1))) double* Mg = QG(w.Lf + (size_t)j * KF_STRIDE(NK));
-    // (256-thread build: the next block's inputs, sent for a block ago by global_load_lds, are counted on this wave's memory counter; they have
-    // long landed -- drain the counter HERE, so that the tiles' wait for them does not have to wait for the row stores below as well)
-    if (FOLLOW && QP_FOLLOW_ASM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (act) {  // row r of M_j and 1 / d_j -> QpWs::Lf (16 bytes per lane and store instruction: the store path of a CU is issue bound)
-        __attribute__((address_space(1))) double* row = Mg + (size_t)r * NK;
-        if ((NK & 1) == 0) {
-#pragma unroll
-            for (int k = 0; k < NK; k += 2)
-                if (k + 1 >= r) *(__attribute__((address_space(1))) kl_d2*)(row + k) = kl_d2{m[k], m[k + 1]};  // (M_j is upper triangular; the staging does not fetch the rest)
-        } else {
-#pragma unroll
-            for (int k = 0; k < NK; ++k)
-                if (k >= r) row[k] = m[k];
-        }
-        Mg[NK * NK + r] = dinv;
-    }
-}
-
-// chain-side timers of the left chain (-DQP_PROFILE; 100 MHz clock, like the phase timers): SC 25 = the rank-NK update, 26 = waiting for the block
-// assembly, 27 = the knot itself (T into the tiles, factorisation, waiting for M; without the fused update also the coupling rows).
-// They must not change what they measure: the time stamp is wave-uniform and stays in scalar registers, a step adds its difference to a
-// 64-bit LDS word behind the progress words (cleared with them at the start of a factorisation; every lane adds, all but lane 0 of the left
-// chain add zero: no branch inside the step), and the three sums go to global memory once per factorisation (CHAIN_FLUSH).
-#if defined(QP_PROFILE) && !defined(QP_LHSTATS) && !defined(QP_SOLVE_TIMERS)
-#define CHAIN_TW(cnt, slot) ((__attribute__((address_space(3))) unsigned long long*)((cnt) + 96) + ((slot) - 25))
-#define CHAIN_T0 long long ct_ = wall_clock64()
-#define CHAIN_T(slot)                                                                                                                              \
-    do {                                                                                                                                           \
-        const long long t_ = wall_clock64();                                                                                                       \
-        __hip_atomic_fetch_add(CHAIN_TW(cnt, slot), (dir > 0 && r == 0) ? (unsigned long long)(t_ - ct_) : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-        ct_ = t_;                                                                                                                                  \
-    } while (0)
-#define CHAIN_FLUSH()                                                                                   \
-    do {                                                                                                \
-        kl_sync();                                                                                      \
-        if (w.prof && dir > 0 && r == 0)                                                                \
-            for (int k_ = 25; k_ < 28; ++k_) w.prof[k_] += (double)(long long)*CHAIN_TW(cnt, k_);       \
-    } while (0)
-#else
-#define CHAIN_T0
-#define CHAIN_T(slot)
-#define CHAIN_FLUSH()
-#endif
-// progress words of chain h (LDS ints behind the assembly counters): [2h] = images / pivots published by the chain wave (monotone over
-// the whole factorisation: block i publishes i * (NK + 1) + 1 ...), [2h + 1] = blocks whose M rows the companion wave has put into MX
-#define CHAIN_SYNC(cnt, h) ((kl_ldsi*)((cnt) + 64 + 2 * (h)))
-// 512-thread build: [h] = number of blocks chain h has read out of the assembling waves' LDS images (a wave may overwrite its image of
-// step i - 2 when this says i - 1)
-#define ASM_CONSUMED(cnt, h) ((kl_ldsi*)((cnt) + 72 + (h)))
-
-// one chain: blocks j0, j0+dir, ... (count of them).  The chain wave factorises; its companion wave (wave_factor_follow) computes
-// M_j = L_j^-T a column or two (panel path: one panel of 4 columns) behind and stores it.  On return the chain's LDS area holds the coupling factor X towards the middle
-// block (MX; on the fused path M of the chain's last block instead, once the companion is done) and the reciprocal pivots of its last block (I): wave_factor_mid
-// reads both chains' areas.
-template <int NK>
-__device__ __forceinline__ bool wave_factor_chain(const QpDims& d, const QpWs& w, int j0, int count, int dir, double* ldsW, int* cnt, int h) {
-    using A = KlArea<NK>;
-    kl_lds* base = (kl_lds*)ldsW;
-    kl_lds *MX = base + A::MX, *I = base + A::I, *U = base + A::C;
-    kl_ldsi *P = CHAIN_SYNC(cnt, h), *Mdone = P + 1;
-    const int r = threadIdx.x & 63;
-    const bool act = r < NK;
-    const int rr = act ? r : 0;
-    bool ok = true;
-    int seen = 0, seen_img = 0;
-    if constexpr (kl_fused_path(NK)) {
-        // S_j is formed in the tiles: -X_j D_jp^-1 X_j' from M_jp (MX: the companion's rows, which this wave no longer overwrites) as soon as the
-        // companion has announced them, still in front of the wait for T_j's image; then T_j, then the factorisation.  No coupling rows.
-        double cf[KlPanels<NK>::NT][3];
-        for (int i = 0, j = j0; i < count; ++i, j += dir) {
-            CHAIN_T0;
-            kl_d4 s[KlPanels<NK>::TILES];
-            kl_tiles_zero<NK>(s);
-            if (i > 0) {
-                kl_await(Mdone, i, seen);
-                CHAIN_T(27);
-                kl_fused_update<NK>(s, MX, I, r, cf);
-            }
-            CHAIN_T(25);
-            if (QP_FOLLOW_ASM)
-                kl_await(ASMF_READY(cnt, h), i + 1, seen_img);
-            else
-                wait_blocks(cnt, i);
-            CHAIN_T(26);
-            fused_coupling_coef<NK>(w, j, dir, r, cf);  // (issued here: nine loads from the L2, needed by the NEXT block's update)
-            const kl_lds* Timg = ASM_HELPERS > 0 ? (const kl_lds*)(ldsW - (size_t)h * A::SIZE + 2 * A::SIZE + 128 + (size_t)(h + 2 * (i & 1)) * ASML_DOUBLES(NK, (NK / 9)))
-                                 : QP_FOLLOW_ASM ? (const kl_lds*)(ldsW - (size_t)h * A::SIZE + 2 * A::SIZE + 128 + (size_t)h * ASML_DOUBLES(NK, (NK / 9)))
-                                                 : nullptr;
-            if (!knot_ldl_add<NK>(w, j, s, base, r, P, i * (NK + 1), Timg, ASM_CONSUMED(cnt, h), i + 1)) ok = false;
-            CHAIN_T(27);
-        }
-        CHAIN_FLUSH();
-        return ok;  // (the last block's M is waited for by the workgroup barrier in front of wave_factor_mid)
-    }
-    for (int i = 0, j = j0; i < count; ++i, j += dir) {
-        CHAIN_T0;
-        if (i > 0) kl_syrk<NK>(MX, I, U, r, false);
-        CHAIN_T(25);
-        if (QP_FOLLOW_ASM)
-            kl_await(ASMF_READY(cnt, h), i + 1, seen_img);  // the companion wave's image of this block
-        else
-            wait_blocks(cnt, i);
-        CHAIN_T(26);
-        double e0, e1, e2, x[NK];
-        coupling_coef(w, j, dir, rr, e0, e1, e2);  // (issued here: three loads from the L2, ~1 us under load, needed after the factorisation)
-        // (512-thread build: T_j from the LDS image of the assembling wave (side h, parity of the step), see twisted_factor)
-        // (256-thread build: from the ONE image of the chain's companion wave, see twisted_factor ROLE 2)
-        const kl_lds* Timg = ASM_HELPERS > 0 ? (const kl_lds*)(ldsW - (size_t)h * A::SIZE + 2 * A::SIZE + 128 + (size_t)(h + 2 * (i & 1)) * ASML_DOUBLES(NK, (NK / 9)))
-                             : QP_FOLLOW_ASM ? (const kl_lds*)(ldsW - (size_t)h * A::SIZE + 2 * A::SIZE + 128 + (size_t)h * ASML_DOUBLES(NK, (NK / 9)))
-                                             : nullptr;
-        if (!knot_ldl<NK>(w, j, i > 0, base, r, act, rr, P, i * (NK + 1), Timg, ASM_CONSUMED(cnt, h), i + 1)) ok = false;
-        kl_await(Mdone, i + 1, seen);
-        kl_coupling_rows<NK>(x, MX, r, act, e0, e1, e2);
-        CHAIN_T(27);
-    }
-    CHAIN_FLUSH();
-    return ok;
-}
-
-// the middle block collects both Schur complements (the chains' areas: ldsL = left chain = this wave's own area, ldsR = right chain)
-template <int NK>
-__device__ __forceinline__ bool wave_factor_mid(const QpDims& d, const QpWs& w, double* ldsL, double* ldsR, int* cnt, int cnt_idx) {
-    using A = KlArea<NK>;
-    kl_lds *bl = (kl_lds*)ldsL, *br = (kl_lds*)ldsR;
-    const int r = threadIdx.x & 63, mid = twist_mid(d.nj);
-    const bool act = r < NK;
-    const int rr = act ? r : 0;
-    int nsy = 0;
-    [[maybe_unused]] kl_d4 s[kl_fused_path(NK) ? KlPanels<NK>::TILES : 1];
-    if constexpr (kl_fused_path(NK)) {  // both chains' updates into the one set of tiles: the left chain's M with the coefficients towards mid from below, the right chain's from above
-        double cl[KlPanels<NK>::NT][3], cr[KlPanels<NK>::NT][3];
-        if (mid > 0) fused_coupling_coef<NK>(w, mid - 1, +1, r, cl);
-        if (mid + 1 < d.nj) fused_coupling_coef<NK>(w, mid + 1, -1, r, cr);
-        kl_tiles_zero<NK>(s);
-        if (mid > 0) kl_fused_update<NK>(s, bl + A::MX, bl + A::I, r, cl);
-        if (mid + 1 < d.nj) {
-            if (mid > 0) {  // each side summed on its own, then the two sums added: the roundings of U_left + U_right (once per factorisation)
-                kl_d4 s2[KlPanels<NK>::TILES];
-                kl_tiles_zero<NK>(s2);
-                kl_fused_update<NK>(s2, br + A::MX, br + A::I, r, cr);
-#pragma unroll
-                for (int t = 0; t < KlPanels<NK>::TILES; ++t) s[t] += s2[t];
-            } else {
-                kl_fused_update<NK>(s, br + A::MX, br + A::I, r, cr);
-            }
-        }
-    } else {
-        if (mid > 0) kl_syrk<NK>(bl + A::MX, bl + A::I, bl + A::C, r, false), nsy++;
-        if (mid + 1 < d.nj) kl_syrk<NK>(br + A::MX, br + A::I, bl + A::C, r, nsy > 0), nsy++;
-    }
-    if (QP_FOLLOW_ASM) {
-        int seen_img = 0;
-        kl_await(ASMF_READY(cnt, 0), mid + 1, seen_img);  // the left chain's companion makes the middle block after the chain's mid blocks
-    } else {
-        wait_blocks(cnt, cnt_idx);
-    }
-    // progress words of the middle block.  512-thread build: its M is computed by the left chain's companion wave, like every other
-    // block's (twisted_factor, ROLE 2) -- on the chain wave it is ~10 k cycles more at the end of every factorisation: one mission
-    // 122.4 -> 121.1 ms.  With two workgroups per CU the polling companion costs the neighbour more than it saves (-1.3 % at 2000
-    // resident, A/B on one box): the 256-thread build keeps M on the chain wave.
-    kl_ldsi* scratch = CHAIN_SYNC(cnt, 2);
-    const kl_lds* Timg = ASM_HELPERS > 0 ? (const kl_lds*)(ldsL + 2 * A::SIZE + 128 + (size_t)(2 * (cnt_idx & 1)) * ASML_DOUBLES(NK, (NK / 9)))
-                         : QP_FOLLOW_ASM ? (const kl_lds*)(ldsL + 2 * A::SIZE + 128) : nullptr;
-    bool ok;
-    if constexpr (kl_fused_path(NK))
-        ok = knot_ldl_add<NK>(w, mid, s, bl, r, scratch, 0, Timg);
-    else
-        ok = knot_ldl<NK>(w, mid, nsy > 0, bl, r, act, rr, scratch, 0, Timg);
-    if (!QP_MID_FOLLOW) {
-        int seen = 0;
-        knot_inverse<NK, false>(w, mid, bl, r, act, scratch, 0, seen, scratch, 0);
-    }
-    return ok;
-}
-
-// whole twisted factorisation; every thread of the workgroup calls it.  flag: LDS int.
-// The knot blocks T_j are ASSEMBLED HERE, by waves that do not run a chain, in the order the chains consume them (step i: blocks i
-// and nj-1-i; last the middle one), each step announced through an LDS counter (wait_blocks): the assembly -- 8-10 % of an
-// interior-point iteration when it was a phase of its own -- disappears behind the dependent chains.
-// ROLE: 0 = compiled for the two chain waves, 2 = for their companions (waves 2, 3), 1 = for the assembling waves (4..) of the
-// 512-thread build: three __noinline__ functions with the same workgroup barriers, see solve_staged.
-template <int NK, int ROLE>
-__device__ __forceinline__ bool twisted_factor(const QpDims& d, const QpWs& w, int* flag, double* lds, const AsmArgs* asmb) {
-    const int wave = (ROLE == 0 || ROLE == 2) ? (threadIdx.x >> 6) & 1 : 4, mid = twist_mid(d.nj);  // roles 0 / 2: which chain
-    const int nl = mid, nr = d.nj - 1 - mid, SF = nl > nr ? nl : nr;
-    constexpr int AREA = KlArea<NK>::SIZE;    // one chain wave's LDS area (knot_lds.inc)
-    int* cnt = (int*)(lds + 2 * AREA);  // [SF + 1] assembly counters, then (at +64) the chains' progress words
-    static_assert((QP_MAX_M - 1) / 2 + 1 <= 64, "cnt[0..SF] must end below CHAIN_SYNC (cnt + 64): sessions with M > QP_MAX_M are refused");
-    if (threadIdx.x == 0) *flag = 0;
-    __syncthreads();
-    bool ok = true;
-    // rows >= NK of the X images are never written by a row's own lane: clear them once (they only feed unused tile entries)
-    for (int i = threadIdx.x; i < 2 * AREA + 64; i += QP_THREADS) lds[i] = 0.0;
-    __syncthreads();
-    // The chain waves issue dependent instructions; whenever the SIMD's arbiter makes one of them queue behind the ready instructions
-    // of other waves (the helpers, the co-resident workgroup's sweeps) the chain stretches, while giving it the first slot costs the
-    // others next to nothing: raise the priority for the chain (+2.5 % at 2000 missions).
-    if (ROLE == 0) {
-        __builtin_amdgcn_s_setprio(QP_CHAIN_PRIO);
-        if (wave == 0 && mid > 0) ok = wave_factor_chain<NK>(d, w, 0, mid, +1, lds, cnt, 0);
-        if (wave == 1 && nr > 0) ok = wave_factor_chain<NK>(d, w, d.nj - 1, nr, -1, lds + AREA, cnt, 1);
-        if (wave == 1) __builtin_amdgcn_s_setprio(0);
-    }
-    if (ROLE == 1) {
-        // assembling waves (512-thread build): through the LDS like the 256-thread build's up-front assembly (assemble_knots_lds), one
-        // wave per block.  Waves 4, 5 take the left / right chain's block of the even steps, waves 6, 7 those of the odd steps (two
-        // chain steps of time per block); a wave announces its block by adding ASM_HELPERS / 2 to the step's counter, so that
-        // wait_blocks sees ASM_HELPERS when both blocks of a step are out.  The middle block (step SF) is wave 4's / 6's.
-        const AsmArgs A = *asmb;
-        const int hw = (threadIdx.x >> 6) - ASM_WAVE0, side = hw & 1, par = hw >> 1;  // par: parity of the steps this wave serves
-        double* scratch = lds + 2 * AREA + 128 + (size_t)hw * ASML_DOUBLES(NK, (NK / 9));
-        int i = par - 2;
-        kl_ldsi* consumed = ASM_CONSUMED(cnt, side);
-        int seen_c = 0;
-        assemble_knots_lds<false>(
-            A, scratch,
-            [&] {
-                for (i += 2; i <= SF; i += 2) {
-                    const bool work = i < SF ? (side ? i < nr : i < nl) : side == 0;
-                    if (work) {
-                        if (i >= 2) kl_await(consumed, i - 1, seen_c);  // the chain has read this wave's image of step i - 2
-                        return i < SF ? (side ? d.nj - 1 - i : i) : mid;
-                    }
-                    // nothing to assemble for this wave at step i: announce it all the same
-                    if ((threadIdx.x & 63) == 0)
-                        __hip_atomic_fetch_add(cnt + i, i < SF ? ASM_HELPERS / 2 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                return -1;
-            },
-            [&](int) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                if ((threadIdx.x & 63) == 0)
-                    __hip_atomic_fetch_add(cnt + i, i < SF ? ASM_HELPERS / 2 : ASM_HELPERS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            });
-    }
-    if (ROLE == 2) {
-        // companion of chain `wave`: M_j behind the chain's factorisation of block j
-        const int count = wave == 0 ? nl : nr, j0 = wave == 0 ? 0 : d.nj - 1, dir = wave == 0 ? +1 : -1;
-        kl_lds* base = (kl_lds*)(lds + wave * AREA);
-        kl_ldsi *P = CHAIN_SYNC(cnt, wave), *Mdone = P + 1;
-        const int r = threadIdx.x & 63;
-        int seen = 0;
-        if (QP_FOLLOW_ASM) {
-            // ... and the chain's blocks, assembled just in time: block n + 1 right after the companion work of block n, while the chain
-            // forms the coupling rows and the rank-NK update; the left chain's companion makes the MIDDLE block last.  One image per chain:
-            // the chain read block n out of it at the start of its factorisation (ASM_CONSUMED), long before block n + 1 is written.
-            const AsmArgs A = *asmb;
-            double* scratch = lds + 2 * AREA + 128 + (size_t)wave * ASML_DOUBLES(NK, (NK / 9));
-            kl_ldsi *ready = ASMF_READY(cnt, wave), *consumed = ASM_CONSUMED(cnt, wave);
-            const int total = count + (wave == 0 ? 1 : 0);
-            int seen_c = 0;
-            auto blk = [&](int n) { return n < count ? j0 + n * dir : mid; };
-            auto make = [&](int n) {  // block n's inputs are in the scratch (fetched a block ago): its tiles, then the fetch of block n + 1
-                if (n > 0) kl_await(consumed, n, seen_c);
-                fasm_tiles(A, scratch, blk(n));
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                kl_publish(ready, n + 1);
-                if (n + 1 < total) fasm_fetch(A, scratch, blk(n + 1));
-            };
-            if (total > 0) {
-                fasm_fetch(A, scratch, blk(0));
-                make(0);
-            }
-            for (int i = 0; i < count; ++i) {
-                knot_inverse<NK, true>(w, j0 + i * dir, base, r, r < NK, P, i * (NK + 1), seen, Mdone, i + 1);
-                if (i + 1 < total) make(i + 1);
-            }
-        } else {
-            for (int i = 0; i < count; ++i) knot_inverse<NK, true>(w, j0 + i * dir, base, r, r < NK, P, i * (NK + 1), seen, Mdone, i + 1);
-        }
-    }
-    if (!ok && (threadIdx.x & 63) == 0) atomicExch(flag, 1);
-    __threadfence_block();
-    __syncthreads();
-    if (*flag) return false;
-    if (ROLE == 0 && wave == 0) {
-        if (!wave_factor_mid<NK>(d, w, lds, lds + AREA, cnt, SF) && threadIdx.x == 0) *flag = 1;
-        __builtin_amdgcn_s_setprio(0);
-    }
-    if (QP_MID_FOLLOW && ROLE == 2 && wave == 0) {  // M of the middle block, behind wave_factor_mid's factorisation
-        const int r = threadIdx.x & 63;
-        int seen = 0;
-        kl_ldsi* P = CHAIN_SYNC(cnt, 2);
-        knot_inverse<NK, true>(w, mid, (kl_lds*)lds, r, r < NK, P, 0, seen, P + 1, 1);
-    }
-    __threadfence_block();
-    __syncthreads();
-    return *flag == 0;
-}
-
-// Substitutions T du = rhs for the twisted factorisation (round 3: matrix-vector products with the explicit M_j = L_j^-T instead of
-// 36-step dependent triangular solves).  With X_j = T_{j,jp} M_jp (jp = the chain's previous knot, never stored):
-//   forward   r'  = rhs_j - T_{j,jp} v_jp          (3x3-block sparse)         y = M_j' r'      z_j = D_j^-1 y      v_j = M_j z_j
-//   backward  w   = T_{jn,j}' x_jn                 (jn = next knot towards the middle)
-//             x_j = M_j (z_j - D_j^-1 M_j' w)
-// i.e. two dense products with the SAME staged matrix per chain step (one by columns, one by rows), vectors broadcast from LDS.
-// The knots' M_j are STAGED THROUGH LDS: waves 2.. prefetch the blocks of step s + QP_STAGE_BUFS - 1 (coalesced global reads) while
-// waves 0 / 1 run step s of the left / right chain.  rhs -> z -> x lives in LDS throughout (vec).
-// ROLE: 0 = compiled for the two chain waves, 1 = for the staging waves (2..): two __noinline__ functions (solve_entry_*), so that the
-// staging waves -- a dozen registers -- have no prologue saving callee-saved VGPRs.
-// The two products of a chain step use M_j's triangle with ALL 64 lanes: a lane owns a PIECE -- KsPieces::CH consecutive terms of one row
-// (or column) -- instead of a whole row, of which only NK <= 36 exist and whose lower half is zeros: 15 loads and multiply-adds per
-// lane instead of 36, then the up to three pieces of a row meet through 64 doubles of LDS.  Chunk t of the product by rows covers the
-// columns NK - CH (t + 1) .. NK - 1 - CH t (anchored at the right edge: row r needs the chunks with NK - 1 - CH t >= r), chunk t of the
-// product by columns the rows CH t .. CH t + CH - 1 (anchored at the top: column c needs the chunks with CH t <= c).  Terms that fall
-// left of / below the diagonal multiply the stage buffers' zeros, terms outside the block multiply the zero padding of the VECTOR (KS_VPAD
-// slots either side; whatever finite number sits at the matrix address): no masks, no branches.
-#define KS_VPAD 16                       // zero slots either side of a chain vector
-#define KS_VLEN (KS_VPAD + KL_I + KS_VPAD)  // doubles per vector (the slot NK + 12 takes the writes of the lanes without a row)
-template <int NK>
-struct KsPieces {
-    static constexpr int CH = (NK * 15 + 35) / 36;  // 36 -> 15, 27 -> 12, 18 -> 8, 9 -> 4
-    static constexpr int N0 = NK, N1 = NK - CH > 0 ? NK - CH : 0, N2 = NK - 2 * CH > 0 ? NK - 2 * CH : 0;
-    static_assert(NK - 3 * CH <= 0 && N0 + N1 + N2 <= 64, "three chunks, one wavefront");
-    static_assert(3 * CH - NK <= KS_VPAD && 3 * CH - 1 - (NK - 1) <= KS_VPAD, "vector padding");
-    __device__ static __forceinline__ void of_lane(int lane, int& idx, int& t) {
-        t = lane < N0 ? 0 : (lane < N0 + N1 ? 1 : 2);
-        idx = lane < N0 ? lane : (lane < N0 + N1 ? lane - N0 : (lane < N0 + N1 + N2 ? lane - N0 - N1 : 0));
-    }
-};
-// sum_k Mst[k][c] * b[k] for column c = rr (lanes rr < NK; b: vector base, i.e. entry 0); psum: 64 doubles of scratch
-template <int NK>
-__device__ __forceinline__ double kl_matvec_cols(const kl_lds* Mst, const kl_lds* b, kl_lds* psum, int lane) {
-    using P = KsPieces<NK>;
-    int idx, t;
-    P::of_lane(lane, idx, t);
-    const int k0 = P::CH * t, c = k0 + idx;
-    const kl_lds* mp = Mst + k0 * KL_LD + c;
-    const kl_lds* bp = b + k0;
-    double mv[P::CH], bv[P::CH];
-#pragma unroll
-    for (int j = 0; j < P::CH; ++j) mv[j] = mp[j * KL_LD], bv[j] = bp[j];
-    double s0 = 0, s1 = 0, s2 = 0;
-#pragma unroll
-    for (int j = 0; j < P::CH; ++j) {
-        if (j % 3 == 0) s0 += mv[j] * bv[j];
-        if (j % 3 == 1) s1 += mv[j] * bv[j];
-        if (j % 3 == 2) s2 += mv[j] * bv[j];
-    }
-    psum[lane] = (s0 + s1) + s2;
-    kl_sync();
-    const int cc = lane < NK ? lane : 0;
-    double r = psum[cc];
-    if (P::N1 > 0) r += cc >= P::CH ? psum[P::N0 + cc - P::CH] : 0.0;
-    if (P::N2 > 0) r += cc >= 2 * P::CH ? psum[P::N0 + P::N1 + cc - 2 * P::CH] : 0.0;
-    return r;
-}
-// sum_k Mst[r][k] * b[k] for row r = rr
-template <int NK>
-__device__ __forceinline__ double kl_matvec_rows(const kl_lds* Mst, const kl_lds* b, kl_lds* psum, int lane) {
-    using P = KsPieces<NK>;
-    int idx, t;
-    P::of_lane(lane, idx, t);
-    const int k0 = NK - P::CH * (t + 1);  // may be negative: the vector is padded, the matrix address holds some finite number
-    const kl_lds* mp = Mst + idx * KL_LD + k0;
-    const kl_lds* bp = b + k0;
-    double mv[P::CH], bv[P::CH];
-#pragma unroll
-    for (int j = 0; j < P::CH; ++j) mv[j] = mp[j], bv[j] = bp[j];
-    double s0 = 0, s1 = 0, s2 = 0;
-#pragma unroll
-    for (int j = 0; j < P::CH; ++j) {
-        if (j % 3 == 0) s0 += mv[j] * bv[j];
-        if (j % 3 == 1) s1 += mv[j] * bv[j];
-        if (j % 3 == 2) s2 += mv[j] * bv[j];
-    }
-    psum[lane] = (s0 + s1) + s2;
-    kl_sync();
-    const int rr = lane < NK ? lane : 0;
-    double r = psum[rr];
-    if (P::N1 > 0) r += rr < P::N1 ? psum[P::N0 + rr] : 0.0;
-    if (P::N2 > 0) r += rr < P::N2 ? psum[P::N0 + P::N1 + rr] : 0.0;
-    return r;
-}
-
-template <int NK>
-struct KsLayout {  // doubles
-    static constexpr int SM = NK * KL_LD, SCH = SM + KL_I, STG = 2 * SCH;  // a stage: left chain (M, 1/d), right chain (M, 1/d)
-    static constexpr int LEAD = 16;  // zeros in front of the first stage buffer (a row piece may start a few entries before its block)
-    // per chain: A (r' / w), Z (z / u), V (v / x of the block just done), each with zero padding either side, and the pieces' scratch
-    static constexpr int VECS = 6 * KS_VLEN + 2 * 64;
-};
-
-// (round 6) the solution's way back to control space (apply_F) can start from the LDS vector the substitutions end with, instead of from a copy
-// in global memory written by one loop and read back by the next: dx_out != null fuses it into the epilogue (wave path only)
-struct SolveOut {
-    double* dx_out;    // [nb][3][oq] direction in control space, or null: the reduced solution goes to rhs as before
-    const double* Lk;  // QpWs::Lk
-    int oq;
-    // ... and the right-hand side (rhs_from_acc) can be formed straight into that LDS vector: rhs_mode 1 = predictor, 2 = corrector, 0 = read rhs
-    int rhs_mode = 0;
-    const double* cpacc = nullptr;  // QpWs::cpacc
-    const double* rbase = nullptr;  // QpWs::rbase
-    double sigma_mu = 0;
-};
-template <int NK, int ROLE>
-__device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, double* rhs, double* lds, SolveOut so = SolveOut{nullptr, nullptr, 0}) {
-    using KS = KsLayout<NK>;
-    constexpr int STG = KS::STG, SCH = KS::SCH, SM = KS::SM;
-    const int tid = threadIdx.x, nj = d.nj, mid = twist_mid(nj);
-    const int nl = mid, nr = nj - 1 - mid, SF = nl > nr ? nl : nr;
-    const int nsteps = 2 * SF + 1;  // SF forward steps, the middle block, SF backward steps
-    lds += KS::LEAD;                                   // (zero-filled with the stage buffers below)
-    kl_lds* vec = (kl_lds*)(lds + QP_STAGE_BUFS * STG);  // nj*NK: rhs -> z -> x  (LDS pointers: through generic ones every access is a flat instruction)
-    kl_lds* small = vec + ((nj * NK + 1) & ~1);        // [2 chains][A, Z, V][KS_VLEN], then [2 chains][64] partial sums
-    if (so.rhs_mode) {  // rhs_from_acc into the LDS vector (same arithmetic): rhs = rbase + F'(G'v) of the sweep's accumulators
-        constexpr int nu = NK / 3;
-        const int oq = so.oq;
-        const size_t ncp = (size_t)(NK / 9) * oq;
-        const bool corrector = so.rhs_mode == 2;
-        for (int it = tid; it < nj * nu; it += QP_THREADS) {
-            const int j = it / nu + 1, u = it % nu, a = u / 3, k = u % 3;
-            double g[6];  // G'v at control points 6(j-1)+3 .. 6j+2 of (agent a, dim k)
-#pragma unroll
-            for (int q = 0; q < 6; ++q) {
-                const int j6 = 6 * (j - 1) + 3 + q;
-                const __attribute__((address_space(1))) double* ac = QGC(so.cpacc) + (size_t)a * oq + j6;
-                g[q] = corrector ? ac[k * ncp] - so.sigma_mu * ac[(3 + k) * ncp] : ac[(6 + k) * ncp];
-            }
-            const __attribute__((address_space(1))) double* L = QGC(so.Lk) + 9 * j;
-            const size_t o0 = (size_t)(j - 1) * NK + u * 3;
-#pragma unroll
-            for (int e = 0; e < 3; ++e) vec[o0 + e] = QGC(so.rbase)[o0 + e] + g[3 + e] + L[0 + e] * g[0] + L[3 + e] * g[1] + L[6 + e] * g[2];
-        }
-    } else {  // rhs -> LDS: every thread's loads first, then its stores (one trip to memory instead of one per round; see apply_F)
-        constexpr int RQ = 4;
-        for (int i0 = tid; i0 < nj * NK; i0 += RQ * QP_THREADS) {
-            double t[RQ];
-#pragma unroll
-            for (int q = 0; q < RQ; ++q) t[q] = i0 + q * QP_THREADS < nj * NK ? rhs[i0 + q * QP_THREADS] : 0.0;
-#pragma unroll
-            for (int q = 0; q < RQ; ++q)
-                if (i0 + q * QP_THREADS < nj * NK) vec[i0 + q * QP_THREADS] = t[q];
-        }
-    }
-    for (int i = tid; i < KS::VECS; i += QP_THREADS) small[i] = 0.0;
-    // block indices handled at step s by the left / right wave (-1: idle)
-    auto left_j = [&](int s) { return s < SF ? (s - (SF - nl) >= 0 ? s - (SF - nl) : -1) : (s == SF ? mid : (mid - 1 - (s - SF - 1) >= 0 ? mid - 1 - (s - SF - 1) : -1)); };
-    auto right_j = [&](int s) { return s < SF ? (s - (SF - nr) >= 0 ? nj - 1 - (s - (SF - nr)) : -1) : (s == SF ? -1 : (mid + 1 + (s - SF - 1) <= nj - 1 ? mid + 1 + (s - SF - 1) : -1)); };
-    // Staging (waves 2..): only the upper triangle of M_j and 1 / d_j are fetched -- NE elements per chain -- and every staging thread's
-    // elements (the same for every step) are mapped once per call, so that a step is ONE batch of loads in flight per thread and a
-    // batch of LDS stores.  What lies left of the diagonal in the stage buffers is zero-filled once per call.
-    constexpr int NTRI = NK * (NK + 1) / 2, NE = NTRI + NK, NST = QP_THREADS - 128, MAXE = (2 * NE + NST - 1) / NST;
-    int soff[MAXE], doff[MAXE];  // element u of this thread: source offset inside a knot's Lf slot, destination inside a stage (-1: none)
-    if (ROLE == 1) {
-#pragma unroll
-        for (int u = 0; u < MAXE; ++u) {
-            const int e = (tid - 128) + u * NST;
-            soff[u] = 0, doff[u] = -1;
-            if (e < 2 * NE) {
-                const int side = e >= NE, idx = side ? e - NE : e;
-                if (idx < NTRI) {
-                    int rw = (int)(((2 * NK + 1) - sqrtf((float)((2 * NK + 1) * (2 * NK + 1) - 8 * idx))) * 0.5f);
-                    if (rw * NK - rw * (rw - 1) / 2 > idx) rw--;
-                    if ((rw + 1) * NK - (rw + 1) * rw / 2 <= idx) rw++;
-                    const int k = rw + idx - (rw * NK - rw * (rw - 1) / 2);
-                    soff[u] = rw * NK + k, doff[u] = side * SCH + rw * KL_LD + k;
-                } else {
-                    soff[u] = NK * NK + (idx - NTRI), doff[u] = side * SCH + SM + (idx - NTRI);
-                }
-            }
-        }
-    }
-    for (int i = tid; i < KS::LEAD + QP_STAGE_BUFS * STG; i += QP_THREADS) (lds - KS::LEAD)[i] = 0.0;
-    __syncthreads();
-    auto stage = [&](int s, double* buf) {
-        const int jl = left_j(s), jr = right_j(s);
-        const double* srcl = w.Lf + (size_t)(jl >= 0 ? jl : 0) * KF_STRIDE(NK);
-        const double* srcr = w.Lf + (size_t)(jr >= 0 ? jr : 0) * KF_STRIDE(NK);
-        double tmp[MAXE];
-#pragma unroll
-        for (int u = 0; u < MAXE; ++u) {
-            const bool right = doff[u] >= SCH;
-            const bool on = doff[u] >= 0 && (right ? jr >= 0 : jl >= 0);
-            tmp[u] = on ? (right ? srcr : srcl)[soff[u]] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < MAXE; ++u) {
-            const bool right = doff[u] >= SCH;
-            if (doff[u] >= 0 && (right ? jr >= 0 : jl >= 0)) buf[doff[u]] = tmp[u];
-        }
-    };
-    // (round 6) the same in two halves, so that a staging thread's loads can stay in flight ACROSS step barriers: under full load a trip to global
-    // memory (3-5 us) is longer than a chain step (~1.5 us), and a staging wave that loads, waits and stores inside one step made every
-    // step as long as that trip however many stage buffers there were (which is why a third buffer never paid).  With QP_STAGE_REGS = R
-    // register sets the loads of step s + QP_STAGE_BUFS - 1 + R are issued at step s and stored R steps later.
-    auto stage_load = [&](int s, double (&tmp)[MAXE]) {
-        if (s >= nsteps) return;
-        const int jl = left_j(s), jr = right_j(s);
-        // (explicitly GLOBAL loads and LDS stores: through generic pointers they are flat instructions, which count on both memory counters
-        // and make the compiler wait for ALL of them at the first use -- no load would stay in flight across a barrier)
-        typedef __attribute__((address_space(1))) const double gdbl;
-        gdbl* srcl = (gdbl*)(w.Lf + (size_t)(jl >= 0 ? jl : 0) * KF_STRIDE(NK));
-        gdbl* srcr = (gdbl*)(w.Lf + (size_t)(jr >= 0 ? jr : 0) * KF_STRIDE(NK));
-        // no predicates: a load nobody needs reads a valid address (soff = 0, knot 0) and is never stored -- straight-line loads are what
-        // lets the compiler count them (s_waitcnt vmcnt(n), n > 0) instead of waiting for all
-#pragma unroll
-        for (int u = 0; u < MAXE; ++u) tmp[u] = (doff[u] >= SCH ? srcr : srcl)[soff[u]];
-    };
-    auto stage_store = [&](int s, const double (&tmp)[MAXE], double* buf) {
-        if (s >= nsteps) return;
-        const int jl = left_j(s), jr = right_j(s);
-        kl_lds* bl = (kl_lds*)buf;
-#pragma unroll
-        for (int u = 0; u < MAXE; ++u) {
-            const bool right = doff[u] >= SCH;
-            if (doff[u] >= 0 && (right ? jr >= 0 : jl >= 0)) bl[doff[u]] = tmp[u];
-        }
-    };
-    if (ROLE == 1)
-        for (int s0 = 0; s0 < QP_STAGE_BUFS - 1 && s0 < nsteps; ++s0) stage(s0, lds + s0 * STG);
-    __syncthreads();
-    const int wave = ROLE == 0 ? (tid >> 6) & 1 : 2, r = tid & 63;  // (role 1 only needs "wave >= 2")
-    const bool act = r < NK;
-    const int rr = act ? r : 0, g3 = 3 * (rr / 3), r3 = rr % 3;
-    const int rs = act ? r : NK + 12;  // lanes >= NK write a slot behind the zero padding of the chain vectors
-    if (wave < 2) __builtin_amdgcn_s_setprio(QP_CHAIN_PRIO);  // see twisted_factor
-    // the three coupling coefficients a chain step starts with (forward: row rr of T_{j,jp}; backward: column rr of T_{jn,j}) come from
-    // global memory: fetched ONE STEP AHEAD (the trip to the L2, ~1 us under load, was the first thing every step waited for)
-    auto step_coef = [&](int s, double& q0, double& q1, double& q2) {
-        q0 = q1 = q2 = 0.0;
-        if (ROLE != 0 || s >= nsteps || s == SF) return;
-        const int jb = wave == 0 ? left_j(s) : right_j(s);
-        if (jb < 0) return;
-        const int dir = wave == 0 ? +1 : -1;
-        if (s < SF) {
-            const bool has_prev = wave == 0 ? jb > 0 : jb + 1 < nj;
-            if (has_prev) coupling_coef(w, jb - dir, dir, rr, q0, q1, q2);
-        } else {
-            const __attribute__((address_space(1))) double* E = QGC(w.Ek) + 9 * (dir > 0 ? jb + 1 : jb);
-            q0 = dir > 0 ? E[3 * r3] : E[r3], q1 = dir > 0 ? E[3 * r3 + 1] : E[3 + r3], q2 = dir > 0 ? E[3 * r3 + 2] : E[6 + r3];
-        }
-    };
-    double cf0, cf1, cf2;
-    step_coef(0, cf0, cf1, cf2);
-#ifdef QP_SOLVE_TIMERS  // developer build: left chain wave, SC 25 = work of the steps, 26 = waiting at the step barrier (staging wave: 29 / 30, right chain: 33 / 34)
-    long long st_ = wall_clock64();
-#define SOLVE_T(slot)                                                              \
-    do {                                                                           \
-        const long long t_ = wall_clock64();                                       \
-        const int who_ = ROLE == 0 ? (tid == 0 ? 0 : (tid == 64 ? 8 : -1)) : (tid == 128 ? 4 : -1); /* left chain 25/26, staging wave 29/30, right chain 33/34 */ \
-        if (w.prof && who_ >= 0) w.prof[slot + who_] += (double)(t_ - st_);        \
-        st_ = t_;                                                                  \
-    } while (0)
-#else
-#define SOLVE_T(slot)
-#endif
-    if (ROLE == 1 && QP_STAGE_REGS > 0) {
-        constexpr int R = QP_STAGE_REGS > 0 ? QP_STAGE_REGS : 1;
-        double tq[R][MAXE];
-#pragma unroll
-        for (int k = 0; k < R; ++k) stage_load(QP_STAGE_BUFS - 1 + k, tq[k]);
-        // steady state, straight-line (no predicate, no branch between a load and its store: only then does the compiler count the loads in
-        // flight instead of waiting for all of them): every element is stored -- the ones a thread does not have go to a padding column
-        // nobody's products see (row 0, column KL_LD - 1, times the zero padding of the vectors), a chain that idles at a step gets knot 0's
-        // numbers into its half of the buffer, which it does not read
-        int dsto[MAXE];
-#pragma unroll
-        for (int u = 0; u < MAXE; ++u) dsto[u] = doff[u] >= 0 ? doff[u] : KL_LD - 1;
-        typedef __attribute__((address_space(1))) const double gdbl;
-        // The loads of the NEXT R steps are issued at the top of an iteration and first touched at its bottom, R step barriers later: the
-        // compiler drains the memory counter completely wherever a loop-carried load is used (it does not count across a back edge), so the
-        // one place where everything must have landed is made to be the place where it drains.
-        double nq[R][MAXE];
-        int s = 0;
-        for (; s + 2 * R + QP_STAGE_BUFS - 1 <= nsteps; s += R) {
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                const int sl = s + R + k + QP_STAGE_BUFS - 1;
-                const int jl = left_j(sl), jr = right_j(sl);
-                gdbl* srcl = (gdbl*)(w.Lf + (size_t)(jl >= 0 ? jl : 0) * KF_STRIDE(NK));
-                gdbl* srcr = (gdbl*)(w.Lf + (size_t)(jr >= 0 ? jr : 0) * KF_STRIDE(NK));
-#pragma unroll
-                for (int u = 0; u < MAXE; ++u) nq[k][u] = (doff[u] >= SCH ? srcr : srcl)[soff[u]];
-            }
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                const int sp = s + k + QP_STAGE_BUFS - 1;
-                kl_lds* bl = (kl_lds*)(lds + (sp % QP_STAGE_BUFS) * STG);
-#pragma unroll
-                for (int u = 0; u < MAXE; ++u) bl[dsto[u]] = tq[k][u];
-                __syncthreads();
-            }
-#pragma unroll
-            for (int k = 0; k < R; ++k)
-#pragma unroll
-                for (int u = 0; u < MAXE; ++u) tq[k][u] = nq[k][u];
-        }
-        for (; s < nsteps; s += R) {  // the last few steps (loads or stores that do not exist any more: predicated)
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                if (s + k < nsteps) {  // (uniform: every thread of the workgroup passes nsteps barriers, here or in the chains' loop)
-                    const int sp = s + k + QP_STAGE_BUFS - 1;
-                    stage_store(sp, tq[k], lds + (sp % QP_STAGE_BUFS) * STG);
-                    stage_load(sp + R, tq[k]);
-                    __syncthreads();
-                }
-            }
-        }
-    } else
-    for (int s = 0; s < nsteps; ++s) {
-        SOLVE_T(26);
-        const double e0 = cf0, e1 = cf1, e2 = cf2;
-        step_coef(s + 1, cf0, cf1, cf2);
-        double* buf = lds + (s % QP_STAGE_BUFS) * STG;
-        if (ROLE == 1) {
-            const int sp = s + QP_STAGE_BUFS - 1;
-            if (sp < nsteps) stage(sp, lds + (sp % QP_STAGE_BUFS) * STG);
-        } else if (s == SF) {
-            if (wave == 0) {  // middle block: forward with both neighbours' v, then backward; x_mid goes to both chains' V
-                const kl_lds* Mst = (const kl_lds*)buf;
-                kl_lds *A0 = (kl_lds*)small + KS_VPAD, *Z0 = A0 + KS_VLEN, *V0 = A0 + 2 * KS_VLEN, *V1 = A0 + 5 * KS_VLEN;
-                kl_lds* ps = (kl_lds*)small + 6 * KS_VLEN;
-                double v = vec[mid * NK + rr];
-                if (mid > 0) {
-                    double e0, e1, e2;
-                    coupling_coef(w, mid - 1, +1, rr, e0, e1, e2);
-                    v -= e0 * V0[g3] + e1 * V0[g3 + 1] + e2 * V0[g3 + 2];
-                }
-                if (mid + 1 < nj) {
-                    double e0, e1, e2;
-                    coupling_coef(w, mid + 1, -1, rr, e0, e1, e2);
-                    v -= e0 * V1[g3] + e1 * V1[g3 + 1] + e2 * V1[g3 + 2];
-                }
-                A0[rs] = v;
-                kl_sync();
-                const double z = Mst[SM + rr] * kl_matvec_cols<NK>(Mst, A0, ps, r);
-                Z0[rs] = z;
-                kl_sync();
-                const double x = kl_matvec_rows<NK>(Mst, Z0, ps, r);
-                kl_sync();
-                V0[rs] = x, V1[rs] = x;
-                if (act) vec[mid * NK + r] = x;
-            }
-        } else {
-            const bool fwd = s < SF;
-            const int jb = wave == 0 ? left_j(s) : right_j(s);
-            if (jb >= 0) {
-                const kl_lds* Mst = (const kl_lds*)(buf + (wave == 0 ? 0 : SCH));
-                kl_lds *A = (kl_lds*)small + KS_VPAD + (wave == 0 ? 0 : 3 * KS_VLEN), *Z = A + KS_VLEN, *V = A + 2 * KS_VLEN;
-                kl_lds* ps = (kl_lds*)small + 6 * KS_VLEN + (wave == 0 ? 0 : 64);
-                const double dinv = Mst[SM + rr];
-                if (fwd) {
-                    double v = vec[jb * NK + rr];
-                    const bool has_prev = wave == 0 ? jb > 0 : jb + 1 < nj;
-                    if (has_prev) v -= e0 * V[g3] + e1 * V[g3 + 1] + e2 * V[g3 + 2];  // r' = rhs_j - T_{j,jp} v_jp
-                    kl_sync();
-                    A[rs] = v;
-                    kl_sync();
-                    const double z = dinv * kl_matvec_cols<NK>(Mst, A, ps, r);
-                    Z[rs] = z;
-                    if (act) vec[jb * NK + r] = z;
-                    kl_sync();
-                    const double vj = kl_matvec_rows<NK>(Mst, Z, ps, r);
-                    kl_sync();
-                    V[rs] = vj;
-                } else {
-                    // w = T_{jn,j}' x_jn: column rr of the 3x3 block of its (agent, dim) group, rows g3 .. g3+2 (x_jn sits in V)
-                    const double wv = e0 * V[g3] + e1 * V[g3 + 1] + e2 * V[g3 + 2];
-                    kl_sync();
-                    A[rs] = wv;
-                    kl_sync();
-                    const double u = vec[jb * NK + rr] - dinv * kl_matvec_cols<NK>(Mst, A, ps, r);
-                    Z[rs] = u;
-                    kl_sync();
-                    const double x = kl_matvec_rows<NK>(Mst, Z, ps, r);
-                    kl_sync();
-                    V[rs] = x;
-                    if (act) vec[jb * NK + r] = x;
-                }
-            }
-        }
-        SOLVE_T(25);
-        __syncthreads();
-    }
-    if (wave < 2) __builtin_amdgcn_s_setprio(0);
-    if (so.dx_out) {  // apply_F from the LDS vector (same arithmetic, same order)
-        constexpr int nu = NK / 3;
-        const int oq = so.oq;
-        for (int it = tid; it < nj * nu; it += QP_THREADS) {
-            const int j = it / nu + 1, u = it % nu;
-            const kl_lds* uu = vec + (size_t)(j - 1) * NK + u * 3;
-            const __attribute__((address_space(1))) double* L = QGC(so.Lk) + 9 * j;
-            const double u0 = uu[0], u1 = uu[1], u2 = uu[2];
-            __attribute__((address_space(1))) double* o = QG(so.dx_out) + (size_t)u * oq + 6 * (j - 1) + 3;  // control points 6(j-1)+3 .. 6j+2
-            o[0] = L[0] * u0 + L[1] * u1 + L[2] * u2;
-            o[1] = L[3] * u0 + L[4] * u1 + L[5] * u2;
-            o[2] = L[6] * u0 + L[7] * u1 + L[8] * u2;
-            o[3] = u0, o[4] = u1, o[5] = u2;
-        }
-        for (int it = tid; it < nu * 6; it += QP_THREADS) {  // the pinned ends
-            const int u = it / 6, q = it % 6;
-            QG(so.dx_out)[(size_t)u * oq + (q < 3 ? q : oq - 6 + q)] = 0.0;
-        }
-    } else {
-        for (int i = tid; i < nj * NK; i += QP_THREADS) rhs[i] = vec[i];
-    }
-    __threadfence_block();
-    __syncthreads();
-}
+#include "qp_wave_factor.inc"  // nk <= 36: twisted factorisation in wave registers
+#include "qp_wave_solve.inc"   // nk <= 36: staged substitutions
 
 // ------------------------------------------------------------------------------------------------------------
 // tiled path (nk > 36: batches of 5..64 agents, e.g. plan/batch_size = 8 or the joint QP of a whole mission).
@@ -2460,36 +1378,9 @@ __device__ __forceinline__ void solve_dispatch(const QpDims& d, const QpWs& w, d
     if (ROLE != 1) solve_tiled(d, w, rhs, lA, lds_avail);  // (the staging role only exists on the wave path)
 }
 
-
 // The block factorisation / substitutions are compiled as stand-alone functions with by-value arguments: their register
 // allocation (the wave-register path wants every VGPR) then neither depends on nor disturbs the row sweeps around them,
 // and no kernel-level struct has its address taken.
-struct BlkArgs {
-    int nk, nj, ldb, lds_avail;
-    double *Td, *To, *Lf;
-    double* Ek;
-    double* prof;
-};
-// Arguments of a non-kernel function arrive in VECTOR registers, and the compiler treats them as divergent: every pointer, dimension and
-// address derived from them would live in VGPRs for the whole function -- that is what spills inside the knot
-// loops, and a spill reload on a dependent chain costs a memory round trip.  They are wave-uniform by construction, so they are moved to
-// scalar registers explicitly (v_readfirstlane); everything computed from them then stays scalar.
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-template <class T>
-__device__ __forceinline__ T* uni(T* p) {
-    const unsigned long long v = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (T*)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ void blk_unpack(const BlkArgs& b, QpDims& d, QpWs& w) {
-    d = QpDims{};
-    w = QpWs{};
-    d.nk = uni(b.nk), d.nj = uni(b.nj), d.ldb = uni(b.ldb), d.ld = d.nk + 1;
-    w.Td = uni(b.Td), w.To = uni(b.To), w.Lf = uni(b.Lf), w.Ek = uni(b.Ek), w.prof = uni(b.prof);
-}
-__device__ __forceinline__ AsmArgs uni(const AsmArgs& A) {
-    return AsmArgs{uni(A.cpacc), uni(A.pwgt), uni(A.Lk), uni(A.Dk), uni(A.normals), uni(A.Td), uni(A.N), uni(A.M), uni(A.nb), uni(A.first), uni(A.oq), uni(A.ldb)};
-}
 // (inlining these two was measured: 1100 VGPR spills, 31k instead of 51k agent-trajectories/s)
 __device__ __noinline__ bool factor_entry_chain(BlkArgs b, AsmArgs A, double* lds, int* flag) {
     QpDims d;
@@ -2538,9 +1429,7 @@ __device__ __forceinline__ void solve_entry(const BlkArgs& b, double* rhs, doubl
         solve_entry_chain(b, rhs, lds, so);
 }
 
-#define QP_POLISH_PART 2
-#include "qp_polish.inc"
-#undef QP_POLISH_PART
+#include "qp_polish.inc"  // the active-set polish: the algorithms (its records: qp_polish_types.inc, above the sweeps)
 
 #ifdef QP_TRACE
 #ifndef QP_TRACE_BATCH
@@ -2828,14 +1717,11 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
     double* red = lds_raw;  // 16
     int* flag = (int*)(lds_raw + 16);
     double* lds = lds_raw + 32;
-    double* lA = lds;
 #ifdef QP_PROFILE
     const BlkArgs ba{d.nk, d.nj, d.ldb, c.lds_avail, w.Td, w.To, w.Lf, w.Ek, scal};
 #else
     const BlkArgs ba{d.nk, d.nj, d.ldb, c.lds_avail, w.Td, w.To, w.Lf, w.Ek, nullptr};
 #endif
-    double* red2 = red;
-    int* flag2 = flag;
 
     PROF_DECL;
     int frozen_free_rows = 0, nfar = 0;
@@ -2950,7 +1836,7 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
                            mu < (early_tries == 0 ? QP_EARLY_TOL : 1e-2 * QP_EARLY_TOL);
         if (S.p.polish && (polish_first || early)) {
             if (!polish_first) early_tries++;
-            const int acc = polish_entry(c, pw, lds, red2, flag2, polish_first ? 1 : 0);
+            const int acc = polish_entry(c, pw, lds, red, flag, polish_first ? 1 : 0);
             __syncthreads();
             PROF(0);
 #ifdef QP_POLSTATS
@@ -2967,12 +1853,12 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
         if (d.nk > 36)
             assemble_blocks(c, lds);
         else if (ASM_HELPERS == 0 && !QP_FOLLOW_ASM)
-            assemble_blocks_lds(asm_args(c), d.nj, lds);  // (256-thread build, round 6: the chains' companion waves assemble just in time instead)  // (256-thread build, round 6: the chains' companion waves assemble just in time instead)
+            assemble_blocks_lds(asm_args(c), d.nj, lds);  // (256-thread build, round 6: the chains' companion waves assemble just in time instead)
         PROF(3);
         __threadfence_block();
         __syncthreads();
         TRC(5, trc_sum(w.Td, (size_t)d.nj * d.ldb * d.ldb, red));
-        if (!factor_entry(ba, asm_args(c), lA, flag)) {
+        if (!factor_entry(ba, asm_args(c), lds, flag)) {
             fail_reason = 2;  // Newton matrix not positive definite
             break;
         }
@@ -2988,7 +1874,7 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
         if (d.nk <= 36) {
             PROF(5);
             // (fused: starts with rhs_from_acc into the LDS vector; ends with apply_F from it, fence and barrier -- see SolveOut)
-            solve_entry(ba, w.rhs, lA, SolveOut{w.dxa, w.Lk, d.oq, 1, w.cpacc, w.rbase, 0.0});
+            solve_entry(ba, w.rhs, lds, SolveOut{w.dxa, w.Lk, d.oq, 1, w.cpacc, w.rbase, 0.0});
             PROF(6);
         } else
 #endif
@@ -2998,7 +1884,7 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
             __syncthreads();
             PROF(5);
             TRC(7, trc_sum(w.rhs, (size_t)d.nj * d.nk, red));
-            solve_entry(ba, w.rhs, lA);
+            solve_entry(ba, w.rhs, lds);
             PROF(6);
             TRC(8, trc_sum(w.rhs, (size_t)d.nj * d.nk, red));
             apply_F(d, w, w.rhs, w.dxa);
@@ -3023,7 +1909,7 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
 #ifndef QP_TRACE
         if (d.nk <= 36) {
             PROF(5);
-            solve_entry(ba, w.rhs, lA, SolveOut{w.dx, w.Lk, d.oq, 2, w.cpacc, w.rbase, io.sigma_mu});
+            solve_entry(ba, w.rhs, lds, SolveOut{w.dx, w.Lk, d.oq, 2, w.cpacc, w.rbase, io.sigma_mu});
             PROF(6);
         } else
 #endif
@@ -3033,7 +1919,7 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
             __syncthreads();
             PROF(5);
             TRC(11, trc_sum(w.rhs, (size_t)d.nj * d.nk, red));
-            solve_entry(ba, w.rhs, lA);
+            solve_entry(ba, w.rhs, lds);
             PROF(6);
             TRC(12, trc_sum(w.rhs, (size_t)d.nj * d.nk, red));
             apply_F(d, w, w.rhs, w.dx);
@@ -3097,8 +1983,8 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
         }
         rows_swept += 2 * nrows_free;
         row_bytes += bytes_iter, sweep_bytes += bytes_sweeps;
-        PROF(10);
-        PROF(11);
+        PROF(10);  // the fused step / neighbourhood / build sweeps
+        PROF(11);  // (slot of the separate update sweep they replaced: tools/qp_phase_profile.py still lists it, ~0)
     }
     if (!ok && nfar > 0) {  // the interior-point method failed on the reduced row set: once more with every row
         if (tid == 0) scal[SC_IPM_ITERS] += it_count, scal[SC_FLOPS] += flops, scal[SC_ROWS] += rows_swept;
@@ -3115,10 +2001,10 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
     }
     // ---- active-set polish
     if (S.p.polish && !polished) {
-        int acc = polish_entry(c, pw, lds, red2, flag2, 0);
+        int acc = polish_entry(c, pw, lds, red, flag, 0);
         if (acc == 3) {  // the dual active-set solve ran out of capacity: once more with the big factor in global memory
             __syncthreads();
-            acc = polish_entry(c, pw, lds, red2, flag2, 2);
+            acc = polish_entry(c, pw, lds, red, flag, 2);
         }
         polished = acc == 0 ? 1 : 0;
 #ifdef QP_POLSTATS

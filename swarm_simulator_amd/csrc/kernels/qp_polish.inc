@@ -1,4 +1,5 @@
-// qp_polish.inc — active-set polish ("crossover") of the interior-point answer, included by qp.hip.
+// qp_polish.inc — active-set polish ("crossover") of the interior-point answer: the algorithms.  Included by qp.hip, once, behind its factor /
+// solve entries; needs its records (qp_polish_types.inc), uni, uni_words (qp_base.inc) and row_pass, apply_F, apply_FT of qp.hip.
 //
 // Same mathematics as the CPU checker's polish, re-implemented for one workgroup (DESIGN.md "Polish"):
 //   candidates C  = rows with dominant multiplier or slack < 1e-6 at the interior-point iterate
@@ -12,88 +13,6 @@
 // multipliers >= 0); otherwise the interior-point answer stands.  It removes the O(sqrt(mu)) bias of the
 // interior-point answer in the weakly curved directions (reduced-Hessian condition number ~1e9).
 
-#if QP_POLISH_PART == 1
-// PL_NC (candidate rows) and PL_PMAX (rows simultaneously active in the dual solve) are defined in qp.hip
-
-struct Cand {
-    double n[3], t[3];  // row = sum_k n_k * (t . u_{a,k}) - [b >= 0] sum_k n_k * (t . u_{b,k})  at knot `knot`
-    double slack, snap_val;
-    double strength;  // z/s of the interior-point iterate (0 < . for candidates): warm start order of the dual solve
-    int row, knot, a, b, snap_idx, pad;
-};
-
-struct PolishWs {
-    Cand* cand;    // [PL_NC]
-    double* v0;    // [3][nred]  the gradient column K0^-1 F'(2Qx); then the gradient F'(2Qx) itself and the primal step's g + J_P' z
-    double* Sg;    // [PL_NC][PL_NC]
-    int* ncand;    // [4] counter, accepted flag, ...
-    double* Lbig;  // [PL_PBIG (PL_PBIG + 1) / 2] packed factor of the second, large-capacity attempt (global memory)
-    double* ptab;  // [6 PL_PBIG][4] primal step: the active rows listed per (agent, dim) -- knot and position in P, sgn n_k t[0..2]
-    // the mission's (k0_mission_tables): K0 depends on the segment times alone
-    double* k0f;   // [nj][18] factor of K0 in double (k0_factor_step), then two ints: the double / the dd factor met a pivot that is not positive
-    double* G;     // lower block triangle of K0^-1 (ipm::k0g_block)
-};
-// (the order follows polish_ws_doubles: what moves with the batch's nk comes last)
-__device__ __forceinline__ PolishWs polish_carve(double* p, int nj) {
-    PolishWs pw;
-    pw.k0f = p, p += 18 * (size_t)nj + 2;
-    pw.G = p, p += k0g_doubles(nj);
-    pw.cand = (Cand*)p, p += PL_NC * 14;
-    pw.Sg = p, p += polish_s_doubles(nj);
-    pw.ncand = (int*)p, p += 8;
-    pw.Lbig = p, p += lhp_size(PL_PBIG);
-    pw.ptab = p, p += 4 * 6 * PL_PBIG;
-    pw.v0 = p;
-    return pw;
-}
-
-#define WSYNC()                                             \
-    do {                                                    \
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                    \
-    } while (0)
-
-// (wave_red, the wave-wide reduction of a double, is qp.hip's; the same steps for an int)
-__device__ __forceinline__ int wave_min_int(int v) {
-    v = min(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false));
-    v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false));
-    v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false));
-    v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false));
-    return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-               min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-// the largest `best` of the wave and, among the lanes that hold it, the smallest index (-1: no lane has a candidate)
-__device__ __forceinline__ void wave_argmax(double& best, int& bidx) {
-    const double top = wave_red(bidx >= 0 ? best : -1e300, 1);
-    const int idx = wave_min_int(bidx >= 0 && best == top ? bidx : 0x7fffffff);
-    best = top, bidx = idx == 0x7fffffff ? -1 : idx;
-}
-
-__device__ __forceinline__ void knot_of(const QpDims& d, const QpWs& w, int j6, int& knot, double t[3]) {
-    const int m = j6 / 6, i = j6 % 6;
-    if (i < 3) {
-        knot = m;
-        t[0] = t[1] = t[2] = 0;
-        t[i] = 1;
-    } else {
-        knot = m + 1;
-        const double* L = w.Lk + 9 * (m + 1) + 3 * (i - 3);
-        t[0] = L[0], t[1] = L[1], t[2] = L[2];
-    }
-}
-
-__device__ __forceinline__ void emit_cand(const QpDims& d, const QpWs& w, const PolishWs& pw, size_t r, int j6, int a, int b, double n0,
-                                          double n1, double n2, double slack, int snap_idx, double snap_val, double strength) {
-    const int idx = atomicAdd(pw.ncand, 1);
-    if (idx >= PL_NC) return;
-    Cand& c = pw.cand[idx];
-    c.n[0] = n0, c.n[1] = n1, c.n[2] = n2;
-    knot_of(d, w, j6, c.knot, c.t);
-    c.slack = slack, c.snap_val = snap_val, c.strength = strength;
-    c.row = (int)r, c.a = a, c.b = b, c.snap_idx = snap_idx, c.pad = 0;
-}
-
-#else  // part 2: algorithms (needs row_pass, wave_factor, apply_F, apply_FT)
 // which (agent, dim) subsystems of K0 a candidate row lives in: agents a | (b + 1) << 8, dims << 16
 __device__ __forceinline__ int cand_meta(const Cand& c) {
     return c.a | ((c.b + 1) << 8) | ((c.n[0] != 0.0) << 16) | ((c.n[1] != 0.0) << 17) | ((c.n[2] != 0.0) << 18);
@@ -689,7 +608,7 @@ __device__ __forceinline__ int polish_qp(RowCtx& c, PassIO& io, const PolishWs& 
         PPROF(1);
         // ---- dual active-set solve (wave 0)
         if (tid < 64) {
-            __builtin_amdgcn_s_setprio(QP_CHAIN_PRIO);  // one wave, one dependent chain (see twisted_factor in qp.hip)
+            __builtin_amdgcn_s_setprio(QP_CHAIN_PRIO);  // one wave, one dependent chain (see twisted_factor in qp_wave_factor.inc)
             const int res_nP = (outer > 0 && nP > 0) ? nP : -1;
 #ifdef QP_LHSTATS
             const int r = lh_wave(n, Suse, ldS, dv, zc, tv, yv, wv, P, inP, banned, Lc, sint + 2, pmax, str, big, c.scal + 20, res_nP, n_prev);
@@ -840,21 +759,7 @@ __device__ __forceinline__ int polish_qp(RowCtx& c, PassIO& io, const PolishWs& 
     return 0;
 }
 
-// stand-alone entry (own copy of the row context, own reduction scratch): see BlkArgs in qp.hip
-// every 32-bit word of a by-value argument through v_readfirstlane: see blk_unpack in qp.hip (wave-uniform arguments into scalar registers)
-template <class T>
-__device__ __forceinline__ T uni_words(const T& v) {
-    static_assert(sizeof(T) % 4 == 0, "whole words");
-    union U {
-        T t;
-        unsigned wd[sizeof(T) / 4];
-        __device__ U() {}
-    } in, out;
-    in.t = v;
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(T) / 4; ++i) out.wd[i] = __builtin_amdgcn_readfirstlane(in.wd[i]);
-    return out.t;
-}
+// stand-alone entry (own copy of the row context, own reduction scratch): see BlkArgs and uni_words in qp_base.inc
 __device__ __noinline__ int polish_entry(RowCtx c_in, PolishWs pw_in, double* lds, double* red, int* flag, int mode) {
     PassIO io = {};
     RowCtx c = uni_words(c_in);
@@ -862,4 +767,3 @@ __device__ __noinline__ int polish_entry(RowCtx c_in, PolishWs pw_in, double* ld
     c.pw = &pw;
     return polish_qp(c, io, pw, uni(lds), uni(red), uni(flag), uni(mode));
 }
-#endif

@@ -11,7 +11,7 @@
 //   sfc_count [K][N] i32  sfc_box [K][N][MB][6] f64  sfc_time [K][N][MB] f64
 //   rsfc_normal [K][N(N-1)/2][M][3] f32 (871 KB)   rsfc_time [K][M] f64
 //   ctrl / coef [K][N][3][6M] f64 (332 KB each)
-//   QP workspace per mission (see qp.hip)
+//   QP workspace per mission (see QpWs in qp_base.inc)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -208,7 +208,7 @@ size_t corridor_lds_bytes(const DevSession& s);  // dynamic LDS of sfc_kernel fo
 // + timeScale behind it
 void launch_planner_prologue(const DevSession& s, hipStream_t st);
 void launch_planner_epilogue(const DevSession& s, hipStream_t st);
-// kernels/qp.hip is built twice: _w2 = 256 VGPRs, one workgroup per CU; _w4 = 128 VGPRs, two workgroups per CU
+// kernels/qp.hip is built twice, both with 256 VGPRs: _w2 = 512 threads, one workgroup per CU; _w4 = 256 threads, two workgroups per CU
 void launch_planner_w2(const DevSession& s, void* qp_ws, size_t qp_ws_bytes_per_mission, hipStream_t st);
 void launch_planner_w4(const DevSession& s, void* qp_ws, size_t qp_ws_bytes_per_mission, hipStream_t st);
 size_t planner_workspace_bytes_w2(int N, int M, int batch_size_eff);

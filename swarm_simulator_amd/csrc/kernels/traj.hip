@@ -2,7 +2,7 @@
 //
 // Replaces the parts of RBPPlanner::update (reference: swarm_planner/include/rbp_planner.hpp:33-84) that are not the QP: build_dummy
 // :513-549, the Bernstein->monomial loop :167-196, timeScale :209-266.  Every planner path launches them through launch_planner_prologue /
-// launch_planner_epilogue: the batch QP in its three schedules (kernels/qp.hip) and the grid-wide joint QP (kernels/jqp.hip, from
+// launch_planner_epilogue: the batch QP (kernels/qp.hip) and the grid-wide joint QP (kernels/jqp.hip, from
 // abi/session.hip).  Nothing here depends on how qp.hip is built; the file is compiled once.
 #include <algorithm>
 
