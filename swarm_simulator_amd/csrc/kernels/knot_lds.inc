@@ -735,3 +735,44 @@ __device__ __forceinline__ double kl_inverse_rows(double (&m)[NK], const kl_lds*
         return dinv;
     }
 }
+
+#include "knot_subst.h"
+// ---- a substitution step out of the chain's own area (fused path; qp.hip: QP_FWD_IN_FACTOR, the predictor's forward pass) -----------------
+// When the companion has announced M_jp (Mdone) the chain's own area holds all a forward step of knot jp needs: M_jp in MX -- rows of
+// stride KL_LD, zeros left of the diagonal (kl_tiles_scatter): the layout of a stage buffer of solve_staged --, 1 / d_jp in I, and on the
+// fused path neither is written again before the chain's factorisation of its NEXT block (I) and the companion's scatter behind it (MX).
+// The step (knot_subst.h, the one solve_staged takes: same operations, same order, same M bits) runs behind the update of the next block,
+// in front of the wait for that block's image, which it fills.  z_jp goes to global memory (z_out: this lane's entry).
+// Where the step's small vectors live (KfSlots, doubles from KlArea::C):
+//   * The panel images end at kp_img_total(NK); the C / U region is (NK + 1) KL_LDU doubles, and on the fused path nothing else is kept
+//     in it (U does not exist, the scatter's padding lands in row NK of MX).  Its tail [PAD, CSZ) is written by nobody but these steps and
+//     was cleared by the caller at the start of the factorisation (twisted_factor): the zeros behind A and in front of Z (the products read A[NK .. 3 CH - 1] and Z[NK - 3 CH .. -1]; one
+//     run of 10 serves both), then Z and V -- V is what travels from step to step and on to the middle block --, then zeros up to CSZ,
+//     which is where the product by rows reads the up to 9 doubles in front of MX.  (Columns 36, 37 of MX's rows are never written: zeros.)
+//   * A (r') and the 64 partial sums overlay the END OF THE LAST PANEL IMAGE.  That is idle in the window: the companion has read every
+//     image of block jp before its scatter, hence before it announced Mdone (kl_inverse_rows: kl_inverse_panels, kl_tiles_scatter, publish;
+//     behind the announcement it only reads MX), and the next writer of the images is this wave's factorisation of the next block, in
+//     program order behind the step.  Nothing outlives the step there.
+//   * The product by columns would read rows NK + 1 .. 3 CH - 1 behind MX: I (finite), then the next area, the progress words, the
+//     assembly images -- not this wave's to vouch for: ks_matvec_cols<NK, GUARD = true> drops those terms.
+// No branch inside the step: lanes >= NK compute row 0's values (rr = 0 throughout) and store them where lane 0 does.
+template <int NK>
+__device__ __forceinline__ void kl_forward_step(kl_lds* base, __attribute__((address_space(1))) double* z_out, double rhs_r, double e0, double e1, double e2, int r) {
+    using A = KlArea<NK>;
+    using F = KfSlots<NK>;
+    static_assert(F::CSZ == A::CSZ, "knot_subst.h out of step with KlArea");
+    kl_lds *C = base + A::C, *MX = base + A::MX, *I = base + A::I;
+    const int rr = r < NK ? r : 0, g3 = 3 * (rr / 3);
+    ks_step_forward<NK, true>((const kl_lds*)MX, I[rr], rhs_r, true, e0, e1, e2, C + F::A, C + F::Z, C + F::V, C + F::PS, r, g3, rr, [] { kl_sync(); },
+                              [&](double z) { *z_out = z; });
+}
+// the middle block's step out of the area `base` that holds M_mid and 1 / d_mid: v = rhs_mid[rr] less both chains' coupling terms (their last
+// v: the V slots of their areas); returns x_mid[rr].  A, Z and the partial sums: base's slots (the middle block's images have been read)
+template <int NK>
+__device__ __forceinline__ double kl_middle_step(kl_lds* base, double v, int r) {
+    using A = KlArea<NK>;
+    using F = KfSlots<NK>;
+    kl_lds* C = base + A::C;
+    const int rr = r < NK ? r : 0;
+    return ks_step_middle<NK, true>((const kl_lds*)(base + A::MX), (const kl_lds*)(base + A::I + rr), v, C + F::A, C + F::Z, C + F::PS, r, rr, [] { kl_sync(); });
+}

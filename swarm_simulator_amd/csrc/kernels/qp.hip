@@ -104,6 +104,27 @@
 #ifndef QP_MID_FOLLOW
 #define QP_MID_FOLLOW (QP_THREADS >= 512)  // see wave_factor_mid
 #endif
+// The predictor's forward substitution carried along the factorisation (blocks on the fused path, i.e. of order 36): a chain wave takes the
+// forward step of the block it has just factorised out of its own LDS area -- M_jp in MX, 1 / d_jp in I -- between the update of the next
+// block and the wait for that block's image, the middle block's step follows its factorisation, and the predictor's solve_staged runs the
+// backward steps only (SolveOut::rhs_mode 3): 18 of its 35 step barriers and one of the four stagings of every M_j go.  kl_forward_step
+// (knot_lds.inc) has the details.  A/B against the parent on one box, builds alternating (profiles/fwd_in_factor_ab.txt): planner stage at
+// 2000 missions 615.7 -> 608.4 ms in every one of three passes, one mission alone 77.07 -> 75.26 ms, the 50-mission sweep 103.1 -> 102.0 ms,
+// control points bit for bit the same.  The chain timers say the step does NOT hide in the wait for the image (3.4 us per step under load,
+// mostly waiting for its own four global loads): the gain is what the solve loses.  The trace build compares the right-hand sides of the
+// full substitution: off there.
+#ifndef QP_FWD_IN_FACTOR
+#ifdef QP_TRACE
+#define QP_FWD_IN_FACTOR 0
+#else
+#define QP_FWD_IN_FACTOR 1  // both builds: profiles/fwd_in_factor_ab.txt
+#endif
+#endif
+#if QP_FWD_IN_FACTOR && KL_FUSED_UPDATE && KL_PANEL && KL_PANEL_MIN_NK <= 36  // (kl_fused_path(36) for the preprocessor: the lever's lines of the kernel body)
+#define QP_FWD36 1
+#else
+#define QP_FWD36 0
+#endif
 #ifndef QP_EARLY_TRIES
 #define QP_EARLY_TRIES 2
 #endif
@@ -1718,9 +1739,17 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
     int* flag = (int*)(lds_raw + 16);
     double* lds = lds_raw + 32;
 #ifdef QP_PROFILE
+#if QP_FWD36
+    const BlkArgs ba{d.nk, d.nj, d.ldb, c.lds_avail, w.Td, w.To, w.Lf, w.Ek, scal, w.rhs};
+#else
     const BlkArgs ba{d.nk, d.nj, d.ldb, c.lds_avail, w.Td, w.To, w.Lf, w.Ek, scal};
+#endif
+#else
+#if QP_FWD36
+    const BlkArgs ba{d.nk, d.nj, d.ldb, c.lds_avail, w.Td, w.To, w.Lf, w.Ek, nullptr, w.rhs};
 #else
     const BlkArgs ba{d.nk, d.nj, d.ldb, c.lds_avail, w.Td, w.To, w.Lf, w.Ek, nullptr};
+#endif
 #endif
 
     PROF_DECL;
@@ -1773,7 +1802,13 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
     // substitutions), plus the reciprocal pivots: 5 triangles + 5 nk.  (Until round 6 the model also counted T_j written and read as a
     // triangle -- 7 triangles -- which both builds have stopped doing: the blocks are assembled just in time into LDS images and never
     // reach global memory, so those bytes are no longer part of what the algorithm has to move.)
+    // (QP_FWD_IN_FACTOR, blocks of order 36: the predictor's forward pass reads M_j where the factorisation left it in LDS and its middle block
+    // is not staged either: 4.5 triangles + 4.5 nk on average -- bookkeeping of what is moved, not a gain of its own)
+#if QP_FWD36
+    const double blk_doubles = d.nk == 36 ? 4.5 * (d.nk * (d.nk + 1) / 2) + 4.5 * d.nk : (d.nk < 36 ? 5.0 * (d.nk * (d.nk + 1) / 2) + 5.0 * d.nk : 8.0 * d.ldb * d.ldb);
+#else
     const double blk_doubles = d.nk <= 36 ? 5.0 * (d.nk * (d.nk + 1) / 2) + 5.0 * d.nk : 8.0 * d.ldb * d.ldb;
+#endif
     const double bytes_sweeps = 88.0 * frozen_free_rows + 64.0 * (double)(d.oq - 6) * (6.0 * d.nb + 2.0 * d.npb) + 288.0 * (double)d.nb * (d.oq - 6);
     const double bytes_iter = bytes_sweeps + 8.0 * (double)d.nj * blk_doubles;
     const PolishWs pw = polish_carve(w.polish, d.nj);
@@ -1854,6 +1889,11 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
             assemble_blocks(c, lds);
         else if (ASM_HELPERS == 0 && !QP_FOLLOW_ASM)
             assemble_blocks_lds(asm_args(c), d.nj, lds);  // (256-thread build, round 6: the chains' companion waves assemble just in time instead)
+        // QP_FWD_IN_FACTOR: the predictor's right-hand side is known now -- rbase + F'G'v of the build sweep's accumulators, the arithmetic the
+        // rhs_mode 1 prologue of solve_staged repeats -- and the chains consume it block by block while they factorise
+#if QP_FWD36
+        if (d.nk == 36) rhs_from_acc(c, false, 0.0);
+#endif
         PROF(3);
         __threadfence_block();
         __syncthreads();
@@ -1874,7 +1914,11 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
         if (d.nk <= 36) {
             PROF(5);
             // (fused: starts with rhs_from_acc into the LDS vector; ends with apply_F from it, fence and barrier -- see SolveOut)
+            #if QP_FWD36
+            solve_entry(ba, w.rhs, lds, SolveOut{w.dxa, w.Lk, d.oq, d.nk == 36 ? 3 : 1, w.cpacc, w.rbase, 0.0});  // (3: z_j and x_mid are in w.rhs, backward steps only)
+#else
             solve_entry(ba, w.rhs, lds, SolveOut{w.dxa, w.Lk, d.oq, 1, w.cpacc, w.rbase, 0.0});
+#endif
             PROF(6);
         } else
 #endif

@@ -186,6 +186,9 @@ struct BlkArgs {
     double *Td, *To, *Lf;
     double* Ek;
     double* prof;
+#if QP_FWD36
+    double* rhs;  // QP_FWD_IN_FACTOR: the chains read the predictor's right-hand side and leave z_j / x_mid there (QpWs::rhs)
+#endif
 };
 // Arguments of a non-kernel function arrive in VECTOR registers, and the compiler treats them as divergent: every pointer, dimension and
 // address derived from them would live in VGPRs for the whole function -- that is what spills inside the knot
@@ -203,6 +206,9 @@ __device__ __forceinline__ void blk_unpack(const BlkArgs& b, QpDims& d, QpWs& w)
     w = QpWs{};
     d.nk = uni(b.nk), d.nj = uni(b.nj), d.ldb = uni(b.ldb), d.ld = d.nk + 1;
     w.Td = uni(b.Td), w.To = uni(b.To), w.Lf = uni(b.Lf), w.Ek = uni(b.Ek), w.prof = uni(b.prof);
+#if QP_FWD36
+    w.rhs = uni(b.rhs);  // (every other pointer of QpWs stays null in the stand-alone functions)
+#endif
 }
 // the same for a whole struct passed by value (polish_entry): every 32-bit word of it through v_readfirstlane
 template <class T>

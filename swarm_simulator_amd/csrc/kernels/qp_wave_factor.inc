@@ -177,7 +177,8 @@ __device__ __forceinline__ void knot_inverse(const QpWs& w, int j, kl_lds* base,
 }
 
 // chain-side timers of the left chain (-DQP_PROFILE; 100 MHz clock, like the phase timers): SC 25 = the rank-NK update, 26 = waiting for the block
-// assembly, 27 = the knot itself (T into the tiles, factorisation, waiting for M; without the fused update also the coupling rows).
+// assembly, 27 = the knot itself (T into the tiles, factorisation, waiting for M; without the fused update also the coupling rows),
+// 29 = the forward substitution steps taken along the way (QP_FWD_IN_FACTOR; slot 28 is SC_SWEEP_BYTES).
 // They must not change what they measure: the time stamp is wave-uniform and stays in scalar registers, a step adds its difference to a
 // 64-bit LDS word behind the progress words (cleared with them at the start of a factorisation; every lane adds, all but lane 0 of the left
 // chain add zero: no branch inside the step), and the three sums go to global memory once per factorisation (CHAIN_FLUSH).
@@ -195,6 +196,7 @@ __device__ __forceinline__ void knot_inverse(const QpWs& w, int j, kl_lds* base,
         kl_sync();                                                                                      \
         if (w.prof && dir > 0 && r == 0)                                                                \
             for (int k_ = 25; k_ < 28; ++k_) w.prof[k_] += (double)(long long)*CHAIN_TW(cnt, k_);       \
+        if (QP_FWD_IN_FACTOR && w.prof && dir > 0 && r == 0) w.prof[29] += (double)(long long)*CHAIN_TW(cnt, 29); \
     } while (0)
 #else
 #define CHAIN_T0
@@ -207,6 +209,24 @@ __device__ __forceinline__ void knot_inverse(const QpWs& w, int j, kl_lds* base,
 // 512-thread build: [h] = number of blocks chain h has read out of the assembling waves' LDS images (a wave may overwrite its image of
 // step i - 2 when this says i - 1)
 #define ASM_CONSUMED(cnt, h) ((kl_ldsi*)((cnt) + 72 + (h)))
+
+// ---- the predictor's forward substitution along the factorisation (QP_FWD_IN_FACTOR; blocks on the fused path): kl_forward_step and
+// kl_middle_step of knot_lds.inc, which has the argument for where the step's vectors live.  z_jp goes to QpWs::rhs, where solve_staged's
+// backward-only mode (SolveOut::rhs_mode 3) finds it.
+static_assert((QP_FWD36 != 0) == (QP_FWD_IN_FACTOR && kl_fused_path(36)), "QP_FWD36 (qp.hip) out of step with kl_fused_path");
+// rhs_r, e0 .. e2: rhs_jp[rr] and row rr of T_{jp,jpp} (zeros for a chain's first block), loaded by the caller a block ahead
+template <int NK>
+__device__ __forceinline__ void wave_forward_step(const QpWs& w, kl_lds* base, int jp, double rhs_r, double e0, double e1, double e2, int r) {
+    kl_forward_step<NK>(base, QG(w.rhs) + (size_t)jp * NK + (r < NK ? r : 0), rhs_r, e0, e1, e2, r);
+}
+// what the caller loads for the step of block j, right after it has factorised it (global loads, see coupling_coef)
+template <int NK>
+__device__ __forceinline__ void wave_forward_fetch(const QpWs& w, int j, int dir, bool first, int r, double& rhs_r, double& e0, double& e1, double& e2) {
+    const int rr = r < NK ? r : 0;
+    rhs_r = QGC(w.rhs)[(size_t)j * NK + rr];
+    coupling_coef(w, first ? j : j - dir, dir, rr, e0, e1, e2);  // (first block: a valid address, T_{j+dir,j}; its coefficients become zeros)
+    e0 = first ? 0.0 : e0, e1 = first ? 0.0 : e1, e2 = first ? 0.0 : e2;
+}
 
 // one chain: blocks j0, j0+dir, ... (count of them).  The chain wave factorises; its companion wave (wave_factor_follow) computes
 // M_j = L_j^-T a column or two (panel path: one panel of 4 columns) behind and stores it.  On return the chain's LDS area holds the coupling factor X towards the middle
@@ -227,6 +247,7 @@ __device__ __forceinline__ bool wave_factor_chain(const QpDims& d, const QpWs& w
         // S_j is formed in the tiles: -X_j D_jp^-1 X_j' from M_jp (MX: the companion's rows, which this wave no longer overwrites) as soon as the
         // companion has announced them, still in front of the wait for T_j's image; then T_j, then the factorisation.  No coupling rows.
         double cf[KlPanels<NK>::NT][3];
+        [[maybe_unused]] double f_rhs = 0, f_e0 = 0, f_e1 = 0, f_e2 = 0;  // QP_FWD_IN_FACTOR: what the forward step of the block just factorised starts from
         for (int i = 0, j = j0; i < count; ++i, j += dir) {
             CHAIN_T0;
             kl_d4 s[KlPanels<NK>::TILES];
@@ -237,6 +258,12 @@ __device__ __forceinline__ bool wave_factor_chain(const QpDims& d, const QpWs& w
                 kl_fused_update<NK>(s, MX, I, r, cf);
             }
             CHAIN_T(25);
+            if (QP_FWD_IN_FACTOR) {
+                // the forward step of block i - 1, out of MX / I, into the wait for block i's image (wave_forward_step).  Its store of z is a
+                // block's factorisation ahead of the next wait on the memory counter (the update's coefficients, one iteration on)
+                if (i > 0) wave_forward_step<NK>(w, base, j - dir, f_rhs, f_e0, f_e1, f_e2, r);
+                CHAIN_T(29);
+            }
             if (QP_FOLLOW_ASM)
                 kl_await(ASMF_READY(cnt, h), i + 1, seen_img);
             else
@@ -247,10 +274,20 @@ __device__ __forceinline__ bool wave_factor_chain(const QpDims& d, const QpWs& w
                                  : QP_FOLLOW_ASM ? (const kl_lds*)(ldsW - (size_t)h * A::SIZE + 2 * A::SIZE + 128 + (size_t)h * ASML_DOUBLES(NK, (NK / 9)))
                                                  : nullptr;
             if (!knot_ldl_add<NK>(w, j, s, base, r, P, i * (NK + 1), Timg, ASM_CONSUMED(cnt, h), i + 1)) ok = false;
+            // (the step's four loads leave here, not earlier: they are not live across the panel loop, and have the companion's last panel
+            // and the next block's update to land)
+            if (QP_FWD_IN_FACTOR) wave_forward_fetch<NK>(w, j, dir, i == 0, r, f_rhs, f_e0, f_e1, f_e2);
             CHAIN_T(27);
         }
+        if (QP_FWD_IN_FACTOR) {  // the chain's last block: its M has to be waited for here (count > 0: see the callers)
+            CHAIN_T0;
+            kl_await(Mdone, count, seen);
+            CHAIN_T(27);
+            wave_forward_step<NK>(w, base, j0 + (count - 1) * dir, f_rhs, f_e0, f_e1, f_e2, r);
+            CHAIN_T(29);
+        }
         CHAIN_FLUSH();
-        return ok;  // (the last block's M is waited for by the workgroup barrier in front of wave_factor_mid)
+        return ok;  // (lever off: the last block's M is waited for by the workgroup barrier in front of wave_factor_mid)
     }
     for (int i = 0, j = j0; i < count; ++i, j += dir) {
         CHAIN_T0;
@@ -329,6 +366,33 @@ __device__ __forceinline__ bool wave_factor_mid(const QpDims& d, const QpWs& w, 
     if (!QP_MID_FOLLOW) {
         int seen = 0;
         knot_inverse<NK, false>(w, mid, bl, r, act, scratch, 0, seen, scratch, 0);
+    }
+    if constexpr (QP_FWD_IN_FACTOR && kl_fused_path(NK)) {
+        // The middle step of the predictor's substitution (the s == SF body of solve_staged): forward with both chains' last v -- each in
+        // the V slot of its chain's area (KfSlots; the right chain's made visible by the workgroup barrier in front of this function; zeros
+        // where there is no chain) --, then backward, out of M_mid in the left area's MX and 1 / d_mid in its I.  x_mid goes to QpWs::rhs.
+        // A, Z and the partial sums: the left area's slots -- the middle block's images have been read (above, or by the companion before its
+        // announcement), and the left chain's own last step is over.
+        using F = KfSlots<NK>;
+        if (QP_MID_FOLLOW) {  // M_mid comes from the left chain's companion (twisted_factor)
+            int seen = 0;
+            kl_await(scratch + 1, 1, seen);
+        }
+        const kl_lds *V0 = bl + A::C + F::V, *V1 = br + A::C + F::V;
+        const int g3 = 3 * (rr / 3);
+        double v = QGC(w.rhs)[(size_t)mid * NK + rr];
+        if (mid > 0) {
+            double e0, e1, e2;
+            coupling_coef(w, mid - 1, +1, rr, e0, e1, e2);
+            v -= e0 * V0[g3] + e1 * V0[g3 + 1] + e2 * V0[g3 + 2];
+        }
+        if (mid + 1 < d.nj) {
+            double e0, e1, e2;
+            coupling_coef(w, mid + 1, -1, rr, e0, e1, e2);
+            v -= e0 * V1[g3] + e1 * V1[g3 + 1] + e2 * V1[g3 + 2];
+        }
+        const double x = kl_middle_step<NK>(bl, v, r);
+        QG(w.rhs)[(size_t)mid * NK + rr] = x;
     }
     return ok;
 }

@@ -12,80 +12,9 @@
 // waves 0 / 1 run step s of the left / right chain.  rhs -> z -> x lives in LDS throughout (vec).
 // ROLE: 0 = compiled for the two chain waves, 1 = for the staging waves (2..): two __noinline__ functions (solve_entry_*), so that the
 // staging waves -- a dozen registers -- have no prologue saving callee-saved VGPRs.
-// The two products of a chain step use M_j's triangle with ALL 64 lanes: a lane owns a PIECE -- KsPieces::CH consecutive terms of one row
-// (or column) -- instead of a whole row, of which only NK <= 36 exist and whose lower half is zeros: 15 loads and multiply-adds per
-// lane instead of 36, then the up to three pieces of a row meet through 64 doubles of LDS.  Chunk t of the product by rows covers the
-// columns NK - CH (t + 1) .. NK - 1 - CH t (anchored at the right edge: row r needs the chunks with NK - 1 - CH t >= r), chunk t of the
-// product by columns the rows CH t .. CH t + CH - 1 (anchored at the top: column c needs the chunks with CH t <= c).  Terms that fall
-// left of / below the diagonal multiply the stage buffers' zeros, terms outside the block multiply the zero padding of the VECTOR (KS_VPAD
-// slots either side; whatever finite number sits at the matrix address): no masks, no branches.
-#define KS_VPAD 16                       // zero slots either side of a chain vector
-#define KS_VLEN (KS_VPAD + KL_I + KS_VPAD)  // doubles per vector (the slot NK + 12 takes the writes of the lanes without a row)
-template <int NK>
-struct KsPieces {
-    static constexpr int CH = (NK * 15 + 35) / 36;  // 36 -> 15, 27 -> 12, 18 -> 8, 9 -> 4
-    static constexpr int N0 = NK, N1 = NK - CH > 0 ? NK - CH : 0, N2 = NK - 2 * CH > 0 ? NK - 2 * CH : 0;
-    static_assert(NK - 3 * CH <= 0 && N0 + N1 + N2 <= 64, "three chunks, one wavefront");
-    static_assert(3 * CH - NK <= KS_VPAD && 3 * CH - 1 - (NK - 1) <= KS_VPAD, "vector padding");
-    __device__ static __forceinline__ void of_lane(int lane, int& idx, int& t) {
-        t = lane < N0 ? 0 : (lane < N0 + N1 ? 1 : 2);
-        idx = lane < N0 ? lane : (lane < N0 + N1 ? lane - N0 : (lane < N0 + N1 + N2 ? lane - N0 - N1 : 0));
-    }
-};
-// sum_k Mst[k][c] * b[k] for column c = rr (lanes rr < NK; b: vector base, i.e. entry 0); psum: 64 doubles of scratch
-template <int NK>
-__device__ __forceinline__ double kl_matvec_cols(const kl_lds* Mst, const kl_lds* b, kl_lds* psum, int lane) {
-    using P = KsPieces<NK>;
-    int idx, t;
-    P::of_lane(lane, idx, t);
-    const int k0 = P::CH * t, c = k0 + idx;
-    const kl_lds* mp = Mst + k0 * KL_LD + c;
-    const kl_lds* bp = b + k0;
-    double mv[P::CH], bv[P::CH];
-#pragma unroll
-    for (int j = 0; j < P::CH; ++j) mv[j] = mp[j * KL_LD], bv[j] = bp[j];
-    double s0 = 0, s1 = 0, s2 = 0;
-#pragma unroll
-    for (int j = 0; j < P::CH; ++j) {
-        if (j % 3 == 0) s0 += mv[j] * bv[j];
-        if (j % 3 == 1) s1 += mv[j] * bv[j];
-        if (j % 3 == 2) s2 += mv[j] * bv[j];
-    }
-    psum[lane] = (s0 + s1) + s2;
-    kl_sync();
-    const int cc = lane < NK ? lane : 0;
-    double r = psum[cc];
-    if (P::N1 > 0) r += cc >= P::CH ? psum[P::N0 + cc - P::CH] : 0.0;
-    if (P::N2 > 0) r += cc >= 2 * P::CH ? psum[P::N0 + P::N1 + cc - 2 * P::CH] : 0.0;
-    return r;
-}
-// sum_k Mst[r][k] * b[k] for row r = rr
-template <int NK>
-__device__ __forceinline__ double kl_matvec_rows(const kl_lds* Mst, const kl_lds* b, kl_lds* psum, int lane) {
-    using P = KsPieces<NK>;
-    int idx, t;
-    P::of_lane(lane, idx, t);
-    const int k0 = NK - P::CH * (t + 1);  // may be negative: the vector is padded, the matrix address holds some finite number
-    const kl_lds* mp = Mst + idx * KL_LD + k0;
-    const kl_lds* bp = b + k0;
-    double mv[P::CH], bv[P::CH];
-#pragma unroll
-    for (int j = 0; j < P::CH; ++j) mv[j] = mp[j], bv[j] = bp[j];
-    double s0 = 0, s1 = 0, s2 = 0;
-#pragma unroll
-    for (int j = 0; j < P::CH; ++j) {
-        if (j % 3 == 0) s0 += mv[j] * bv[j];
-        if (j % 3 == 1) s1 += mv[j] * bv[j];
-        if (j % 3 == 2) s2 += mv[j] * bv[j];
-    }
-    psum[lane] = (s0 + s1) + s2;
-    kl_sync();
-    const int rr = lane < NK ? lane : 0;
-    double r = psum[rr];
-    if (P::N1 > 0) r += rr < P::N1 ? psum[P::N0 + rr] : 0.0;
-    if (P::N2 > 0) r += rr < P::N2 ? psum[P::N0 + P::N1 + rr] : 0.0;
-    return r;
-}
+// The step bodies and their two products (KsPieces: a lane owns a piece of a row or column) are stated in knot_subst.h, for this file,
+// for the forward steps the chain waves take along the factorisation (QP_FWD_IN_FACTOR, qp_wave_factor.inc) and for the host.
+#include "knot_subst.h"
 
 template <int NK>
 struct KsLayout {  // doubles
@@ -102,6 +31,9 @@ struct SolveOut {
     const double* Lk;  // QpWs::Lk
     int oq;
     // ... and the right-hand side (rhs_from_acc) can be formed straight into that LDS vector: rhs_mode 1 = predictor, 2 = corrector, 0 = read rhs
+    // 3 (QP_FWD_IN_FACTOR, blocks on the fused path): BACKWARD ONLY -- the chains took the forward steps and the middle block along the
+    // factorisation (wave_forward_step, wave_factor_mid): rhs holds z_j and x_mid; both chains' V start as x_mid, the steps SF + 1 .. 2 SF run,
+    // and only their blocks are staged
     int rhs_mode = 0;
     const double* cpacc = nullptr;  // QpWs::cpacc
     const double* rbase = nullptr;  // QpWs::rbase
@@ -114,10 +46,13 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
     const int tid = threadIdx.x, nj = d.nj, mid = twist_mid(nj);
     const int nl = mid, nr = nj - 1 - mid, SF = nl > nr ? nl : nr;
     const int nsteps = 2 * SF + 1;  // SF forward steps, the middle block, SF backward steps
+    constexpr bool FWD = QP_FWD_IN_FACTOR && kl_fused_path(NK);  // (only then can rhs_mode be 3)
+    const bool bwd_only = FWD && so.rhs_mode == 3;
+    const int s_first = bwd_only ? SF + 1 : 0;  // first step of this call
     lds += KS::LEAD;                                   // (zero-filled with the stage buffers below)
     kl_lds* vec = (kl_lds*)(lds + QP_STAGE_BUFS * STG);  // nj*NK: rhs -> z -> x  (LDS pointers: through generic ones every access is a flat instruction)
     kl_lds* small = vec + ((nj * NK + 1) & ~1);        // [2 chains][A, Z, V][KS_VLEN], then [2 chains][64] partial sums
-    if (so.rhs_mode) {  // rhs_from_acc into the LDS vector (same arithmetic): rhs = rbase + F'(G'v) of the sweep's accumulators
+    if (FWD ? so.rhs_mode == 1 || so.rhs_mode == 2 : so.rhs_mode != 0) {  // rhs_from_acc into the LDS vector (same arithmetic): rhs = rbase + F'(G'v) of the sweep's accumulators
         constexpr int nu = NK / 3;
         const int oq = so.oq;
         const size_t ncp = (size_t)(NK / 9) * oq;
@@ -177,6 +112,7 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
     }
     for (int i = tid; i < KS::LEAD + QP_STAGE_BUFS * STG; i += QP_THREADS) (lds - KS::LEAD)[i] = 0.0;
     __syncthreads();
+    if (bwd_only && tid < NK) small[KS_VPAD + 2 * KS_VLEN + tid] = small[KS_VPAD + 5 * KS_VLEN + tid] = vec[mid * NK + tid];  // x_mid into both chains' V
     auto stage = [&](int s, double* buf) {
         const int jl = left_j(s), jr = right_j(s);
         const double* srcl = w.Lf + (size_t)(jl >= 0 ? jl : 0) * KF_STRIDE(NK);
@@ -222,7 +158,7 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
         }
     };
     if (ROLE == 1)
-        for (int s0 = 0; s0 < QP_STAGE_BUFS - 1 && s0 < nsteps; ++s0) stage(s0, lds + s0 * STG);
+        for (int s0 = s_first; s0 < s_first + QP_STAGE_BUFS - 1 && s0 < nsteps; ++s0) stage(s0, lds + (bwd_only ? s0 % QP_STAGE_BUFS : s0) * STG);
     __syncthreads();
     const int wave = ROLE == 0 ? (tid >> 6) & 1 : 2, r = tid & 63;  // (role 1 only needs "wave >= 2")
     const bool act = r < NK;
@@ -246,7 +182,7 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
         }
     };
     double cf0, cf1, cf2;
-    step_coef(0, cf0, cf1, cf2);
+    step_coef(s_first, cf0, cf1, cf2);
 #ifdef QP_SOLVE_TIMERS  // developer build: left chain wave, SC 25 = work of the steps, 26 = waiting at the step barrier (staging wave: 29 / 30, right chain: 33 / 34)
     long long st_ = wall_clock64();
 #define SOLVE_T(slot)                                                              \
@@ -263,7 +199,7 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
         constexpr int R = QP_STAGE_REGS > 0 ? QP_STAGE_REGS : 1;
         double tq[R][MAXE];
 #pragma unroll
-        for (int k = 0; k < R; ++k) stage_load(QP_STAGE_BUFS - 1 + k, tq[k]);
+        for (int k = 0; k < R; ++k) stage_load(s_first + QP_STAGE_BUFS - 1 + k, tq[k]);
         // steady state, straight-line (no predicate, no branch between a load and its store: only then does the compiler count the loads in
         // flight instead of waiting for all of them): every element is stored -- the ones a thread does not have go to a padding column
         // nobody's products see (row 0, column KL_LD - 1, times the zero padding of the vectors), a chain that idles at a step gets knot 0's
@@ -276,7 +212,7 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
         // compiler drains the memory counter completely wherever a loop-carried load is used (it does not count across a back edge), so the
         // one place where everything must have landed is made to be the place where it drains.
         double nq[R][MAXE];
-        int s = 0;
+        int s = s_first;
         for (; s + 2 * R + QP_STAGE_BUFS - 1 <= nsteps; s += R) {
 #pragma unroll
             for (int k = 0; k < R; ++k) {
@@ -312,7 +248,7 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
             }
         }
     } else
-    for (int s = 0; s < nsteps; ++s) {
+    for (int s = s_first; s < nsteps; ++s) {
         SOLVE_T(26);
         const double e0 = cf0, e1 = cf1, e2 = cf2;
         step_coef(s + 1, cf0, cf1, cf2);
@@ -336,13 +272,7 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
                     coupling_coef(w, mid + 1, -1, rr, e0, e1, e2);
                     v -= e0 * V1[g3] + e1 * V1[g3 + 1] + e2 * V1[g3 + 2];
                 }
-                A0[rs] = v;
-                kl_sync();
-                const double z = Mst[SM + rr] * kl_matvec_cols<NK>(Mst, A0, ps, r);
-                Z0[rs] = z;
-                kl_sync();
-                const double x = kl_matvec_rows<NK>(Mst, Z0, ps, r);
-                kl_sync();
+                const double x = ks_step_middle<NK>(Mst, Mst + SM + rr, v, A0, Z0, ps, r, rs, [] { kl_sync(); });
                 V0[rs] = x, V1[rs] = x;
                 if (act) vec[mid * NK + r] = x;
             }
@@ -355,31 +285,12 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
                 kl_lds* ps = (kl_lds*)small + 6 * KS_VLEN + (wave == 0 ? 0 : 64);
                 const double dinv = Mst[SM + rr];
                 if (fwd) {
-                    double v = vec[jb * NK + rr];
                     const bool has_prev = wave == 0 ? jb > 0 : jb + 1 < nj;
-                    if (has_prev) v -= e0 * V[g3] + e1 * V[g3 + 1] + e2 * V[g3 + 2];  // r' = rhs_j - T_{j,jp} v_jp
-                    kl_sync();
-                    A[rs] = v;
-                    kl_sync();
-                    const double z = dinv * kl_matvec_cols<NK>(Mst, A, ps, r);
-                    Z[rs] = z;
-                    if (act) vec[jb * NK + r] = z;
-                    kl_sync();
-                    const double vj = kl_matvec_rows<NK>(Mst, Z, ps, r);
-                    kl_sync();
-                    V[rs] = vj;
+                    ks_step_forward<NK>(Mst, dinv, vec[jb * NK + rr], has_prev, e0, e1, e2, A, Z, V, ps, r, g3, rs, [] { kl_sync(); }, [&](double z) {
+                        if (act) vec[jb * NK + r] = z;
+                    });
                 } else {
-                    // w = T_{jn,j}' x_jn: column rr of the 3x3 block of its (agent, dim) group, rows g3 .. g3+2 (x_jn sits in V)
-                    const double wv = e0 * V[g3] + e1 * V[g3 + 1] + e2 * V[g3 + 2];
-                    kl_sync();
-                    A[rs] = wv;
-                    kl_sync();
-                    const double u = vec[jb * NK + rr] - dinv * kl_matvec_cols<NK>(Mst, A, ps, r);
-                    Z[rs] = u;
-                    kl_sync();
-                    const double x = kl_matvec_rows<NK>(Mst, Z, ps, r);
-                    kl_sync();
-                    V[rs] = x;
+                    const double x = ks_step_backward<NK>(Mst, dinv, vec + jb * NK + rr, e0, e1, e2, A, Z, V, ps, r, g3, rs, [] { kl_sync(); });
                     if (act) vec[jb * NK + r] = x;
                 }
             }

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Developer tool (no GPU needed): is the gfx950 device code of two source trees the same, function by function?
 
-usage: tools/isa_diff.py <tree A> <tree B> [--jobs N] > profiles/<tag>_isa.txt        (exit status 1 when anything differs)
+usage: tools/isa_diff.py <tree A> <tree B> [--jobs N] [--b-flags "-DLEVER=0"] > profiles/<tag>_isa.txt        (exit status 1 when anything differs)
+--b-flags: extra compiler flags for tree B only -- a lever that B adds, switched off, must give A's device code.
 
 Cross-compiles every kernels/*.hip of both trees to assembly (hipcc --cuda-device-only -S) under the flag sets of csrc/Makefile -- qp.hip
 once per build of it, everything else with the plain flags --, cuts the output into functions (`.type NAME,@function` .. `.Lfunc_end`, plus
@@ -38,11 +39,11 @@ def functions(asm):
     return {fn: ren("\n".join(lines), {}) for fn, lines in out.items()}
 
 
-def compile_tree(tree, pool):
+def compile_tree(tree, pool, extra=()):
     """{variant: {function: (file, text)}}: the plain files alone, and together with each build of qp.hip"""
     src = os.path.join(tree, "swarm_simulator_amd", "csrc")
     inc = ["-I" + os.path.join(tree, "include"), "-I" + src, "-I" + os.path.join(src, "kernels"), "-I" + os.path.join(src, "abi")]
-    run = lambda f, fl: pool.submit(lambda: functions(subprocess.run(["hipcc"] + BASE + inc + fl + [f], check=True, stdout=subprocess.PIPE,
+    run = lambda f, fl: pool.submit(lambda: functions(subprocess.run(["hipcc"] + BASE + inc + list(extra) + fl + [f], check=True, stdout=subprocess.PIPE,
                                                                      stderr=subprocess.DEVNULL, text=True).stdout))
     files = sorted(glob.glob(os.path.join(src, "kernels", "*.hip")))
     plain = {os.path.basename(f): run(f, []) for f in files if os.path.basename(f) != "qp.hip"}
@@ -56,10 +57,13 @@ def compile_tree(tree, pool):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("a"), ap.add_argument("b"), ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
+    ap.add_argument("--b-flags", default="", help="extra compiler flags for tree B only")
     args = ap.parse_args()
     with concurrent.futures.ThreadPoolExecutor(args.jobs) as pool:
-        A, B = compile_tree(args.a, pool), compile_tree(args.b, pool)
+        A, B = compile_tree(args.a, pool), compile_tree(args.b, pool, args.b_flags.split())
     bad = 0
+    if args.b_flags:
+        print("# tree B compiled with", args.b_flags)
     print("# tools/isa_diff.py: device functions of B against A, text of the gfx950 assembly per function (labels renumbered, comments stripped)")
     for v in A:
         a, b = A[v], B[v]
