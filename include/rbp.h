@@ -346,7 +346,7 @@ void rbp_release_thread_context(void);
                               4: rbp_solver_opts (the library no longer reads environment variables); 5: rbp_session_shard_joint, RBP_ERR_EXCHANGE;
                               6: rbp_param.timescale_rule, rbp_plan.time_scale_alt */
 enum { RBP_SIZEOF_WORLD = 0, RBP_SIZEOF_MISSION = 1, RBP_SIZEOF_PARAM = 2, RBP_SIZEOF_PLAN = 3, RBP_SIZEOF_COUNTERS = 4, RBP_SIZEOF_DEVICE_ARRAYS = 5,
-       RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7 };
+       RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7, RBP_SIZEOF_REPORT = 8 };
 int rbp_abi_version(void);
 size_t rbp_sizeof(int which);
 const char* rbp_version(void);
@@ -447,6 +447,39 @@ void rbp_dev_ecbs_destroy(rbp_dev_ecbs* e);
  * run_async, download, reset, device_arrays, set_solver_opts ... work as on a session of rbp_session_create.  A search whose missions
  * came without max_vel / max_acc is refused. */
 int  rbp_session_create_from_ecbs(rbp_session** out, const rbp_dev_ecbs* e, const rbp_param* param, int32_t max_boxes, int32_t* slot_of);
+
+/* ---- a mission's acceptance signals on the device ---------------------------
+ * The two numbers the reference prints per plan (rbp_publisher.hpp:685-695, 769-798): the smallest safety ratio -- downwash-scaled
+ * distance of two agents over the sum of their radii, should be >= 1 -- over all pairs at every sample t = j * dt, j < floor(T[M] / dt),
+ * and the summed length of the agents' sampled paths.  The arithmetic is stated once, in csrc/common/report_rules.h, for the kernels
+ * (kernels/report.hip) and for rbp_report_host of rbp_host.h: both return the same bits.  They are not the bits of rbp_validate, whose
+ * std::pow polynomial and single running sum no GPU reproduces: positions are Horner's scheme here, the distance is a sum per agent and
+ * then over the agents, and the minimum names the lexicographically first (sample, qi, qj) among equal ratios; a NaN is never the minimum.
+ * rbp_session_report: the reports of a session's K missions from its own coef, T, time scale, radius and status, which stay in HBM: it
+ *   waits for an asynchronous solve like every call, enqueues two kernels on `stream`, copies K structs back in one copy and returns when
+ *   they have arrived.  Nothing of the session changes.  A mission whose status is not 0 is reported with that status and nothing else.
+ *   RBP_ERR_BAD_ARGUMENT: a session whose last run did not include the PLANNER stage; more agents than one sample's positions fit the LDS
+ *   budget for (1365); and, before a device is looked for, a null pointer or dt <= 0.
+ * rbp_dev_report: the same kernels on a caller's host arrays, uploaded once -- coefficients from anywhere, the reference's own log for one.
+ *   Mission k has M[k] <= M_stride segments; T is [K][M_stride + 1] (M[k] + 1 entries used), not scaled; time_scale [K] multiplies it as
+ *   rbp_session_download does (NULL: 1); coef holds per mission a slot of N * 3 * 6 * M_stride doubles with the mission's own
+ *   [N][3][6 M[k]] at its front, a session's layout; radius [K][N].  device < 0: the current one.  Argument errors (a null pointer,
+ *   K, N <= 0, an M[k] outside 1..M_stride, dt, downwash or a time scale <= 0) are RBP_ERR_BAD_ARGUMENT before a device is looked for. */
+#define RBP_REPORT_MAX_SAMPLES (1 << 20)
+typedef struct rbp_report {
+    double  min_safety_ratio;      /* 1e9: no pair or no sample */
+    double  total_flight_distance;
+    double  end_time;              /* Ts[M]: the mission's last segment time, scaled */
+    int32_t samples;               /* -1: more than RBP_REPORT_MAX_SAMPLES, nothing else computed (ratio 1e9, distance 0) */
+    int32_t min_sample, min_qi, min_qj;  /* where the minimum is; -1: none */
+    int32_t status;                /* the mission's status; != 0: nothing computed, ratio 0, distance 0, end time 0, no samples, indices -1 */
+    int32_t reserved;
+} rbp_report;
+int rbp_session_report(rbp_session* s, double dt, rbp_report* out /* [K] */, void* stream);
+int rbp_dev_report(int device, int32_t K, int32_t N, const int32_t* M /* [K] */, int32_t M_stride,
+                   const double* T /* [K][M_stride+1], unscaled */, const double* time_scale /* [K] or NULL = 1 */,
+                   const double* coef /* per mission the session's layout */, const double* radius /* [K][N] */,
+                   double downwash, double dt, rbp_report* out /* [K] */);
 
 const char* rbp_last_error(void);
 int rbp_device_count(void);

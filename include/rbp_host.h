@@ -82,6 +82,13 @@ void rbp_init_traj_free(rbp_init_traj_buf* t);
 int rbp_validate(const rbp_mission* mission, const rbp_param* param, int32_t M, const double* T, const double* coef,
                  double dt, double* min_safety_ratio, double* total_flight_distance);
 
+/* The same two signals as an rbp_report (rbp.h), by the rule of csrc/common/report_rules.h that the device shares: what
+ * rbp_session_report / rbp_dev_report return for the same plan, bit for bit, and their reference.  Same inputs as rbp_validate (T as
+ * downloaded, i.e. scaled); it differs from rbp_validate by rounding only -- Horner instead of std::pow, the distance summed per agent and
+ * then over the agents -- and also says at which (sample, qi, qj) the minimum lies.  out->status is 0. */
+int rbp_report_host(const rbp_mission* mission, const rbp_param* param, int32_t M, const double* T, const double* coef,
+                    double dt, rbp_report* out);
+
 /* crazyswarm CSV of rbp_planner.hpp:295-324 (one file per agent: <dir>/coef<qi+1>.csv) */
 int rbp_write_coef_csv(const char* dir, int32_t N, int32_t M, const double* T, const double* coef);
 

@@ -96,6 +96,16 @@ class rbp_ecbs_out(C.Structure):
                 ("T", c_double_p), ("init_traj", c_float_p)]
 
 
+RBP_REPORT_MAX_SAMPLES = 1 << 20     # rbp_report.samples is -1 beyond (include/rbp.h)
+RBP_SIZEOF_REPORT = 8
+
+
+class rbp_report(C.Structure):
+    _fields_ = [("min_safety_ratio", C.c_double), ("total_flight_distance", C.c_double), ("end_time", C.c_double),
+                ("samples", C.c_int32), ("min_sample", C.c_int32), ("min_qi", C.c_int32), ("min_qj", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class rbp_mission_buf(C.Structure):
     _fields_ = [("N", C.c_int32), ("start", c_double_p), ("goal", c_double_p), ("radius", c_double_p),
                 ("speed", c_double_p), ("max_vel", c_double_p), ("max_acc", c_double_p)]

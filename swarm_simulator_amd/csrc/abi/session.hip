@@ -108,6 +108,7 @@ struct rbp_session {
     // the exchange buffers are the session's own
     JointShard shard{};
     char* shard_buf = nullptr;
+    char* report_buf = nullptr;  // rbp_session_report: K reports and the pair kernel's partial minima (report_workspace_bytes), reserved by the first call
 };
 
 // waits for the session's asynchronous joint run, if one is in flight; reports its error once
@@ -133,6 +134,7 @@ size_t rbp_sizeof(int which) {
         case RBP_SIZEOF_DEVICE_ARRAYS: return sizeof(rbp_device_arrays);
         case RBP_SIZEOF_SOLVER_OPTS: return sizeof(rbp_solver_opts);
         case RBP_SIZEOF_ECBS_OUT: return sizeof(rbp_ecbs_out);
+        case RBP_SIZEOF_REPORT: return sizeof(rbp_report);
         default: return 0;
     }
 }
@@ -845,6 +847,36 @@ int rbp_session_download(rbp_session* s, rbp_plan* plans, int32_t* status, void*
     return first;
 }
 
+// The missions' safety ratios and flight distances from where the plans lie (kernels/report.hip): coef, T, the time scale among the
+// scalars, radius and status are read in place, K structs come back in one copy, and nothing of the session is written.
+int rbp_session_report(rbp_session* s, double dt, rbp_report* out, void* stream) {
+    if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_report: null argument");
+    if (!(dt > 0)) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_report: dt must be positive");
+    if (int jrc = join_worker(s)) return jrc;
+    if (!(s->last_stages & RBP_STAGE_PLANNER))
+        return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_report: the session's last run did not include the PLANNER stage: there are no coefficients to report on");
+    const DevSession& d = s->d;
+    if (report_tile(d.N) <= 0)
+        return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_report: " + std::to_string(d.N) + " agents: the positions of one sample do not fit the report kernel's LDS budget");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->report_buf) {
+        const hipError_t e = hipMalloc((void**)&s->report_buf, report_workspace_bytes(d.K));
+        if (e != hipSuccess) {
+            s->report_buf = nullptr;
+            return fail(RBP_ERR_HIP, std::string("rbp_session_report: workspace: ") + hipGetErrorString(e));
+        }
+    }
+    ReportInputs in{};
+    in.K = d.K, in.N = d.N, in.M_stride = d.M, in.Mk = d.Mk, in.T = d.T, in.coef = d.coef, in.radius = d.radius;
+    in.ts = d.scalars + SC_TIME_SCALE, in.ts_stride = SC_N, in.status = d.status;
+    in.downwash = d.p.downwash, in.dt = dt;
+    if (int rc = launch_report(in, s->report_buf, st)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, s->report_buf, sizeof(rbp_report) * (size_t)d.K, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RBP_OK;
+}
+
 int rbp_session_device_arrays(rbp_session* s, int32_t mission, rbp_device_arrays* out) {
     if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "null argument");
     const DevSession& d = s->d;
@@ -910,6 +942,10 @@ void rbp_session_destroy(rbp_session* s) {
     if (s->shard_buf) {
         (void)hipSetDevice(s->device);
         (void)hipFree(s->shard_buf);
+    }
+    if (s->report_buf) {
+        (void)hipSetDevice(s->device);
+        (void)hipFree(s->report_buf);
     }
     if (s->ctx) {
         s->ctx->busy = false;  // the arena (and the QP workspace) stay with the context

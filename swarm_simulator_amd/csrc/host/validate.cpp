@@ -5,6 +5,8 @@
 //   coef CSV           rbp_planner.hpp:295-324
 #include "rbp_host.h"
 
+#include "common/report_rules.h"
+
 #include <cmath>
 #include <cstdio>
 #include <string>
@@ -57,6 +59,20 @@ extern "C" int rbp_validate(const rbp_mission* mission, const rbp_param* param, 
             }
     if (min_safety_ratio) *min_safety_ratio = ratio_min;
     if (total_flight_distance) *total_flight_distance = len;
+    return RBP_OK;
+}
+
+// The same two signals by the rule of common/report_rules.h, which the device's report kernels (kernels/report.hip) share: Horner
+// positions, one sum of step lengths per agent, and where the minimum is.  T arrives scaled (a downloaded plan's), so the scale is 1.
+extern "C" int rbp_report_host(const rbp_mission* mission, const rbp_param* param, int32_t M, const double* T, const double* coef,
+                               double dt, rbp_report* out) {
+    if (!mission || !param || !T || !coef || !out || !mission->radius || mission->N <= 0 || M <= 0 || !(dt > 0)) return RBP_ERR_BAD_ARGUMENT;
+    std::vector<double> scratch((size_t)7 * mission->N);
+    const report_rules::Result r =
+        report_rules::report_sequential(mission->N, M, T, 1.0, coef, mission->radius, param->downwash, dt, scratch.data());
+    out->min_safety_ratio = r.min_safety_ratio, out->total_flight_distance = r.total_flight_distance, out->end_time = r.end_time;
+    out->samples = r.samples, out->min_sample = r.min_sample, out->min_qi = r.min_qi, out->min_qj = r.min_qj;
+    out->status = 0, out->reserved = 0;
     return RBP_OK;
 }
 

@@ -201,6 +201,25 @@ int launch_ecbs_plan_write(const rbp_dev_ecbs& e, int n, const int* src, const i
 int launch_ecbs_mission_gather(const rbp_dev_ecbs& e, int n, const int* src, double* start, double* goal, double* radius, double* max_vel,
                                double* max_acc, hipStream_t st);
 
+// kernels/report.hip: the safety ratio and flight distance of K missions (rbp_report of include/rbp.h) from device arrays in a session's
+// layout.  launch_report enqueues its two kernels on `st`; the K reports are then at the front of `workspace` (report_workspace_bytes(K)
+// bytes of device memory, nothing to initialise).  report_tile(N) == 0: more agents than one sample's positions fit the LDS budget for,
+// which launch_report refuses with RBP_ERR_BAD_ARGUMENT before it launches anything.
+struct ReportInputs {
+    int K, N, M_stride;
+    const int* Mk;         // [K] segments of mission k (<= M_stride)
+    const double* T;       // [K][M_stride + 1], not scaled
+    const double* coef;    // [K] slots of N * 3 * 6 * M_stride, mission k's own [N][3][6 Mk[k]] at the front of its slot
+    const double* radius;  // [K][N]
+    const double* ts;      // mission k's time scale is ts[k * ts_stride] (<= 0 reads as 1); null: 1
+    int ts_stride;
+    const int* status;     // [K] or null: a mission whose status is not 0 is reported as such and not evaluated
+    double downwash, dt;
+};
+int report_tile(int N);
+size_t report_workspace_bytes(int K);
+int launch_report(const ReportInputs& in, void* workspace, hipStream_t st);
+
 // launchers (defined in the .hip files)
 int launch_corridor(const DevSession& s, hipStream_t st);
 size_t corridor_lds_bytes(const DevSession& s);  // dynamic LDS of sfc_kernel for this session's shapes

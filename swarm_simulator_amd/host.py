@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _abi as A
-from .types import Mission, Param, PlanResult, World
+from .types import Mission, Param, PlanResult, Report, World
 
 _lib = None
 
@@ -43,6 +43,8 @@ def lib():
         L.rbp_init_traj_free.restype = None
         L.rbp_validate.argtypes = [C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.c_int32, A.c_double_p,
                                    A.c_double_p, C.c_double, A.c_double_p, A.c_double_p]
+        L.rbp_report_host.argtypes = [C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.c_int32, A.c_double_p,
+                                      A.c_double_p, C.c_double, C.POINTER(A.rbp_report)]
         L.rbp_write_coef_csv.argtypes = [C.c_char_p, C.c_int32, C.c_int32, A.c_double_p, A.c_double_p]
         L.rbp_write_qp_lp.argtypes = [C.c_char_p, C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.POINTER(A.rbp_plan), C.c_int32,
                                       A.c_double_p]
@@ -176,6 +178,17 @@ def validate(mission: Mission, param: Param, plan: PlanResult, dt=0.1):
     if rc:
         raise RuntimeError(f"rbp_validate rc={rc}")
     return ratio.value, dist.value
+
+
+def report(mission: Mission, param: Param, plan: PlanResult, dt=0.1) -> Report:
+    """the same two signals as a Report, by the rule the device shares (csrc/common/report_rules.h): what planner.Session.report /
+    planner.report_coefs return for this plan, bit for bit, and where the minimum lies.  Differs from validate by rounding only."""
+    ms, ps = mission.c_struct(), param.c_struct()
+    out = A.rbp_report()
+    rc = lib().rbp_report_host(C.byref(ms), C.byref(ps), plan.M, A.ptr(plan.T, A.c_double_p), A.ptr(plan.coef, A.c_double_p), dt, C.byref(out))
+    if rc:
+        raise ValueError(f"rbp_report_host rc={rc}")
+    return Report.from_c(out)
 
 
 def write_coef_csv(directory, plan: PlanResult):

@@ -11,7 +11,7 @@ import ctypes as C
 import os
 
 from . import _abi as A
-from .types import DeviceWorld, Mission, Param, PlanResult, World
+from .types import DeviceWorld, Mission, Param, PlanResult, Report, World
 
 _lib = None
 
@@ -129,6 +129,11 @@ def lib():
             L.rbp_dev_ecbs_destroy.argtypes = [C.c_void_p]
             L.rbp_dev_ecbs_destroy.restype = None
             L.rbp_session_create_from_ecbs.argtypes = [P(C.c_void_p), C.c_void_p, P(A.rbp_param), C.c_int32, A.c_int32_p]
+            L.rbp_session_report.argtypes = [C.c_void_p, C.c_double, P(A.rbp_report), C.c_void_p]
+            L.rbp_dev_report.argtypes = [C.c_int, C.c_int32, C.c_int32, A.c_int32_p, C.c_int32, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p,
+                                         C.c_double, C.c_double, P(A.rbp_report)]
+            if L.rbp_sizeof(A.RBP_SIZEOF_REPORT) != C.sizeof(A.rbp_report):
+                raise RbpLibraryMissing(f"{path}: sizeof(rbp_report) is {L.rbp_sizeof(A.RBP_SIZEOF_REPORT)} in the library, {C.sizeof(A.rbp_report)} in this binding")
         except AttributeError:
             if not os.environ.get("RBP_HIP_LIB"):
                 raise
@@ -165,6 +170,7 @@ EXPORTED_SYMBOLS = [
     "rbp_dev_worlds_create", "rbp_dev_worlds_count", "rbp_dev_worlds_get", "rbp_dev_worlds_download", "rbp_dev_worlds_destroy",
     "rbp_dev_worlds_ecbs_obstacles", "rbp_dev_ecbs_plan_masks", "rbp_dev_worlds_ecbs_plan",
     "rbp_dev_worlds_ecbs_search", "rbp_dev_ecbs_count", "rbp_dev_ecbs_download", "rbp_dev_ecbs_destroy", "rbp_session_create_from_ecbs",
+    "rbp_session_report", "rbp_dev_report",
 ]
 
 
@@ -423,6 +429,18 @@ class Session:
             p.sync_from(c)
         return st.tolist()
 
+    def report(self, dt=0.1, stream=None):
+        """the missions' safety ratios and flight distances, computed where the plans lie (rbp_session_report): a list of K Report records,
+        the bits host.report gives for the downloaded plans.  Nothing is downloaded and nothing of the session changes; a mission whose
+        status is not 0 comes back with that status and nothing computed."""
+        out = (A.rbp_report * self.K)()
+        rc = lib().rbp_session_report(self._h, dt, out, C.c_void_p(stream or 0))
+        if rc == A.RBP_ERR_BAD_ARGUMENT:
+            raise ValueError(f"rbp_session_report rc={rc}: {last_error()}")
+        if rc:
+            raise RuntimeError(f"rbp_session_report rc={rc}: {last_error()}")
+        return [Report.from_c(r) for r in out]
+
     def reserve_workspace(self, stream=None):
         """reserve the QP workspace now (otherwise the first PLANNER run does)"""
         rc = lib().rbp_session_reserve_workspace(self._h, C.c_void_p(stream or 0))
@@ -478,6 +496,29 @@ class Session:
             self.close()
         except Exception:
             pass
+
+
+def report_coefs(M, T, coef, radius, downwash, dt=0.1, time_scale=None, device=0):
+    """rbp_dev_report: the report kernels on the caller's arrays, uploaded once -- coefficients from anywhere, the reference's own log for
+    one.  M [K] segments per mission; T [K][S + 1] unscaled times (S >= max M, M[k] + 1 entries of row k used); coef [K][N][3][6 S] with
+    mission k's own [N][3][6 M[k]] packed at the front of its slot (a session's layout: for M[k] == S simply [N][3][6 S]); radius [K][N];
+    time_scale [K] or None.  Returns K Report records, the bits host.report gives for the scaled times."""
+    import numpy as np
+    M = np.ascontiguousarray(M, np.int32).reshape(-1)
+    K = len(M)
+    T, coef, radius = A.as_f64(T).reshape(K, -1), A.as_f64(coef), A.as_f64(radius).reshape(K, -1)
+    S, N = T.shape[1] - 1, radius.shape[1]
+    if coef.size != K * N * 3 * 6 * S:
+        raise ValueError(f"coef holds {coef.size} doubles, K * N * 3 * 6 * M_stride = {K * N * 3 * 6 * S}")
+    ts = None if time_scale is None else A.as_f64(time_scale).reshape(K)
+    out = (A.rbp_report * K)()
+    rc = lib().rbp_dev_report(device, K, N, A.ptr(M, A.c_int32_p), S, A.ptr(T, A.c_double_p), A.ptr(ts, A.c_double_p), A.ptr(coef, A.c_double_p),
+                              A.ptr(radius, A.c_double_p), downwash, dt, out)
+    if rc == A.RBP_ERR_BAD_ARGUMENT:
+        raise ValueError(f"rbp_dev_report rc={rc}: {last_error()}")
+    if rc:
+        raise RuntimeError(f"rbp_dev_report rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+    return [Report.from_c(r) for r in out]
 
 
 def build_world(keys, res, param: Param, max_dist=1.0):

@@ -7,12 +7,17 @@ With --device-ecbs (only with --device-worlds) the searches of all maps run on t
 initial trajectories, and one report line for the whole front-end instead of one per map.
 With --device-handoff (only with --device-ecbs and --mode batched) the searches' plans never come to the host: the session is built from
 them where they lie (planner.ecbs_search_batch, planner.Session.from_ecbs).  The same report lines.
+With --device-report (only with --device-worlds --mode batched) the safety ratio and flight distance of every map's report line come from ONE
+planner.Session.report() on the resident plans instead of host.validate per downloaded plan: the same line format, the numbers of the
+rule the device and host.report share (csrc/common/report_rules.h; they differ from host.validate's by rounding).  Without --csv nothing
+but K small records and two scalars per map is downloaded.
 
-usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
+usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]] [--device-report]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
        [--batch-size 4] [--iteration 1] [--joint] [--csv DIR]
 """
 import argparse
 import time
+from types import SimpleNamespace
 
 from . import host, planner, test_all
 from .types import Param
@@ -26,6 +31,8 @@ def main(argv=None):
                     "with an error where the host search would go on")
     ap.add_argument("--device-handoff", action="store_true", help="with --device-worlds --device-ecbs --mode batched: the session is built on the device from the "
                     "search's resident results, no initial trajectory passes through the host")
+    ap.add_argument("--device-report", action="store_true", help="with --device-worlds --mode batched: safety ratio and flight distance of all maps from one "
+                    "report call on the device (planner.Session.report); without --csv the coefficients are not downloaded")
     ap.add_argument("--mission", default="mission_64agents_15.json")
     ap.add_argument("--maps", default="1-50")
     ap.add_argument("--mode", choices=["serial", "batched"], default="serial")
@@ -34,6 +41,8 @@ def main(argv=None):
     ap.add_argument("--joint", action="store_true")
     ap.add_argument("--csv", default=None, help="write coef<qi>.csv per map into DIR/map<i>/ (generateCoefCSV)")
     args, rest = ap.parse_known_args(argv)
+    if args.device_report and not (args.device_worlds and args.mode == "batched"):
+        ap.error("--device-report needs --device-worlds --mode batched")
     if args.device_ecbs and not args.device_worlds:
         ap.error("--device-ecbs needs --device-worlds")
     if args.device_handoff and not (args.device_ecbs and args.mode == "batched"):
@@ -92,18 +101,7 @@ def main(argv=None):
             plans.append(pr)
         if args.mode == "batched":
             sess = planner.Session([worlds[n] for n in range(len(maps))], [mission] * len(plans), param, plans)
-            t0 = time.perf_counter()
-            sess.run()
-            status = sess.download()
-            dt = time.perf_counter() - t0
-            print(f"BoxGenerator + SwarmPlanner runtime, {len(plans)} maps in one session: {dt:.6f} "
-                  f"({len(plans) * mission.qn / dt:.1f} agent-trajectories/s incl. download)")
-            sess.close()
-            for i, p, st in zip(maps, plans, status):
-                if st:
-                    print(f"[ERROR] map{i}: status {st}")
-                    return -1
-                test_all.report(i, mission, param, p, args.csv)
+            return run_and_report(args, sess, maps, plans, mission, param)
         return 0
     finally:
         worlds.close()
@@ -123,19 +121,44 @@ def handoff_sweep(args, worlds, maps, mission, param):
         print(f"Map: map{i}.bt")
     sess = planner.Session.from_ecbs(search, param)
     search.close()
+    return run_and_report(args, sess, maps, sess.plans, mission, param)
+
+
+def run_and_report(args, sess, maps, plans, mission, param):
+    """the batched mode's run of a session and its report lines.  --device-report: the lines' two signals come from one Session.report(),
+    and without --csv each line's cost, time scale and makespan from the session's scalars and that record instead of a download."""
+    download = not args.device_report or bool(args.csv)
     t0 = time.perf_counter()
     sess.run()
-    status = sess.download()
+    status = sess.download() if download else None
+    records = sess.report() if args.device_report else [None] * sess.K
     dt = time.perf_counter() - t0
     print(f"BoxGenerator + SwarmPlanner runtime, {sess.K} maps in one session: {dt:.6f} "
-          f"({sess.K * mission.qn / dt:.1f} agent-trajectories/s incl. download)")
+          f"({sess.K * mission.qn / dt:.1f} agent-trajectories/s incl. {'download' if download else 'report'})")
+    if not download:
+        sc = sess.scalars(n=2)   # (kernels/rbp_dev.h: SC_TIME_SCALE, SC_TOTAL_COST -- read as rbp_session_download reads them)
+        status = [r.status for r in records]
+        plans = [SimpleNamespace(total_cost=float(c), time_scale=float(ts) if ts > 0 else 1.0, T=[r.end_time]) for (ts, c), r in zip(sc, records)]
     sess.close()
-    for i, p, st in zip(maps, sess.plans, status):
+    for i, p, st, rec in zip(maps, plans, status, records):
         if st:
             print(f"[ERROR] map{i}: status {st}")
             return -1
-        test_all.report(i, mission, param, p, args.csv)
+        if rec is None:
+            test_all.report(i, mission, param, p, args.csv)
+        else:
+            report_line(i, p, rec, args.csv)
     return 0
+
+
+def report_line(i, plan, record, csv_dir):
+    """test_all.report's line, format and all, with the two signals of a types.Report computed on the device (planner.Session.report)
+    where test_all.report calls host.validate; `plan` only has to carry total_cost, time_scale and T[-1] (and coef for a CSV)"""
+    print(f"map{i}: QP total cost {plan.total_cost:.6f}  time_scale {plan.time_scale:.4f}  makespan {plan.T[-1]:.3f}  "
+          f"safety margin ratio {record.min_safety_ratio:.4f}  total flight distance {record.total_flight_distance:.3f}")
+    if csv_dir:
+        import os
+        host.write_coef_csv(os.path.join(csv_dir, f"map{i}"), plan)
 
 
 if __name__ == "__main__":

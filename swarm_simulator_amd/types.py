@@ -174,6 +174,29 @@ class DeviceWorld:
         return World(self._owner.detach().cpu().numpy(), self.key_min, self.res)
 
 
+@dataclass
+class Report:
+    """rbp_report (include/rbp.h): a mission's two acceptance signals and where the smallest ratio lies.  min_safety_ratio is 1e9 and the
+    three indices -1 for a mission without a pair or a sample; samples is -1 beyond RBP_REPORT_MAX_SAMPLES; status != 0: nothing computed."""
+    min_safety_ratio: float
+    total_flight_distance: float
+    end_time: float
+    samples: int
+    min_sample: int
+    min_qi: int
+    min_qj: int
+    status: int = 0
+
+    @classmethod
+    def from_c(cls, r):
+        return cls(r.min_safety_ratio, r.total_flight_distance, r.end_time, r.samples, r.min_sample, r.min_qi, r.min_qj, r.status)
+
+    def bits(self):
+        """the record with its doubles as bit patterns: what two evaluations of the one rule must agree on"""
+        f = np.array([self.min_safety_ratio, self.total_flight_distance, self.end_time], np.float64).view(np.uint64)
+        return tuple(int(x) for x in f) + (self.samples, self.min_sample, self.min_qi, self.min_qj, self.status)
+
+
 class PlanResult:
     """sp_const.hpp:21-28 as flat arrays (include/rbp.h rbp_plan)."""
 
