@@ -121,9 +121,7 @@ __device__ __forceinline__ Ws carve(const JArgs& A, int mission) {
 }
 __device__ __forceinline__ double* red_slot(const Ws& w, const JLayout& L, int slot, int comp) { return w.red + ((size_t)slot * 4 + comp) * L.nred; }
 
-#define JQ_POLISH_PART 1
-#include "jqp_polish.inc"
-#undef JQ_POLISH_PART
+#include "jqp_polish_types.inc"  // the polish's records, as far as the sweeps and the layout need them
 
 // ------------------------------------------------------------------------------------------------------------------------
 // setup: mission constants (qp.hip mission_constants), SFC box per (agent, segment) (rbp_planner.hpp:447-453), pinned end control
@@ -232,7 +230,7 @@ struct PassIO {
     double sum0, sum1, sum2, vmax, vmin;
 };
 
-// one row, as row_op in qp.hip: the arithmetic is common/ipm_rows.h.  s, z: current state; out: new state (INIT, UPBUILD) through
+// one row, as row_op in qp_rows.inc: the arithmetic is common/ipm_rows.h.  s, z: current state; out: new state (INIT, UPBUILD) through
 // sn_out / zn_out, the target shift (GOND) through sn_out.  BUILD assembles the NEXT iteration's matrix: dregn
 template <int PASS>
 __device__ __forceinline__ void row_op(double slack, double ga, double gd, double s, double z, PassIO& io, double cw, double& wgt, double& v,
@@ -1063,9 +1061,7 @@ __global__ __launch_bounds__(256) void jq_xfer(JArgs A, int what, int dir, int c
     }
 }
 
-#define JQ_POLISH_PART 2
-#include "jqp_polish.inc"
-#undef JQ_POLISH_PART
+#include "jqp_polish.inc"  // the active-set polish: the kernels
 
 // ------------------------------------------------------------------------------------------------------------------------
 // end of a solve: objective sum x' Q_p x (cplex.getObjValue, rbp_planner.hpp:164), diagnostics, status
@@ -1153,7 +1149,7 @@ JLayout jq_layout(int N, int MS) {
     L.o_Y = take((size_t)4 * d.nblk * JTT), L.o_P = take((size_t)10 * JTT);  // (per chain: two panel tiles per block row; 2 + 2 single pivots, 3 + 3 tiles of double pivots)
     L.o_scr = take((size_t)2 * d.nkp * d.nkp);
     const PolLayout PL = pol_layout(N, MS);
-    L.o_inv = take(std::max((size_t)d.nj * d.nkp * d.nkp, PL.big_total));  // (the polish's matrices overlay the inverses: jqp_polish.inc pol_layout)
+    L.o_inv = take(std::max((size_t)d.nj * d.nkp * d.nkp, PL.big_total));  // (the polish's matrices overlay the inverses: jqp_polish_types.inc pol_layout)
     L.o_pol = take(PL.total);
     L.o_rhsc = take((size_t)d.nj * d.nkp), L.o_dx2 = take(3 * ncp), L.o_tb = take(6 * ncp), L.o_tp = take(nrow);
     L.stride = o;

@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void jq_pivot0(JArgs A, int kind, int s, int m
 }
 
 // operand fragments of a 16-row block for v_mfma_f64_16x16x4_f64 over K = 64: lane (i, g) holds rows[i][16 ch + 4 g + q], ch, q = 0..3
-// (the four MFMA steps of a 16-chunk use k = 4 g + q on both operands: a permutation of the summation index, see tile_nt in qp.hip).
+// (the four MFMA steps of a 16-chunk use k = 4 g + q on both operands: a permutation of the summation index, see tile_nt in qp_tiled.inc).
 // TR: the operand is the TRANSPOSE of the stored tile (rows of the operand are columns of the tile).
 __device__ __forceinline__ void load_frag(const double* tile, int row0, bool tr, int li, int lg, d4 (&f)[4]) {
     if (!tr) {

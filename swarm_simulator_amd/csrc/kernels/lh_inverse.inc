@@ -1,6 +1,6 @@
 // Dual active-set solve of the polish (qp_polish.inc): products with the explicit inverse factor W = L^-1 of S_PP, one wavefront.
 // Included by qp_polish.inc (and by tools/ubench/lhw.hip, which times and checks it alone); needs rl_dyn (qp_polish.inc), WSYNC
-// (qp_polish_types.inc), fast_rsqrt (qp.hip), kl_lds (knot_lds.inc).
+// (qp_polish_types.inc), fast_rsqrt (qp_rows.inc), kl_lds (knot_lds.inc).
 //
 // With L every step of Lawson-Hanson is a triangular solve: nP DEPENDENT steps of one wave, twice per appended row, and the Givens
 // sweep of a deletion is another dependent chain with a wave barrier per column pair (measured: ~250 cycles per step of either).

@@ -1,5 +1,5 @@
-// qp_polish.inc — active-set polish ("crossover") of the interior-point answer: the algorithms.  Included by qp.hip, once, behind its factor /
-// solve entries; needs its records (qp_polish_types.inc), uni, uni_words (qp_base.inc) and row_pass, apply_F, apply_FT of qp.hip.
+// qp_polish.inc — active-set polish ("crossover") of the interior-point answer: the algorithms.  Included by qp.hip, once, behind
+// qp_entries.inc; needs its records (qp_polish_types.inc), uni, uni_words (qp_base.inc), row_pass (qp_rows.inc) and apply_F, apply_FT (qp_newton.inc).
 //
 // Same mathematics as the CPU checker's polish, re-implemented for one workgroup (DESIGN.md "Polish"):
 //   candidates C  = rows with dominant multiplier or slack < 1e-6 at the interior-point iterate

@@ -1,6 +1,6 @@
 // qp_polish_types.inc — what the row sweeps need of the active-set polish (qp_polish.inc: the algorithms): the candidate record and the
 // polish workspace (Cand, PolishWs, polish_carve), emit_cand, and the wave helpers of the dual solve (WSYNC, wave_argmax).
-// Included by qp.hip after qp_base.inc, ahead of its row sweeps; needs QpDims, QpWs, wave_red (qp_base.inc) and the PL_* sizes of qp.hip.
+// Included by qp.hip after qp_base.inc, ahead of qp_rows.inc; needs QpDims, QpWs, wave_red (qp_base.inc) and the PL_* sizes of qp.hip.
 
 // PL_NC (candidate rows) and PL_PMAX (rows simultaneously active in the dual solve) are defined in qp.hip
 

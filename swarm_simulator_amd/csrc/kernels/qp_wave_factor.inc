@@ -1,7 +1,8 @@
 // qp_wave_factor.inc — the wave-register path (nk <= 36), factorisation: the twisted block-tridiagonal L D L' of two chain waves, their
 // companions (M = L^-T) and the waves that assemble the knot blocks just in time (twisted_factor).  Included by qp.hip behind
-// its knot-block assembly; needs from qp.hip the levers (QP_THREADS, QP_MID_FOLLOW, QP_CHAIN_PRIO), QG / QGC, fast_rsqrt, AsmArgs,
-// ASML_DOUBLES, assemble_knots_lds, fasm_fetch / fasm_tiles; QpDims, QpWs, rl (qp_base.inc); kl_*, KL_*, KlPanels (knot_lds.inc).
+// qp_newton.inc, whose knot-block assembly it needs (AsmArgs, ASML_DOUBLES, assemble_knots_lds, fasm_fetch / fasm_tiles); from qp.hip the
+// levers (QP_THREADS, QP_MID_FOLLOW, QP_CHAIN_PRIO) and QG / QGC; fast_rsqrt (qp_rows.inc); QpDims, QpWs, rl (qp_base.inc); kl_*, KL_*,
+// KlPanels (knot_lds.inc).
 
 // ------------------------------------------------------------------------------------------------------------
 // wave-register path (nk <= 36, i.e. batches of up to 4 agents): the whole block-tridiagonal Cholesky and the
