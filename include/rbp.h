@@ -346,7 +346,7 @@ void rbp_release_thread_context(void);
                               4: rbp_solver_opts (the library no longer reads environment variables); 5: rbp_session_shard_joint, RBP_ERR_EXCHANGE;
                               6: rbp_param.timescale_rule, rbp_plan.time_scale_alt */
 enum { RBP_SIZEOF_WORLD = 0, RBP_SIZEOF_MISSION = 1, RBP_SIZEOF_PARAM = 2, RBP_SIZEOF_PLAN = 3, RBP_SIZEOF_COUNTERS = 4, RBP_SIZEOF_DEVICE_ARRAYS = 5,
-       RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7, RBP_SIZEOF_REPORT = 8 };
+       RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7, RBP_SIZEOF_REPORT = 8, RBP_SIZEOF_DYNAMICS = 9 };
 int rbp_abi_version(void);
 size_t rbp_sizeof(int which);
 const char* rbp_version(void);
@@ -480,6 +480,50 @@ int rbp_dev_report(int device, int32_t K, int32_t N, const int32_t* M /* [K] */,
                    const double* T /* [K][M_stride+1], unscaled */, const double* time_scale /* [K] or NULL = 1 */,
                    const double* coef /* per mission the session's layout */, const double* radius /* [K][N] */,
                    double downwash, double dt, rbp_report* out /* [K] */);
+
+/* ---- the sampled states of resident plans, their limit peaks and ratio curves (the rest of it) ----
+ * What the reference's publisher samples of a plan at t = j * dt, j < samples, besides the two numbers above (rbp_publisher.hpp:670-683
+ * update_quad_state, 697-767 plot_quad_dynamics, 769-798 update_safety_margin_ratio), by the rule of csrc/common/state_rules.h, which
+ * the kernels (kernels/dynamics.hip) and rbp_dynamics_host of rbp_host.h share: both return the same bits.  Times, samples, the segment of
+ * a sample and positions are the report's (report_rules.h).
+ *   states  [K][N][9][S_stride]: agent, row, sample; row / 3 = derivative (position, velocity, acceleration), row % 3 = axis.  Velocity
+ *           and acceleration are Horner's scheme over the differentiated coefficients, every product and sum rounded on its own.
+ *   curves  [K][S_stride][2]: per sample the smallest (from 1e9) and the largest (from 0) safety ratio over the pairs; a NaN moves neither.
+ *   peaks   the largest |v_k| / max_vel[agent][k] and |a_k| / max_acc[agent][k] over samples, agents and axes -- above 1 the plan breaks a
+ *           limit at a sample, which the literal timeScale rule (rbp_param.timescale_rule) can leave behind -- each with the value itself
+ *           (signed), the limit it was divided by, and the lexicographically first (sample, agent, axis) among equal ratios; a ratio
+ *           that is 0, negative or NaN is never a peak.
+ * states and curves may each be NULL, a host pointer, or a device pointer on the plans' device (classified with hipPointerGetAttributes as
+ * rbp_world.dist is; another device: RBP_ERR_BAD_ARGUMENT).  A device destination is written in place by the kernels.  A host destination
+ * goes through a staging allocation of at most RBP_DYNAMICS_STAGE_BYTES (one mission's rows where those alone are larger), a chunk of
+ * missions at a time.  A mission with samples > S_stride or samples = -1 has nothing stored and stored = 0 (its peaks are still reported,
+ * except for -1); entries beyond a mission's `samples` are left untouched, as is everything of a mission that is not stored.  Size the
+ * buffers from rbp_session_report's `samples`.  S_stride is not read where both are NULL.
+ * rbp_session_dynamics: of a session's K missions, from its own arrays, which stay in HBM; waits for an asynchronous solve, refuses a
+ *   session whose last run had no PLANNER stage and more than 1365 agents, and checks its arguments before a device is looked for (a null
+ *   session or `out`, dt <= 0, S_stride < 1 with a buffer), all as rbp_session_report does.  A mission whose status is not 0 gets that
+ *   status, nothing computed (zeros, indices -1) and nothing stored.  Nothing of the session changes.
+ * rbp_dev_dynamics: the same kernels on a caller's host arrays in rbp_dev_report's layout, with max_vel / max_acc [K][N][3]. */
+#define RBP_DYNAMICS_STAGE_BYTES (64 << 20)
+typedef struct rbp_dynamics {
+    double  peak_vel_ratio, peak_vel, peak_vel_limit;   /* 0: no sample */
+    double  peak_acc_ratio, peak_acc, peak_acc_limit;
+    double  end_time;
+    int32_t samples;                                    /* as rbp_report.samples, -1 included */
+    int32_t vel_sample, vel_agent, vel_axis;            /* -1: none */
+    int32_t acc_sample, acc_agent, acc_axis;
+    int32_t stored;                                     /* 1: states / curves of this mission were written */
+    int32_t status;
+} rbp_dynamics;
+int rbp_session_dynamics(rbp_session* s, double dt, rbp_dynamics* out /* [K] */,
+                         double* states /* [K][N][9][S_stride] or NULL */,
+                         double* curves /* [K][S_stride][2] or NULL */,
+                         int32_t S_stride, void* stream);
+int rbp_dev_dynamics(int device, int32_t K, int32_t N, const int32_t* M, int32_t M_stride,
+                     const double* T, const double* time_scale, const double* coef,
+                     const double* radius, const double* max_vel, const double* max_acc,
+                     double downwash, double dt, rbp_dynamics* out,
+                     double* states, double* curves, int32_t S_stride);
 
 const char* rbp_last_error(void);
 int rbp_device_count(void);

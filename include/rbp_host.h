@@ -89,6 +89,13 @@ int rbp_validate(const rbp_mission* mission, const rbp_param* param, int32_t M, 
 int rbp_report_host(const rbp_mission* mission, const rbp_param* param, int32_t M, const double* T, const double* coef,
                     double dt, rbp_report* out);
 
+/* The sampled states, limit peaks and ratio curves of one plan as an rbp_dynamics (rbp.h), by the sequential loop of
+ * csrc/common/state_rules.h that the device shares: what rbp_session_dynamics / rbp_dev_dynamics return for the same plan, bit for bit,
+ * and their reference.  T as downloaded (scaled); max_vel / max_acc are the mission's.  states [N][9][S_stride] and curves [S_stride][2]
+ * may each be NULL; they are written only where samples <= S_stride (out->stored), entries beyond `samples` stay.  out->status is 0. */
+int rbp_dynamics_host(const rbp_mission* mission, const rbp_param* param, int32_t M, const double* T, const double* coef,
+                      double dt, rbp_dynamics* out, double* states, double* curves, int32_t S_stride);
+
 /* crazyswarm CSV of rbp_planner.hpp:295-324 (one file per agent: <dir>/coef<qi+1>.csv) */
 int rbp_write_coef_csv(const char* dir, int32_t N, int32_t M, const double* T, const double* coef);
 

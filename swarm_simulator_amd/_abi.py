@@ -106,6 +106,17 @@ class rbp_report(C.Structure):
                 ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+RBP_SIZEOF_DYNAMICS = 9
+RBP_DYNAMICS_STAGE_BYTES = 64 << 20  # most staging memory a host destination of rbp_session_dynamics / rbp_dev_dynamics takes (include/rbp.h)
+
+
+class rbp_dynamics(C.Structure):
+    _fields_ = [("peak_vel_ratio", C.c_double), ("peak_vel", C.c_double), ("peak_vel_limit", C.c_double),
+                ("peak_acc_ratio", C.c_double), ("peak_acc", C.c_double), ("peak_acc_limit", C.c_double), ("end_time", C.c_double),
+                ("samples", C.c_int32), ("vel_sample", C.c_int32), ("vel_agent", C.c_int32), ("vel_axis", C.c_int32),
+                ("acc_sample", C.c_int32), ("acc_agent", C.c_int32), ("acc_axis", C.c_int32), ("stored", C.c_int32), ("status", C.c_int32)]
+
+
 class rbp_mission_buf(C.Structure):
     _fields_ = [("N", C.c_int32), ("start", c_double_p), ("goal", c_double_p), ("radius", c_double_p),
                 ("speed", c_double_p), ("max_vel", c_double_p), ("max_acc", c_double_p)]

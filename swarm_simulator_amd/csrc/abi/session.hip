@@ -109,6 +109,7 @@ struct rbp_session {
     JointShard shard{};
     char* shard_buf = nullptr;
     char* report_buf = nullptr;  // rbp_session_report: K reports and the pair kernel's partial minima (report_workspace_bytes), reserved by the first call
+    char* dynamics_buf = nullptr;  // rbp_session_dynamics: K structs and the state kernel's partial peaks (dynamics_workspace_bytes), reserved by the first call
 };
 
 // waits for the session's asynchronous joint run, if one is in flight; reports its error once
@@ -135,6 +136,7 @@ size_t rbp_sizeof(int which) {
         case RBP_SIZEOF_SOLVER_OPTS: return sizeof(rbp_solver_opts);
         case RBP_SIZEOF_ECBS_OUT: return sizeof(rbp_ecbs_out);
         case RBP_SIZEOF_REPORT: return sizeof(rbp_report);
+        case RBP_SIZEOF_DYNAMICS: return sizeof(rbp_dynamics);
         default: return 0;
     }
 }
@@ -877,6 +879,35 @@ int rbp_session_report(rbp_session* s, double dt, rbp_report* out, void* stream)
     return RBP_OK;
 }
 
+// The missions' sampled states, limit peaks and ratio curves from where the plans lie (kernels/dynamics.hip): the report's inputs and the
+// agents' limits are read in place, K structs come back in one copy (per chunk of missions where a destination is on the host), states and
+// curves go where the caller wants them, and nothing of the session is written.
+int rbp_session_dynamics(rbp_session* s, double dt, rbp_dynamics* out, double* states, double* curves, int32_t S_stride, void* stream) {
+    if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_dynamics: null argument");
+    if (!(dt > 0)) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_dynamics: dt must be positive");
+    if ((states || curves) && S_stride < 1) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_dynamics: S_stride must be at least 1 where states or curves are given");
+    if (int jrc = join_worker(s)) return jrc;
+    if (!(s->last_stages & RBP_STAGE_PLANNER))
+        return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_dynamics: the session's last run did not include the PLANNER stage: there are no coefficients to sample");
+    const DevSession& d = s->d;
+    if (dynamics_tile(d.N) <= 0)
+        return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_dynamics: " + std::to_string(d.N) + " agents: the positions of one sample do not fit the curve kernel's LDS budget");
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->dynamics_buf) {
+        const hipError_t e = hipMalloc((void**)&s->dynamics_buf, dynamics_workspace_bytes(d.K));
+        if (e != hipSuccess) {
+            s->dynamics_buf = nullptr;
+            return fail(RBP_ERR_HIP, std::string("rbp_session_dynamics: workspace: ") + hipGetErrorString(e));
+        }
+    }
+    DynamicsInputs in{};
+    in.r.K = d.K, in.r.N = d.N, in.r.M_stride = d.M, in.r.Mk = d.Mk, in.r.T = d.T, in.r.coef = d.coef, in.r.radius = d.radius;
+    in.r.ts = d.scalars + SC_TIME_SCALE, in.r.ts_stride = SC_N, in.r.status = d.status;
+    in.r.downwash = d.p.downwash, in.r.dt = dt;
+    in.max_vel = d.max_vel, in.max_acc = d.max_acc;
+    return dynamics_run("rbp_session_dynamics", s->device, in, out, states, curves, S_stride, s->dynamics_buf, (hipStream_t)stream);
+}
+
 int rbp_session_device_arrays(rbp_session* s, int32_t mission, rbp_device_arrays* out) {
     if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "null argument");
     const DevSession& d = s->d;
@@ -946,6 +977,10 @@ void rbp_session_destroy(rbp_session* s) {
     if (s->report_buf) {
         (void)hipSetDevice(s->device);
         (void)hipFree(s->report_buf);
+    }
+    if (s->dynamics_buf) {
+        (void)hipSetDevice(s->device);
+        (void)hipFree(s->dynamics_buf);
     }
     if (s->ctx) {
         s->ctx->busy = false;  // the arena (and the QP workspace) stay with the context

@@ -6,6 +6,7 @@
 #include "rbp_host.h"
 
 #include "common/report_rules.h"
+#include "common/state_rules.h"
 
 #include <cmath>
 #include <cstdio>
@@ -73,6 +74,25 @@ extern "C" int rbp_report_host(const rbp_mission* mission, const rbp_param* para
     out->min_safety_ratio = r.min_safety_ratio, out->total_flight_distance = r.total_flight_distance, out->end_time = r.end_time;
     out->samples = r.samples, out->min_sample = r.min_sample, out->min_qi = r.min_qi, out->min_qj = r.min_qj;
     out->status = 0, out->reserved = 0;
+    return RBP_OK;
+}
+
+// The sampled states, limit peaks and ratio curves by the rule of common/state_rules.h, which the device's dynamics kernels
+// (kernels/dynamics.hip) share.  T arrives scaled, so the scale is 1.
+extern "C" int rbp_dynamics_host(const rbp_mission* mission, const rbp_param* param, int32_t M, const double* T, const double* coef,
+                                 double dt, rbp_dynamics* out, double* states, double* curves, int32_t S_stride) {
+    if (!mission || !param || !T || !coef || !out || !mission->radius || !mission->max_vel || !mission->max_acc || mission->N <= 0 || M <= 0 ||
+        !(dt > 0) || ((states || curves) && S_stride < 1))
+        return RBP_ERR_BAD_ARGUMENT;
+    std::vector<double> scratch((size_t)3 * mission->N);
+    const state_rules::Result r = state_rules::states_sequential(mission->N, M, T, 1.0, coef, mission->radius, mission->max_vel, mission->max_acc,
+                                                                 param->downwash, dt, states, curves, S_stride, scratch.data());
+    out->peak_vel_ratio = r.vel.ratio, out->peak_vel = r.vel.value, out->peak_vel_limit = r.vel.limit;
+    out->peak_acc_ratio = r.acc.ratio, out->peak_acc = r.acc.value, out->peak_acc_limit = r.acc.limit;
+    out->end_time = r.end_time, out->samples = r.samples;
+    out->vel_sample = r.vel.sample, out->vel_agent = r.vel.agent, out->vel_axis = r.vel.axis;
+    out->acc_sample = r.acc.sample, out->acc_agent = r.acc.agent, out->acc_axis = r.acc.axis;
+    out->stored = r.stored, out->status = 0;
     return RBP_OK;
 }
 

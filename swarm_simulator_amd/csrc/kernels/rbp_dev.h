@@ -220,6 +220,23 @@ int report_tile(int N);
 size_t report_workspace_bytes(int K);
 int launch_report(const ReportInputs& in, void* workspace, hipStream_t st);
 
+// kernels/dynamics.hip: the sampled states, limit peaks and ratio curves of K missions (rbp_dynamics of include/rbp.h) from device arrays in
+// a session's layout.  launch_dynamics enqueues its kernels on `st` and allocates nothing; states [K][N][9][S_stride] and curves
+// [K][S_stride][2] are device pointers or null; the K structs are then at the front of `workspace` (dynamics_workspace_bytes(K) bytes of
+// device memory, nothing to initialise).  dynamics_tile(N) == 0: more agents than the curve kernel's LDS budget holds one sample of, which
+// launch_dynamics refuses.  dynamics_run: the same with `states` / `curves` wherever the caller has them -- on `device` (the current one),
+// written in place, or on the host, through bounded staging -- and the structs copied to `out` on the host; it returns when all has arrived.
+struct DynamicsInputs {
+    ReportInputs r;
+    const double* max_vel;  // [K][N][3]
+    const double* max_acc;  // [K][N][3]
+};
+int dynamics_tile(int N);
+size_t dynamics_workspace_bytes(int K);
+int launch_dynamics(const DynamicsInputs& in, double* states, double* curves, int S_stride, void* workspace, hipStream_t st);
+int dynamics_run(const char* who, int device, const DynamicsInputs& in, rbp_dynamics* out, double* states, double* curves, int S_stride,
+                 void* workspace, hipStream_t st);
+
 // launchers (defined in the .hip files)
 int launch_corridor(const DevSession& s, hipStream_t st);
 size_t corridor_lds_bytes(const DevSession& s);  // dynamic LDS of sfc_kernel for this session's shapes

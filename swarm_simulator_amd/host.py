@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _abi as A
-from .types import Mission, Param, PlanResult, Report, World
+from .types import Dynamics, Mission, Param, PlanResult, Report, World
 
 _lib = None
 
@@ -45,6 +45,8 @@ def lib():
                                    A.c_double_p, C.c_double, A.c_double_p, A.c_double_p]
         L.rbp_report_host.argtypes = [C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.c_int32, A.c_double_p,
                                       A.c_double_p, C.c_double, C.POINTER(A.rbp_report)]
+        L.rbp_dynamics_host.argtypes = [C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.c_int32, A.c_double_p, A.c_double_p, C.c_double,
+                                        C.POINTER(A.rbp_dynamics), C.c_void_p, C.c_void_p, C.c_int32]
         L.rbp_write_coef_csv.argtypes = [C.c_char_p, C.c_int32, C.c_int32, A.c_double_p, A.c_double_p]
         L.rbp_write_qp_lp.argtypes = [C.c_char_p, C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.POINTER(A.rbp_plan), C.c_int32,
                                       A.c_double_p]
@@ -189,6 +191,31 @@ def report(mission: Mission, param: Param, plan: PlanResult, dt=0.1) -> Report:
     if rc:
         raise ValueError(f"rbp_report_host rc={rc}")
     return Report.from_c(out)
+
+
+def dynamics(mission: Mission, param: Param, plan: PlanResult, dt=0.1, states=None, curves=None):
+    """the plan's limit peaks as a Dynamics, by the sequential loop the device shares (csrc/common/state_rules.h): what
+    planner.Session.dynamics / planner.dynamics_coefs return for this plan, bit for bit.  states [N][9][S] and curves [S][2]: None or
+    C-contiguous float64 arrays with one S, written in place up to the plan's samples where samples <= S (Dynamics.stored), else untouched."""
+    S = 0
+    for a in (states, curves):
+        if a is not None and (a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"]):
+            raise ValueError("states / curves must be C-contiguous float64 arrays")
+    if states is not None:
+        S = states.shape[-1]
+        if states.shape != (plan.N, 9, S):
+            raise ValueError(f"states must be [N][9][S], not {states.shape}")
+    if curves is not None:
+        if curves.ndim != 2 or curves.shape[1] != 2 or (states is not None and curves.shape[0] != S):
+            raise ValueError(f"curves must be [S][2] with the S of states, not {curves.shape}")
+        S = curves.shape[0]
+    ms, ps = mission.c_struct(), param.c_struct()
+    out = A.rbp_dynamics()
+    rc = lib().rbp_dynamics_host(C.byref(ms), C.byref(ps), plan.M, A.ptr(plan.T, A.c_double_p), A.ptr(plan.coef, A.c_double_p), dt, C.byref(out),
+                                 C.c_void_p(None if states is None else states.ctypes.data), C.c_void_p(None if curves is None else curves.ctypes.data), S)
+    if rc:
+        raise ValueError(f"rbp_dynamics_host rc={rc}")
+    return Dynamics.from_c(out)
 
 
 def write_coef_csv(directory, plan: PlanResult):

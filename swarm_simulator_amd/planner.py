@@ -11,7 +11,7 @@ import ctypes as C
 import os
 
 from . import _abi as A
-from .types import DeviceWorld, Mission, Param, PlanResult, Report, World
+from .types import DeviceWorld, Dynamics, Mission, Param, PlanResult, Report, World
 
 _lib = None
 
@@ -134,6 +134,11 @@ def lib():
                                          C.c_double, C.c_double, P(A.rbp_report)]
             if L.rbp_sizeof(A.RBP_SIZEOF_REPORT) != C.sizeof(A.rbp_report):
                 raise RbpLibraryMissing(f"{path}: sizeof(rbp_report) is {L.rbp_sizeof(A.RBP_SIZEOF_REPORT)} in the library, {C.sizeof(A.rbp_report)} in this binding")
+            L.rbp_session_dynamics.argtypes = [C.c_void_p, C.c_double, P(A.rbp_dynamics), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+            L.rbp_dev_dynamics.argtypes = [C.c_int, C.c_int32, C.c_int32, A.c_int32_p, C.c_int32, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p,
+                                           A.c_double_p, A.c_double_p, C.c_double, C.c_double, P(A.rbp_dynamics), C.c_void_p, C.c_void_p, C.c_int32]
+            if L.rbp_sizeof(A.RBP_SIZEOF_DYNAMICS) != C.sizeof(A.rbp_dynamics):
+                raise RbpLibraryMissing(f"{path}: sizeof(rbp_dynamics) is {L.rbp_sizeof(A.RBP_SIZEOF_DYNAMICS)} in the library, {C.sizeof(A.rbp_dynamics)} in this binding")
         except AttributeError:
             if not os.environ.get("RBP_HIP_LIB"):
                 raise
@@ -171,6 +176,7 @@ EXPORTED_SYMBOLS = [
     "rbp_dev_worlds_ecbs_obstacles", "rbp_dev_ecbs_plan_masks", "rbp_dev_worlds_ecbs_plan",
     "rbp_dev_worlds_ecbs_search", "rbp_dev_ecbs_count", "rbp_dev_ecbs_download", "rbp_dev_ecbs_destroy", "rbp_session_create_from_ecbs",
     "rbp_session_report", "rbp_dev_report",
+    "rbp_session_dynamics", "rbp_dev_dynamics",
 ]
 
 
@@ -441,6 +447,37 @@ class Session:
             raise RuntimeError(f"rbp_session_report rc={rc}: {last_error()}")
         return [Report.from_c(r) for r in out]
 
+    def dynamics(self, dt=0.1, states=False, curves=False, device_out=False, stream=None):
+        """the missions' limit peaks and, where asked for, their sampled states and ratio curves, computed where the plans lie
+        (rbp_session_dynamics): (records, states, curves) -- K Dynamics records, the bits host.dynamics gives for the downloaded plans;
+        states [K][N][9][S] (agent, row = derivative * 3 + axis, sample) and curves [K][S][2] (smallest, largest safety ratio of a sample),
+        or None where not asked for.  S is the largest number of samples of a mission, from report() (at least 1); mission k's entries
+        beyond records[k].samples are zero.  device_out: the two arrays are torch tensors on the session's device, written in place by
+        the kernels; otherwise numpy arrays.  Nothing of the session changes; a mission whose status is not 0 comes back with that
+        status, nothing computed and nothing stored."""
+        import numpy as np
+        S, N = 1, self.plans[0].N
+        if states or curves:
+            S = max([1] + [r.samples for r in self.report(dt, stream)])
+        out = (A.rbp_dynamics * self.K)()
+        if device_out:
+            import torch
+            dev = torch.device("cuda", self.device)
+            st = torch.zeros((self.K, N, 9, S), dtype=torch.float64, device=dev) if states else None
+            cu = torch.zeros((self.K, S, 2), dtype=torch.float64, device=dev) if curves else None
+            torch.cuda.synchronize(dev)   # (the zeros are written on torch's stream, the kernels run on `stream`)
+            sp, cp = (st.data_ptr() if states else None), (cu.data_ptr() if curves else None)
+        else:
+            st = np.zeros((self.K, N, 9, S)) if states else None
+            cu = np.zeros((self.K, S, 2)) if curves else None
+            sp, cp = (st.ctypes.data if states else None), (cu.ctypes.data if curves else None)
+        rc = lib().rbp_session_dynamics(self._h, dt, out, C.c_void_p(sp), C.c_void_p(cp), S, C.c_void_p(stream or 0))
+        if rc == A.RBP_ERR_BAD_ARGUMENT:
+            raise ValueError(f"rbp_session_dynamics rc={rc}: {last_error()}")
+        if rc:
+            raise RuntimeError(f"rbp_session_dynamics rc={rc}: {last_error()}")
+        return [Dynamics.from_c(r) for r in out], st, cu
+
     def reserve_workspace(self, stream=None):
         """reserve the QP workspace now (otherwise the first PLANNER run does)"""
         rc = lib().rbp_session_reserve_workspace(self._h, C.c_void_p(stream or 0))
@@ -519,6 +556,44 @@ def report_coefs(M, T, coef, radius, downwash, dt=0.1, time_scale=None, device=0
     if rc:
         raise RuntimeError(f"rbp_dev_report rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
     return [Report.from_c(r) for r in out]
+
+
+def dynamics_coefs(M, T, coef, radius, max_vel, max_acc, downwash, dt=0.1, time_scale=None, states=None, curves=None, S_stride=0, device=0):
+    """rbp_dev_dynamics: the dynamics kernels on the caller's arrays, uploaded once, in report_coefs' layout with max_vel / max_acc
+    [K][N][3].  states / curves: None, a C-contiguous float64 numpy array ([K][N][9][S_stride] / [K][S_stride][2]) or a torch tensor of
+    that shape on `device`, written in place -- a mission's entries up to its samples where samples <= S_stride, nothing else.
+    Returns K Dynamics records, the bits host.dynamics gives for the scaled times."""
+    import numpy as np
+    M = np.ascontiguousarray(M, np.int32).reshape(-1)
+    K = len(M)
+    T, coef, radius = A.as_f64(T).reshape(K, -1), A.as_f64(coef), A.as_f64(radius).reshape(K, -1)
+    S, N = T.shape[1] - 1, radius.shape[1]
+    max_vel, max_acc = A.as_f64(max_vel).reshape(K, N, 3), A.as_f64(max_acc).reshape(K, N, 3)
+    if coef.size != K * N * 3 * 6 * S:
+        raise ValueError(f"coef holds {coef.size} doubles, K * N * 3 * 6 * M_stride = {K * N * 3 * 6 * S}")
+    ts = None if time_scale is None else A.as_f64(time_scale).reshape(K)
+
+    def address(a, count):
+        if a is None:
+            return None
+        if isinstance(a, np.ndarray):
+            if a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"] or a.size != count:
+                raise ValueError(f"a destination must be a C-contiguous float64 array of {count} elements")
+            return a.ctypes.data
+        if str(a.dtype) != "torch.float64" or not a.is_contiguous() or a.numel() != count:
+            raise ValueError(f"a destination must be a contiguous float64 tensor of {count} elements")
+        return a.data_ptr()
+
+    sp, cp = address(states, K * N * 9 * S_stride), address(curves, K * S_stride * 2)
+    out = (A.rbp_dynamics * K)()
+    rc = lib().rbp_dev_dynamics(device, K, N, A.ptr(M, A.c_int32_p), S, A.ptr(T, A.c_double_p), A.ptr(ts, A.c_double_p), A.ptr(coef, A.c_double_p),
+                                A.ptr(radius, A.c_double_p), A.ptr(max_vel, A.c_double_p), A.ptr(max_acc, A.c_double_p), downwash, dt, out,
+                                C.c_void_p(sp), C.c_void_p(cp), int(S_stride))
+    if rc == A.RBP_ERR_BAD_ARGUMENT:
+        raise ValueError(f"rbp_dev_dynamics rc={rc}: {last_error()}")
+    if rc:
+        raise RuntimeError(f"rbp_dev_dynamics rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+    return [Dynamics.from_c(r) for r in out]
 
 
 def build_world(keys, res, param: Param, max_dist=1.0):

@@ -11,8 +11,11 @@ With --device-report (only with --device-worlds --mode batched) the safety ratio
 planner.Session.report() on the resident plans instead of host.validate per downloaded plan: the same line format, the numbers of the
 rule the device and host.report share (csrc/common/report_rules.h; they differ from host.validate's by rounding).  Without --csv nothing
 but K small records and two scalars per map is downloaded.
+With --device-dynamics (only with --device-worlds --mode batched; off by default) ONE planner.Session.dynamics() on the resident plans adds a
+line per map with the largest |velocity| / max_vel and |acceleration| / max_acc over all samples, agents and axes and where they lie
+(csrc/common/state_rules.h): whether the plan respects its limits at the samples, the reference's third acceptance signal.
 
-usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]] [--device-report]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
+usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]] [--device-report] [--device-dynamics]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
        [--batch-size 4] [--iteration 1] [--joint] [--csv DIR]
 """
 import argparse
@@ -33,6 +36,8 @@ def main(argv=None):
                     "search's resident results, no initial trajectory passes through the host")
     ap.add_argument("--device-report", action="store_true", help="with --device-worlds --mode batched: safety ratio and flight distance of all maps from one "
                     "report call on the device (planner.Session.report); without --csv the coefficients are not downloaded")
+    ap.add_argument("--device-dynamics", action="store_true", help="with --device-worlds --mode batched: one more line per map with both limit peak ratios and "
+                    "where they lie, from one dynamics call on the device (planner.Session.dynamics)")
     ap.add_argument("--mission", default="mission_64agents_15.json")
     ap.add_argument("--maps", default="1-50")
     ap.add_argument("--mode", choices=["serial", "batched"], default="serial")
@@ -43,6 +48,8 @@ def main(argv=None):
     args, rest = ap.parse_known_args(argv)
     if args.device_report and not (args.device_worlds and args.mode == "batched"):
         ap.error("--device-report needs --device-worlds --mode batched")
+    if args.device_dynamics and not (args.device_worlds and args.mode == "batched"):
+        ap.error("--device-dynamics needs --device-worlds --mode batched")
     if args.device_ecbs and not args.device_worlds:
         ap.error("--device-ecbs needs --device-worlds")
     if args.device_handoff and not (args.device_ecbs and args.mode == "batched"):
@@ -132,6 +139,7 @@ def run_and_report(args, sess, maps, plans, mission, param):
     sess.run()
     status = sess.download() if download else None
     records = sess.report() if args.device_report else [None] * sess.K
+    peaks = sess.dynamics()[0] if args.device_dynamics else [None] * sess.K
     dt = time.perf_counter() - t0
     print(f"BoxGenerator + SwarmPlanner runtime, {sess.K} maps in one session: {dt:.6f} "
           f"({sess.K * mission.qn / dt:.1f} agent-trajectories/s incl. {'download' if download else 'report'})")
@@ -140,7 +148,7 @@ def run_and_report(args, sess, maps, plans, mission, param):
         status = [r.status for r in records]
         plans = [SimpleNamespace(total_cost=float(c), time_scale=float(ts) if ts > 0 else 1.0, T=[r.end_time]) for (ts, c), r in zip(sc, records)]
     sess.close()
-    for i, p, st, rec in zip(maps, plans, status, records):
+    for i, p, st, rec, pk in zip(maps, plans, status, records, peaks):
         if st:
             print(f"[ERROR] map{i}: status {st}")
             return -1
@@ -148,7 +156,17 @@ def run_and_report(args, sess, maps, plans, mission, param):
             test_all.report(i, mission, param, p, args.csv)
         else:
             report_line(i, p, rec, args.csv)
+        if pk is not None:
+            dynamics_line(i, pk)
     return 0
+
+
+def dynamics_line(i, d):
+    """--device-dynamics: both limit peak ratios of a types.Dynamics and where they lie (agent, axis, sample); `none` for a plan without one"""
+    def where(ratio, agent, axis, sample):
+        return f"{ratio:.4f} (agent {agent} {'xyz'[axis]} sample {sample})" if sample >= 0 else "none"
+    print(f"map{i}: peak velocity ratio {where(d.peak_vel_ratio, d.vel_agent, d.vel_axis, d.vel_sample)}  "
+          f"peak acceleration ratio {where(d.peak_acc_ratio, d.acc_agent, d.acc_axis, d.acc_sample)}  samples {d.samples}")
 
 
 def report_line(i, plan, record, csv_dir):

@@ -197,6 +197,41 @@ class Report:
         return tuple(int(x) for x in f) + (self.samples, self.min_sample, self.min_qi, self.min_qj, self.status)
 
 
+@dataclass
+class Dynamics:
+    """rbp_dynamics (include/rbp.h): a mission's limit peaks -- the largest |v| / max_vel and |a| / max_acc over samples, agents and axes,
+    with the value itself, its limit and where it lies (-1: none) -- its end time and samples, and whether its states / curves were
+    written.  status != 0: nothing computed."""
+    peak_vel_ratio: float
+    peak_vel: float
+    peak_vel_limit: float
+    peak_acc_ratio: float
+    peak_acc: float
+    peak_acc_limit: float
+    end_time: float
+    samples: int
+    vel_sample: int
+    vel_agent: int
+    vel_axis: int
+    acc_sample: int
+    acc_agent: int
+    acc_axis: int
+    stored: int = 0
+    status: int = 0
+
+    FIELDS = ("peak_vel_ratio", "peak_vel", "peak_vel_limit", "peak_acc_ratio", "peak_acc", "peak_acc_limit", "end_time", "samples",
+              "vel_sample", "vel_agent", "vel_axis", "acc_sample", "acc_agent", "acc_axis", "stored", "status")
+
+    @classmethod
+    def from_c(cls, r):
+        return cls(*[getattr(r, n) for n in cls.FIELDS])
+
+    def bits(self):
+        """the record with its doubles as bit patterns: what two evaluations of the one rule must agree on"""
+        f = np.array([getattr(self, n) for n in self.FIELDS[:7]], np.float64).view(np.uint64)
+        return tuple(int(x) for x in f) + tuple(getattr(self, n) for n in self.FIELDS[7:])
+
+
 class PlanResult:
     """sp_const.hpp:21-28 as flat arrays (include/rbp.h rbp_plan)."""
 
