@@ -346,7 +346,7 @@ void rbp_release_thread_context(void);
                               4: rbp_solver_opts (the library no longer reads environment variables); 5: rbp_session_shard_joint, RBP_ERR_EXCHANGE;
                               6: rbp_param.timescale_rule, rbp_plan.time_scale_alt */
 enum { RBP_SIZEOF_WORLD = 0, RBP_SIZEOF_MISSION = 1, RBP_SIZEOF_PARAM = 2, RBP_SIZEOF_PLAN = 3, RBP_SIZEOF_COUNTERS = 4, RBP_SIZEOF_DEVICE_ARRAYS = 5,
-       RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7, RBP_SIZEOF_REPORT = 8, RBP_SIZEOF_DYNAMICS = 9 };
+       RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7, RBP_SIZEOF_REPORT = 8, RBP_SIZEOF_DYNAMICS = 9, RBP_SIZEOF_CLEARANCE = 10 };
 int rbp_abi_version(void);
 size_t rbp_sizeof(int which);
 const char* rbp_version(void);
@@ -524,6 +524,44 @@ int rbp_dev_dynamics(int device, int32_t K, int32_t N, const int32_t* M, int32_t
                      const double* radius, const double* max_vel, const double* max_acc,
                      double downwash, double dt, rbp_dynamics* out,
                      double* states, double* curves, int32_t S_stride);
+
+/* ---- the clearance of resident plans to the obstacles (does the plan hit anything, and where is it closest) ----
+ * The distance grid's value under every agent at every sample t = j * dt, j < samples, less the agent's radius, by the rule of
+ * csrc/common/clearance_rules.h, which the kernels (kernels/clearance.hip) and rbp_clearance_host of rbp_host.h share: both return the same
+ * bits.  Times, samples, the segment of a sample and positions are the report's (report_rules.h).  The lookup is
+ * DynamicEDTOctomap::getDistance(point3d) as rbp_world describes it: the coordinate rounded to float, the key floor((1 / res) * (double)pf),
+ * -1 outside the grid.  A (sample, agent) item is a HIT where the grid reads less than radius - 1e-6 (rbp_corridor.hpp:67, SP_EPSILON_FLOAT)
+ * and an OUTSIDE where its lookup left the grid (also a hit for every radius above -1 + 1e-6, as in the reference).  The minimum names the
+ * lexicographically first (sample, agent) among equal clearances; a NaN clearance (a NaN radius) is never the minimum.
+ * agent_clearance [K][N] (NULL: not wanted): agent a's smallest clearance over its samples, 1e9 where it has none; the row of a mission that
+ * is not computed (a status, or samples = -1) is left untouched.  It may be a host pointer or a device pointer on the plans' device
+ * (classified with hipPointerGetAttributes as rbp_world.dist is; another device: RBP_ERR_BAD_ARGUMENT): a device destination is written in
+ * place by the kernels, a host destination goes through one staging buffer and one copy.
+ * rbp_session_clearance: of a session's K missions, from its own coef, T, time scale, radius and status and the grid of each mission's
+ *   world, all of which stay in HBM; waits for an asynchronous solve like every call, enqueues two kernels on `stream`, copies K structs
+ *   back in one copy and returns when they have arrived.  Nothing of the session changes.  A mission whose status is not 0 gets that status
+ *   and nothing computed.  RBP_ERR_BAD_ARGUMENT: a session whose last run did not include the PLANNER stage; and, before a device is looked
+ *   for, a null pointer or dt <= 0 -- as rbp_session_report.  (A session cannot exist without a grid for every mission: rbp_session_create
+ *   refuses a world without one, and rbp_session_create_from_ecbs takes the resident grids of the search's set.)
+ * rbp_dev_clearance: the same kernels on a caller's host arrays in rbp_dev_report's layout, uploaded once, and K worlds.  worlds[k].dist
+ *   may be a host grid, uploaded once per distinct (pointer, shape), or a device grid on `device`, referenced in place (another device:
+ *   RBP_ERR_BAD_ARGUMENT).  Argument errors (a null pointer, K, N <= 0, an M[k] outside 1..M_stride, dt, res or a time scale <= 0, a
+ *   dim <= 0) are RBP_ERR_BAD_ARGUMENT before a device is looked for. */
+typedef struct rbp_clearance {
+    double  min_clearance;   /* metres; 1e9: no sample.  Saturates at (grid clamp - radius): the grid is clamped at its maxDist */
+    double  min_dist;        /* the grid's value at the minimum (-1: outside); 0 where there is none */
+    double  end_time;        /* Ts[M]: the mission's last segment time, scaled */
+    int64_t hits, outside;   /* (sample, agent) counts */
+    int32_t samples;         /* as rbp_report.samples, -1 included (then nothing else is computed) */
+    int32_t min_sample, min_agent;  /* where the minimum is; -1: none */
+    int32_t status;          /* the mission's status; != 0: nothing computed, zeros, indices -1 */
+} rbp_clearance;
+int rbp_session_clearance(rbp_session* s, double dt, rbp_clearance* out /* [K] */,
+                          double* agent_clearance /* [K][N] or NULL; host or device pointer */, void* stream);
+int rbp_dev_clearance(int device, int32_t K, int32_t N, const int32_t* M, int32_t M_stride, const double* T,
+                      const double* time_scale, const double* coef, const double* radius,
+                      const rbp_world* worlds /* [K]; dist host or device */, double dt,
+                      rbp_clearance* out, double* agent_clearance);
 
 const char* rbp_last_error(void);
 int rbp_device_count(void);

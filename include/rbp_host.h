@@ -96,6 +96,13 @@ int rbp_report_host(const rbp_mission* mission, const rbp_param* param, int32_t 
 int rbp_dynamics_host(const rbp_mission* mission, const rbp_param* param, int32_t M, const double* T, const double* coef,
                       double dt, rbp_dynamics* out, double* states, double* curves, int32_t S_stride);
 
+/* The clearance of one plan to the obstacles of its world as an rbp_clearance (rbp.h), by the sequential loop of
+ * csrc/common/clearance_rules.h that the device shares: what rbp_session_clearance / rbp_dev_clearance return for the same plan and grid,
+ * bit for bit, and their reference.  world->dist is a host grid; T as downloaded (scaled); radius is the mission's.  agent_clearance [N]
+ * may be NULL; it is written only where the samples are evaluated (out->samples >= 0).  out->status is 0. */
+int rbp_clearance_host(const rbp_world* world, const rbp_mission* mission, int32_t M, const double* T,
+                       const double* coef, double dt, rbp_clearance* out, double* agent_clearance /* [N] or NULL */);
+
 /* crazyswarm CSV of rbp_planner.hpp:295-324 (one file per agent: <dir>/coef<qi+1>.csv) */
 int rbp_write_coef_csv(const char* dir, int32_t N, int32_t M, const double* T, const double* coef);
 

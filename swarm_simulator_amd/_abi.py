@@ -117,6 +117,14 @@ class rbp_dynamics(C.Structure):
                 ("acc_sample", C.c_int32), ("acc_agent", C.c_int32), ("acc_axis", C.c_int32), ("stored", C.c_int32), ("status", C.c_int32)]
 
 
+RBP_SIZEOF_CLEARANCE = 10
+
+
+class rbp_clearance(C.Structure):
+    _fields_ = [("min_clearance", C.c_double), ("min_dist", C.c_double), ("end_time", C.c_double), ("hits", C.c_int64), ("outside", C.c_int64),
+                ("samples", C.c_int32), ("min_sample", C.c_int32), ("min_agent", C.c_int32), ("status", C.c_int32)]
+
+
 class rbp_mission_buf(C.Structure):
     _fields_ = [("N", C.c_int32), ("start", c_double_p), ("goal", c_double_p), ("radius", c_double_p),
                 ("speed", c_double_p), ("max_vel", c_double_p), ("max_acc", c_double_p)]

@@ -110,6 +110,7 @@ struct rbp_session {
     char* shard_buf = nullptr;
     char* report_buf = nullptr;  // rbp_session_report: K reports and the pair kernel's partial minima (report_workspace_bytes), reserved by the first call
     char* dynamics_buf = nullptr;  // rbp_session_dynamics: K structs and the state kernel's partial peaks (dynamics_workspace_bytes), reserved by the first call
+    char* clearance_buf = nullptr;  // rbp_session_clearance: K structs and the agent kernel's records (clearance_workspace_bytes), reserved by the first call
 };
 
 // waits for the session's asynchronous joint run, if one is in flight; reports its error once
@@ -137,6 +138,7 @@ size_t rbp_sizeof(int which) {
         case RBP_SIZEOF_ECBS_OUT: return sizeof(rbp_ecbs_out);
         case RBP_SIZEOF_REPORT: return sizeof(rbp_report);
         case RBP_SIZEOF_DYNAMICS: return sizeof(rbp_dynamics);
+        case RBP_SIZEOF_CLEARANCE: return sizeof(rbp_clearance);
         default: return 0;
     }
 }
@@ -908,6 +910,32 @@ int rbp_session_dynamics(rbp_session* s, double dt, rbp_dynamics* out, double* s
     return dynamics_run("rbp_session_dynamics", s->device, in, out, states, curves, S_stride, s->dynamics_buf, (hipStream_t)stream);
 }
 
+// The missions' clearance to the obstacles from where the plans and the grids lie (kernels/clearance.hip): the report's inputs and the
+// session's worlds are read in place, K structs come back in one copy, the agents' clearances go where the caller wants them, and nothing
+// of the session is written.
+int rbp_session_clearance(rbp_session* s, double dt, rbp_clearance* out, double* agent_clearance, void* stream) {
+    if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_clearance: null argument");
+    if (!(dt > 0)) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_clearance: dt must be positive");
+    if (int jrc = join_worker(s)) return jrc;
+    if (!(s->last_stages & RBP_STAGE_PLANNER))
+        return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_clearance: the session's last run did not include the PLANNER stage: there are no coefficients to look up");
+    const DevSession& d = s->d;
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->clearance_buf) {
+        const hipError_t e = hipMalloc((void**)&s->clearance_buf, clearance_workspace_bytes(d.K, d.N));
+        if (e != hipSuccess) {
+            s->clearance_buf = nullptr;
+            return fail(RBP_ERR_HIP, std::string("rbp_session_clearance: workspace: ") + hipGetErrorString(e));
+        }
+    }
+    ClearanceInputs in{};
+    in.r.K = d.K, in.r.N = d.N, in.r.M_stride = d.M, in.r.Mk = d.Mk, in.r.T = d.T, in.r.coef = d.coef, in.r.radius = d.radius;
+    in.r.ts = d.scalars + SC_TIME_SCALE, in.r.ts_stride = SC_N, in.r.status = d.status;
+    in.r.downwash = d.p.downwash, in.r.dt = dt;
+    in.worlds = d.worlds;
+    return clearance_run("rbp_session_clearance", s->device, in, out, agent_clearance, s->clearance_buf, (hipStream_t)stream);
+}
+
 int rbp_session_device_arrays(rbp_session* s, int32_t mission, rbp_device_arrays* out) {
     if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "null argument");
     const DevSession& d = s->d;
@@ -981,6 +1009,10 @@ void rbp_session_destroy(rbp_session* s) {
     if (s->dynamics_buf) {
         (void)hipSetDevice(s->device);
         (void)hipFree(s->dynamics_buf);
+    }
+    if (s->clearance_buf) {
+        (void)hipSetDevice(s->device);
+        (void)hipFree(s->clearance_buf);
     }
     if (s->ctx) {
         s->ctx->busy = false;  // the arena (and the QP workspace) stay with the context

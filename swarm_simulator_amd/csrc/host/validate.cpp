@@ -5,6 +5,7 @@
 //   coef CSV           rbp_planner.hpp:295-324
 #include "rbp_host.h"
 
+#include "common/clearance_rules.h"
 #include "common/report_rules.h"
 #include "common/state_rules.h"
 
@@ -93,6 +94,21 @@ extern "C" int rbp_dynamics_host(const rbp_mission* mission, const rbp_param* pa
     out->vel_sample = r.vel.sample, out->vel_agent = r.vel.agent, out->vel_axis = r.vel.axis;
     out->acc_sample = r.acc.sample, out->acc_agent = r.acc.agent, out->acc_axis = r.acc.axis;
     out->stored = r.stored, out->status = 0;
+    return RBP_OK;
+}
+
+// The plan's clearance to the obstacles of its world by the rule of common/clearance_rules.h, which the device's clearance kernels
+// (kernels/clearance.hip) share.  T arrives scaled, so the scale is 1.
+extern "C" int rbp_clearance_host(const rbp_world* world, const rbp_mission* mission, int32_t M, const double* T, const double* coef, double dt,
+                                  rbp_clearance* out, double* agent_clearance) {
+    if (!world || !mission || !T || !coef || !out || !world->dist || !mission->radius || mission->N <= 0 || M <= 0 || !(dt > 0) || !(world->res > 0) ||
+        world->dim[0] <= 0 || world->dim[1] <= 0 || world->dim[2] <= 0)
+        return RBP_ERR_BAD_ARGUMENT;
+    const clearance_rules::Result r = clearance_rules::clearance_sequential(mission->N, M, T, 1.0, coef, mission->radius, world->dim, world->key_min,
+                                                                            world->res, world->dist, dt, agent_clearance);
+    out->min_clearance = r.min.clearance, out->min_dist = r.min.dist, out->end_time = r.end_time;
+    out->hits = r.hits, out->outside = r.outside;
+    out->samples = r.samples, out->min_sample = r.min.sample, out->min_agent = r.min.agent, out->status = 0;
     return RBP_OK;
 }
 

@@ -237,6 +237,20 @@ int launch_dynamics(const DynamicsInputs& in, double* states, double* curves, in
 int dynamics_run(const char* who, int device, const DynamicsInputs& in, rbp_dynamics* out, double* states, double* curves, int S_stride,
                  void* workspace, hipStream_t st);
 
+// kernels/clearance.hip: the clearance of K missions to the obstacles of their worlds (rbp_clearance of include/rbp.h) from device arrays
+// in a session's layout and a device array of K worlds whose grids lie on the device.  launch_clearance enqueues its two kernels on `st` and
+// allocates nothing; agent_clearance [K][N] is a device pointer or null; the K structs are then at the front of `workspace`
+// (clearance_workspace_bytes(K, N) bytes of device memory, nothing to initialise).  clearance_run: the same with `agent_clearance` wherever
+// the caller has it -- on `device` (the current one), written in place, or on the host, through one staging buffer -- and the structs
+// copied to `out` on the host; it returns when all has arrived.  (r.downwash is not read.)
+struct ClearanceInputs {
+    ReportInputs r;
+    const DevWorld* worlds;  // [K] on the device
+};
+size_t clearance_workspace_bytes(int K, int N);
+int launch_clearance(const ClearanceInputs& in, double* agent_clearance, void* workspace, hipStream_t st);
+int clearance_run(const char* who, int device, const ClearanceInputs& in, rbp_clearance* out, double* agent_clearance, void* workspace, hipStream_t st);
+
 // launchers (defined in the .hip files)
 int launch_corridor(const DevSession& s, hipStream_t st);
 size_t corridor_lds_bytes(const DevSession& s);  // dynamic LDS of sfc_kernel for this session's shapes

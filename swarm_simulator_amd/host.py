@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _abi as A
-from .types import Dynamics, Mission, Param, PlanResult, Report, World
+from .types import Clearance, Dynamics, Mission, Param, PlanResult, Report, World
 
 _lib = None
 
@@ -47,7 +47,9 @@ def lib():
                                       A.c_double_p, C.c_double, C.POINTER(A.rbp_report)]
         L.rbp_dynamics_host.argtypes = [C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.c_int32, A.c_double_p, A.c_double_p, C.c_double,
                                         C.POINTER(A.rbp_dynamics), C.c_void_p, C.c_void_p, C.c_int32]
-        L.rbp_write_coef_csv.argtypes = [C.c_char_p, C.c_int32, C.c_int32, A.c_double_p, A.c_double_p]
+        L.rbp_clearance_host.argtypes = [C.POINTER(A.rbp_world), C.POINTER(A.rbp_mission), C.c_int32, A.c_double_p, A.c_double_p, C.c_double,
+                                         C.POINTER(A.rbp_clearance), A.c_double_p]
+        L.rbp_write_coef_csv.argtypes =[C.c_char_p, C.c_int32, C.c_int32, A.c_double_p, A.c_double_p]
         L.rbp_write_qp_lp.argtypes = [C.c_char_p, C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.POINTER(A.rbp_plan), C.c_int32,
                                       A.c_double_p]
         _lib = L
@@ -216,6 +218,20 @@ def dynamics(mission: Mission, param: Param, plan: PlanResult, dt=0.1, states=No
     if rc:
         raise ValueError(f"rbp_dynamics_host rc={rc}")
     return Dynamics.from_c(out)
+
+
+def clearance(world: World, mission: Mission, plan: PlanResult, dt=0.1, per_agent=False):
+    """the plan's clearance to the obstacles of `world` as a Clearance, by the sequential loop the device shares
+    (csrc/common/clearance_rules.h): what planner.Session.clearance / planner.clearance_coefs return for this plan and grid, bit for bit.
+    per_agent: returns (Clearance, [N] array of every agent's smallest clearance, 1e9 without a sample)."""
+    ws, ms = world.c_struct(), mission.c_struct()
+    out = A.rbp_clearance()
+    agents = np.full(plan.N, 1e9) if per_agent else None
+    rc = lib().rbp_clearance_host(C.byref(ws), C.byref(ms), plan.M, A.ptr(plan.T, A.c_double_p), A.ptr(plan.coef, A.c_double_p), dt, C.byref(out),
+                                  A.ptr(agents, A.c_double_p))
+    if rc:
+        raise ValueError(f"rbp_clearance_host rc={rc}")
+    return (Clearance.from_c(out), agents) if per_agent else Clearance.from_c(out)
 
 
 def write_coef_csv(directory, plan: PlanResult):

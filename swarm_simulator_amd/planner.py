@@ -11,7 +11,7 @@ import ctypes as C
 import os
 
 from . import _abi as A
-from .types import DeviceWorld, Dynamics, Mission, Param, PlanResult, Report, World
+from .types import Clearance, DeviceWorld, Dynamics, Mission, Param, PlanResult, Report, World
 
 _lib = None
 
@@ -139,6 +139,11 @@ def lib():
                                            A.c_double_p, A.c_double_p, C.c_double, C.c_double, P(A.rbp_dynamics), C.c_void_p, C.c_void_p, C.c_int32]
             if L.rbp_sizeof(A.RBP_SIZEOF_DYNAMICS) != C.sizeof(A.rbp_dynamics):
                 raise RbpLibraryMissing(f"{path}: sizeof(rbp_dynamics) is {L.rbp_sizeof(A.RBP_SIZEOF_DYNAMICS)} in the library, {C.sizeof(A.rbp_dynamics)} in this binding")
+            L.rbp_session_clearance.argtypes = [C.c_void_p, C.c_double, P(A.rbp_clearance), C.c_void_p, C.c_void_p]
+            L.rbp_dev_clearance.argtypes = [C.c_int, C.c_int32, C.c_int32, A.c_int32_p, C.c_int32, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p,
+                                            P(A.rbp_world), C.c_double, P(A.rbp_clearance), C.c_void_p]
+            if L.rbp_sizeof(A.RBP_SIZEOF_CLEARANCE) != C.sizeof(A.rbp_clearance):
+                raise RbpLibraryMissing(f"{path}: sizeof(rbp_clearance) is {L.rbp_sizeof(A.RBP_SIZEOF_CLEARANCE)} in the library, {C.sizeof(A.rbp_clearance)} in this binding")
         except AttributeError:
             if not os.environ.get("RBP_HIP_LIB"):
                 raise
@@ -177,6 +182,7 @@ EXPORTED_SYMBOLS = [
     "rbp_dev_worlds_ecbs_search", "rbp_dev_ecbs_count", "rbp_dev_ecbs_download", "rbp_dev_ecbs_destroy", "rbp_session_create_from_ecbs",
     "rbp_session_report", "rbp_dev_report",
     "rbp_session_dynamics", "rbp_dev_dynamics",
+    "rbp_session_clearance", "rbp_dev_clearance",
 ]
 
 
@@ -478,6 +484,32 @@ class Session:
             raise RuntimeError(f"rbp_session_dynamics rc={rc}: {last_error()}")
         return [Dynamics.from_c(r) for r in out], st, cu
 
+    def clearance(self, dt=0.1, per_agent=False, device_out=False, stream=None):
+        """the missions' clearance to the obstacles of their worlds, computed where the plans and the grids lie (rbp_session_clearance):
+        (records, agents) -- K Clearance records, the bits host.clearance gives for the downloaded plans on the downloaded grids; agents
+        [K][N], every agent's smallest clearance (1e9 without a sample), or None unless per_agent.  device_out: the array is a torch tensor
+        on the session's device, written in place by the kernel; otherwise a numpy array.  The row of a mission that is not computed keeps
+        its 1e9.  Nothing of the session changes; a mission whose status is not 0 comes back with that status and nothing computed."""
+        import numpy as np
+        N = self.plans[0].N
+        out = (A.rbp_clearance * self.K)()
+        ag, ap = None, None
+        if per_agent and device_out:
+            import torch
+            dev = torch.device("cuda", self.device)
+            ag = torch.full((self.K, N), 1e9, dtype=torch.float64, device=dev)
+            torch.cuda.synchronize(dev)   # (the fill is written on torch's stream, the kernels run on `stream`)
+            ap = ag.data_ptr()
+        elif per_agent:
+            ag = np.full((self.K, N), 1e9)
+            ap = ag.ctypes.data
+        rc = lib().rbp_session_clearance(self._h, dt, out, C.c_void_p(ap), C.c_void_p(stream or 0))
+        if rc == A.RBP_ERR_BAD_ARGUMENT:
+            raise ValueError(f"rbp_session_clearance rc={rc}: {last_error()}")
+        if rc:
+            raise RuntimeError(f"rbp_session_clearance rc={rc}: {last_error()}")
+        return [Clearance.from_c(r) for r in out], ag
+
     def reserve_workspace(self, stream=None):
         """reserve the QP workspace now (otherwise the first PLANNER run does)"""
         rc = lib().rbp_session_reserve_workspace(self._h, C.c_void_p(stream or 0))
@@ -594,6 +626,41 @@ def dynamics_coefs(M, T, coef, radius, max_vel, max_acc, downwash, dt=0.1, time_
     if rc:
         raise RuntimeError(f"rbp_dev_dynamics rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
     return [Dynamics.from_c(r) for r in out]
+
+
+def clearance_coefs(M, T, coef, radius, worlds, dt=0.1, time_scale=None, agent_clearance=None, device=0):
+    """rbp_dev_clearance: the clearance kernels on the caller's arrays, uploaded once, in report_coefs' layout, and K worlds (World: a host
+    grid, uploaded once per distinct grid; DeviceWorld: referenced in place).  agent_clearance: None, a C-contiguous float64 numpy array
+    [K][N] or a torch tensor of that shape on `device`, written in place -- the rows of the missions that are computed, nothing else.
+    Returns K Clearance records, the bits host.clearance gives for the scaled times."""
+    import numpy as np
+    M = np.ascontiguousarray(M, np.int32).reshape(-1)
+    K = len(M)
+    T, coef, radius = A.as_f64(T).reshape(K, -1), A.as_f64(coef), A.as_f64(radius).reshape(K, -1)
+    S, N = T.shape[1] - 1, radius.shape[1]
+    if coef.size != K * N * 3 * 6 * S:
+        raise ValueError(f"coef holds {coef.size} doubles, K * N * 3 * 6 * M_stride = {K * N * 3 * 6 * S}")
+    if len(worlds) != K:
+        raise ValueError(f"{len(worlds)} worlds for {K} missions")
+    ts = None if time_scale is None else A.as_f64(time_scale).reshape(K)
+    ap = None
+    if isinstance(agent_clearance, np.ndarray):
+        if agent_clearance.dtype != np.float64 or not agent_clearance.flags["C_CONTIGUOUS"] or agent_clearance.size != K * N:
+            raise ValueError(f"agent_clearance must be a C-contiguous float64 array of {K * N} elements")
+        ap = agent_clearance.ctypes.data
+    elif agent_clearance is not None:
+        if str(agent_clearance.dtype) != "torch.float64" or not agent_clearance.is_contiguous() or agent_clearance.numel() != K * N:
+            raise ValueError(f"agent_clearance must be a contiguous float64 tensor of {K * N} elements")
+        ap = agent_clearance.data_ptr()
+    ws = (A.rbp_world * K)(*[w.c_struct() for w in worlds])
+    out = (A.rbp_clearance * K)()
+    rc = lib().rbp_dev_clearance(device, K, N, A.ptr(M, A.c_int32_p), S, A.ptr(T, A.c_double_p), A.ptr(ts, A.c_double_p), A.ptr(coef, A.c_double_p),
+                                 A.ptr(radius, A.c_double_p), ws, dt, out, C.c_void_p(ap))
+    if rc == A.RBP_ERR_BAD_ARGUMENT:
+        raise ValueError(f"rbp_dev_clearance rc={rc}: {last_error()}")
+    if rc:
+        raise RuntimeError(f"rbp_dev_clearance rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+    return [Clearance.from_c(r) for r in out]
 
 
 def build_world(keys, res, param: Param, max_dist=1.0):

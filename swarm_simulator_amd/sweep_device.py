@@ -14,8 +14,11 @@ but K small records and two scalars per map is downloaded.
 With --device-dynamics (only with --device-worlds --mode batched; off by default) ONE planner.Session.dynamics() on the resident plans adds a
 line per map with the largest |velocity| / max_vel and |acceleration| / max_acc over all samples, agents and axes and where they lie
 (csrc/common/state_rules.h): whether the plan respects its limits at the samples, the reference's third acceptance signal.
+With --device-clearance (only with --device-worlds --mode batched; off by default) ONE planner.Session.clearance() on the resident plans and
+grids adds a line per map with the smallest clearance to the obstacles, where it lies, and how many (sample, agent) items hit an obstacle
+or left the grid (csrc/common/clearance_rules.h): whether the plan hits anything.
 
-usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]] [--device-report] [--device-dynamics]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
+usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]] [--device-report] [--device-dynamics] [--device-clearance]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
        [--batch-size 4] [--iteration 1] [--joint] [--csv DIR]
 """
 import argparse
@@ -38,6 +41,8 @@ def main(argv=None):
                     "report call on the device (planner.Session.report); without --csv the coefficients are not downloaded")
     ap.add_argument("--device-dynamics", action="store_true", help="with --device-worlds --mode batched: one more line per map with both limit peak ratios and "
                     "where they lie, from one dynamics call on the device (planner.Session.dynamics)")
+    ap.add_argument("--device-clearance", action="store_true", help="with --device-worlds --mode batched: one more line per map with the smallest clearance "
+                    "to the obstacles, where it lies, hits and outsides, from one clearance call on the device (planner.Session.clearance)")
     ap.add_argument("--mission", default="mission_64agents_15.json")
     ap.add_argument("--maps", default="1-50")
     ap.add_argument("--mode", choices=["serial", "batched"], default="serial")
@@ -50,6 +55,8 @@ def main(argv=None):
         ap.error("--device-report needs --device-worlds --mode batched")
     if args.device_dynamics and not (args.device_worlds and args.mode == "batched"):
         ap.error("--device-dynamics needs --device-worlds --mode batched")
+    if args.device_clearance and not (args.device_worlds and args.mode == "batched"):
+        ap.error("--device-clearance needs --device-worlds --mode batched")
     if args.device_ecbs and not args.device_worlds:
         ap.error("--device-ecbs needs --device-worlds")
     if args.device_handoff and not (args.device_ecbs and args.mode == "batched"):
@@ -140,6 +147,7 @@ def run_and_report(args, sess, maps, plans, mission, param):
     status = sess.download() if download else None
     records = sess.report() if args.device_report else [None] * sess.K
     peaks = sess.dynamics()[0] if args.device_dynamics else [None] * sess.K
+    clear = sess.clearance()[0] if args.device_clearance else [None] * sess.K
     dt = time.perf_counter() - t0
     print(f"BoxGenerator + SwarmPlanner runtime, {sess.K} maps in one session: {dt:.6f} "
           f"({sess.K * mission.qn / dt:.1f} agent-trajectories/s incl. {'download' if download else 'report'})")
@@ -148,7 +156,7 @@ def run_and_report(args, sess, maps, plans, mission, param):
         status = [r.status for r in records]
         plans = [SimpleNamespace(total_cost=float(c), time_scale=float(ts) if ts > 0 else 1.0, T=[r.end_time]) for (ts, c), r in zip(sc, records)]
     sess.close()
-    for i, p, st, rec, pk in zip(maps, plans, status, records, peaks):
+    for i, p, st, rec, pk, cl in zip(maps, plans, status, records, peaks, clear):
         if st:
             print(f"[ERROR] map{i}: status {st}")
             return -1
@@ -158,7 +166,15 @@ def run_and_report(args, sess, maps, plans, mission, param):
             report_line(i, p, rec, args.csv)
         if pk is not None:
             dynamics_line(i, pk)
+        if cl is not None:
+            clearance_line(i, cl)
     return 0
+
+
+def clearance_line(i, c):
+    """--device-clearance: the smallest clearance of a types.Clearance and where it lies (agent, sample), hits and outsides; `none` for a plan without a sample"""
+    where = f"{c.min_clearance:.4f} (agent {c.min_agent} sample {c.min_sample})" if c.min_sample >= 0 else "none"
+    print(f"map{i}: minimum clearance {where}  hits {c.hits}  outside {c.outside}  samples {c.samples}")
 
 
 def dynamics_line(i, d):

@@ -232,6 +232,34 @@ class Dynamics:
         return tuple(int(x) for x in f) + tuple(getattr(self, n) for n in self.FIELDS[7:])
 
 
+@dataclass
+class Clearance:
+    """rbp_clearance (include/rbp.h): a mission's smallest clearance to the obstacles -- the distance grid's value under an agent at a
+    sample less the agent's radius -- with the grid's value there (-1: outside the grid) and where it lies (-1: none, clearance 1e9), how
+    many (sample, agent) items hit an obstacle by the reference's test and how many fell outside the grid, the end time and the samples.
+    status != 0: nothing computed."""
+    min_clearance: float
+    min_dist: float
+    end_time: float
+    hits: int
+    outside: int
+    samples: int
+    min_sample: int
+    min_agent: int
+    status: int = 0
+
+    FIELDS = ("min_clearance", "min_dist", "end_time", "hits", "outside", "samples", "min_sample", "min_agent", "status")
+
+    @classmethod
+    def from_c(cls, r):
+        return cls(*[getattr(r, n) for n in cls.FIELDS])
+
+    def bits(self):
+        """the record with its doubles as bit patterns: what two evaluations of the one rule must agree on"""
+        f = np.array([getattr(self, n) for n in self.FIELDS[:3]], np.float64).view(np.uint64)
+        return tuple(int(x) for x in f) + tuple(getattr(self, n) for n in self.FIELDS[3:])
+
+
 class PlanResult:
     """sp_const.hpp:21-28 as flat arrays (include/rbp.h rbp_plan)."""
 
