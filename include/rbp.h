@@ -346,7 +346,7 @@ void rbp_release_thread_context(void);
                               4: rbp_solver_opts (the library no longer reads environment variables); 5: rbp_session_shard_joint, RBP_ERR_EXCHANGE;
                               6: rbp_param.timescale_rule, rbp_plan.time_scale_alt */
 enum { RBP_SIZEOF_WORLD = 0, RBP_SIZEOF_MISSION = 1, RBP_SIZEOF_PARAM = 2, RBP_SIZEOF_PLAN = 3, RBP_SIZEOF_COUNTERS = 4, RBP_SIZEOF_DEVICE_ARRAYS = 5,
-       RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7, RBP_SIZEOF_REPORT = 8, RBP_SIZEOF_DYNAMICS = 9, RBP_SIZEOF_CLEARANCE = 10 };
+       RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7, RBP_SIZEOF_REPORT = 8, RBP_SIZEOF_DYNAMICS = 9, RBP_SIZEOF_CLEARANCE = 10, RBP_SIZEOF_SEPARATION = 11 };
 int rbp_abi_version(void);
 size_t rbp_sizeof(int which);
 const char* rbp_version(void);
@@ -562,6 +562,51 @@ int rbp_dev_clearance(int device, int32_t K, int32_t N, const int32_t* M, int32_
                       const double* time_scale, const double* coef, const double* radius,
                       const rbp_world* worlds /* [K]; dist host or device */, double dt,
                       rbp_clearance* out, double* agent_clearance);
+
+/* ---- a certified interval for the smallest safety ratio of resident plans in CONTINUOUS time ----
+ * rbp_report, rbp_dynamics and rbp_clearance look at the samples t = j * dt; the relative Bernstein polynomial promises separation at
+ * every instant.  For a pair qi < qj and a segment m (an ITEM) the squared downwash-scaled relative distance is a polynomial of degree
+ * 10; on a PIECE of the segment its smallest Bernstein coefficient less an error term is a lower bound of it and its first and last
+ * coefficient plus that term are upper bounds of its minimum.  Piece p of depth D covers [p / 2^D, (p+1) / 2^D] of the segment.  All
+ * of it -- the Bernstein form, the halving, the squared norm, the error term c u S with its derivation, the 3 doubles every ratio is
+ * moved outwards for its square root and division, the order of the minima -- is the rule of csrc/common/separation_rules.h, which the
+ * kernels (kernels/separation.hip) and rbp_separation_host of rbp_host.h share: both return the same bits.  The promise:
+ *     lower_ratio <= the smallest safety ratio of the mission over all pairs at every instant of [0, Ts[M]] <= upper_ratio,
+ * for the polynomials the double coefficients define.  lower_ratio >= 1 certifies the plan; upper_ratio < 1 proves a collision.
+ * Refinement is fixed: every item is evaluated at depth 0; an item whose lower ratio there is below refine_below is evaluated again on
+ * all 2^depth pieces of depth `depth`, which replace its depth-0 bounds.  depth in 0 .. RBP_SEPARATION_MAX_DEPTH; refine_below > 0
+ * (1e9, the ratio of no pair, refines everything).  The minima name the lexicographically first (segment, piece, qi, qj) among equal
+ * ratios; a NaN is never a minimum.
+ * pair_lower [K][N (N-1) / 2] (NULL: not wanted), in the pair order of rbp_plan: a pair's smallest lower ratio over its segments, 1e9
+ * where none is a number; the row of a mission with a status is left untouched.  It may be a host pointer or a device pointer on the
+ * plans' device (classified with hipPointerGetAttributes as rbp_world.dist is; another device: RBP_ERR_BAD_ARGUMENT): a device
+ * destination is written in place by the kernels, a host destination goes through one staging buffer and one copy.
+ * Memory: items that are refined go through a work list of one uint32 per item, sized for the worst case (every item), of at most
+ * RBP_SEPARATION_LIST_BYTES; missions are processed in chunks where all of them would need more (a single mission always is one chunk,
+ * and one of more than 2^32 - 64 items is refused).  No allocation depends on the data.
+ * rbp_session_separation: of a session's K missions, from its own coef, T, time scale, radius and status, all of which stay in HBM;
+ *   waits for an asynchronous solve like every call, enqueues its kernels on `stream`, copies K structs back in one copy and returns
+ *   when they have arrived.  Nothing of the session changes.  A mission whose status is not 0 gets that status and nothing computed.
+ *   RBP_ERR_BAD_ARGUMENT: a session whose last run did not include the PLANNER stage; and, before a device is looked for, a null
+ *   pointer, a depth outside 0 .. RBP_SEPARATION_MAX_DEPTH, a refine_below that is not a number above 0.
+ * rbp_dev_separation: the same kernels on a caller's host arrays in rbp_dev_report's layout, uploaded once.  Argument errors (those
+ *   above, K, N <= 0, an M[k] outside 1..M_stride, a time scale or a downwash <= 0) are RBP_ERR_BAD_ARGUMENT before a device is looked for. */
+#define RBP_SEPARATION_MAX_DEPTH 8
+#define RBP_SEPARATION_LIST_BYTES (64u << 20) /* the work list's budget: 16 Mi items of a chunk of missions */
+typedef struct rbp_separation {
+    double  lower_ratio, upper_ratio;   /* 1e9: no pair */
+    double  end_time;                   /* Ts[M]: the mission's last segment time, scaled */
+    int64_t uncertified, colliding, refined;   /* items whose lower ratio is < 1, whose upper ratio is < 1, that went to `depth` */
+    int32_t lower_segment, lower_piece, lower_qi, lower_qj;   /* -1: none */
+    int32_t upper_segment, upper_piece, upper_qi, upper_qj;
+    int32_t lower_depth, upper_depth;   /* depth of the piece the bound came from (0 or `depth`; -1: none) */
+    int32_t status, reserved;           /* the mission's status; != 0: nothing computed, zeros, indices -1 */
+} rbp_separation;
+int rbp_session_separation(rbp_session* s, int32_t depth, double refine_below, rbp_separation* out /* [K] */,
+                           double* pair_lower /* [K][N(N-1)/2] or NULL; host or device pointer */, void* stream);
+int rbp_dev_separation(int device, int32_t K, int32_t N, const int32_t* M, int32_t M_stride, const double* T,
+                       const double* time_scale, const double* coef, const double* radius, double downwash,
+                       int32_t depth, double refine_below, rbp_separation* out, double* pair_lower);
 
 const char* rbp_last_error(void);
 int rbp_device_count(void);

@@ -103,6 +103,14 @@ int rbp_dynamics_host(const rbp_mission* mission, const rbp_param* param, int32_
 int rbp_clearance_host(const rbp_world* world, const rbp_mission* mission, int32_t M, const double* T,
                        const double* coef, double dt, rbp_clearance* out, double* agent_clearance /* [N] or NULL */);
 
+/* The certified interval of one plan's smallest safety ratio in continuous time as an rbp_separation (rbp.h), by the sequential loop of
+ * csrc/common/separation_rules.h that the device shares: what rbp_session_separation / rbp_dev_separation return for the same plan, bit
+ * for bit, and their reference.  T as downloaded (scaled); radius is the mission's, the downwash param's.  depth in
+ * 0 .. RBP_SEPARATION_MAX_DEPTH and refine_below > 0, otherwise RBP_ERR_BAD_ARGUMENT.  pair_lower [N (N-1) / 2] may be NULL.
+ * out->status is 0. */
+int rbp_separation_host(const rbp_mission* mission, const rbp_param* param, int32_t M, const double* T, const double* coef,
+                        int32_t depth, double refine_below, rbp_separation* out, double* pair_lower /* [N (N-1) / 2] or NULL */);
+
 /* crazyswarm CSV of rbp_planner.hpp:295-324 (one file per agent: <dir>/coef<qi+1>.csv) */
 int rbp_write_coef_csv(const char* dir, int32_t N, int32_t M, const double* T, const double* coef);
 

@@ -125,6 +125,18 @@ class rbp_clearance(C.Structure):
                 ("samples", C.c_int32), ("min_sample", C.c_int32), ("min_agent", C.c_int32), ("status", C.c_int32)]
 
 
+RBP_SIZEOF_SEPARATION = 11
+RBP_SEPARATION_MAX_DEPTH = 8
+
+
+class rbp_separation(C.Structure):
+    _fields_ = [("lower_ratio", C.c_double), ("upper_ratio", C.c_double), ("end_time", C.c_double),
+                ("uncertified", C.c_int64), ("colliding", C.c_int64), ("refined", C.c_int64),
+                ("lower_segment", C.c_int32), ("lower_piece", C.c_int32), ("lower_qi", C.c_int32), ("lower_qj", C.c_int32),
+                ("upper_segment", C.c_int32), ("upper_piece", C.c_int32), ("upper_qi", C.c_int32), ("upper_qj", C.c_int32),
+                ("lower_depth", C.c_int32), ("upper_depth", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class rbp_mission_buf(C.Structure):
     _fields_ = [("N", C.c_int32), ("start", c_double_p), ("goal", c_double_p), ("radius", c_double_p),
                 ("speed", c_double_p), ("max_vel", c_double_p), ("max_acc", c_double_p)]

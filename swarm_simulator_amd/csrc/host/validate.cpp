@@ -7,6 +7,7 @@
 
 #include "common/clearance_rules.h"
 #include "common/report_rules.h"
+#include "common/separation_rules.h"
 #include "common/state_rules.h"
 
 #include <cmath>
@@ -109,6 +110,24 @@ extern "C" int rbp_clearance_host(const rbp_world* world, const rbp_mission* mis
     out->min_clearance = r.min.clearance, out->min_dist = r.min.dist, out->end_time = r.end_time;
     out->hits = r.hits, out->outside = r.outside;
     out->samples = r.samples, out->min_sample = r.min.sample, out->min_agent = r.min.agent, out->status = 0;
+    return RBP_OK;
+}
+
+// The certified interval of the plan's smallest safety ratio in continuous time by the rule of common/separation_rules.h, which the
+// device's separation kernels (kernels/separation.hip) share.  T arrives scaled, so the scale is 1.
+extern "C" int rbp_separation_host(const rbp_mission* mission, const rbp_param* param, int32_t M, const double* T, const double* coef,
+                                   int32_t depth, double refine_below, rbp_separation* out, double* pair_lower) {
+    if (!mission || !param || !T || !coef || !out || !mission->radius || mission->N <= 0 || M <= 0 || depth < 0 ||
+        depth > RBP_SEPARATION_MAX_DEPTH || !(refine_below > 0))
+        return RBP_ERR_BAD_ARGUMENT;
+    const separation_rules::Tally t = separation_rules::separation_sequential(mission->N, M, T, 1.0, coef, mission->radius, param->downwash,
+                                                                              depth, refine_below, pair_lower);
+    out->lower_ratio = t.lower.ratio, out->upper_ratio = t.upper.ratio, out->end_time = T[M];
+    out->uncertified = t.uncertified, out->colliding = t.colliding, out->refined = t.refined;
+    out->lower_segment = t.lower.segment, out->lower_piece = t.lower.piece, out->lower_qi = t.lower.qi, out->lower_qj = t.lower.qj;
+    out->upper_segment = t.upper.segment, out->upper_piece = t.upper.piece, out->upper_qi = t.upper.qi, out->upper_qj = t.upper.qj;
+    out->lower_depth = t.lower.depth, out->upper_depth = t.upper.depth;
+    out->status = 0, out->reserved = 0;
     return RBP_OK;
 }
 

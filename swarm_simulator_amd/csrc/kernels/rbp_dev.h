@@ -251,6 +251,23 @@ size_t clearance_workspace_bytes(int K, int N);
 int launch_clearance(const ClearanceInputs& in, double* agent_clearance, void* workspace, hipStream_t st);
 int clearance_run(const char* who, int device, const ClearanceInputs& in, rbp_clearance* out, double* agent_clearance, void* workspace, hipStream_t st);
 
+// kernels/separation.hip: a certified interval for the smallest safety ratio of K missions in continuous time (rbp_separation of
+// include/rbp.h) from device arrays in a session's layout.  launch_separation enqueues its kernels on `st` and allocates nothing;
+// pair_lower [K][N (N-1) / 2] is a device pointer or null; the K structs are then at the front of `workspace`
+// (separation_workspace_bytes(K, N, M_stride) bytes of device memory, nothing to initialise: the structs, and one chunk's work-list counters,
+// work list and partial tallies, sized by the shapes alone).  separation_run: the same with `pair_lower` wherever the caller has it -- on
+// `device` (the current one), written in place, or on the host, through one staging buffer -- and the structs copied to `out` on the host;
+// it returns when all has arrived.  separation_check_arguments: depth and refine_below, no device work.  (r.dt is not read.)
+struct SeparationInputs {
+    ReportInputs r;
+    int depth;
+    double refine_below;
+};
+int separation_check_arguments(const char* who, int32_t depth, double refine_below);
+size_t separation_workspace_bytes(int K, int N, int M_stride);
+int launch_separation(const SeparationInputs& in, double* pair_lower, void* workspace, hipStream_t st);
+int separation_run(const char* who, int device, const SeparationInputs& in, rbp_separation* out, double* pair_lower, void* workspace, hipStream_t st);
+
 // launchers (defined in the .hip files)
 int launch_corridor(const DevSession& s, hipStream_t st);
 size_t corridor_lds_bytes(const DevSession& s);  // dynamic LDS of sfc_kernel for this session's shapes

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _abi as A
-from .types import Clearance, Dynamics, Mission, Param, PlanResult, Report, World
+from .types import Clearance, Dynamics, Mission, Param, PlanResult, Report, Separation, World
 
 _lib = None
 
@@ -49,6 +49,8 @@ def lib():
                                         C.POINTER(A.rbp_dynamics), C.c_void_p, C.c_void_p, C.c_int32]
         L.rbp_clearance_host.argtypes = [C.POINTER(A.rbp_world), C.POINTER(A.rbp_mission), C.c_int32, A.c_double_p, A.c_double_p, C.c_double,
                                          C.POINTER(A.rbp_clearance), A.c_double_p]
+        L.rbp_separation_host.argtypes = [C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.c_int32, A.c_double_p, A.c_double_p, C.c_int32,
+                                          C.c_double, C.POINTER(A.rbp_separation), A.c_double_p]
         L.rbp_write_coef_csv.argtypes =[C.c_char_p, C.c_int32, C.c_int32, A.c_double_p, A.c_double_p]
         L.rbp_write_qp_lp.argtypes = [C.c_char_p, C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.POINTER(A.rbp_plan), C.c_int32,
                                       A.c_double_p]
@@ -232,6 +234,20 @@ def clearance(world: World, mission: Mission, plan: PlanResult, dt=0.1, per_agen
     if rc:
         raise ValueError(f"rbp_clearance_host rc={rc}")
     return (Clearance.from_c(out), agents) if per_agent else Clearance.from_c(out)
+
+
+def separation(mission: Mission, param: Param, plan: PlanResult, depth=4, refine_below=2.0, per_pair=False):
+    """a certified interval for the plan's smallest safety ratio in continuous time as a Separation, by the sequential loop the device
+    shares (csrc/common/separation_rules.h): what planner.Session.separation / planner.separation_coefs return for this plan, bit for bit.
+    per_pair: returns (Separation, [N (N-1) / 2] array of every pair's smallest lower ratio, 1e9 where there is none)."""
+    ms, ps = mission.c_struct(), param.c_struct()
+    out = A.rbp_separation()
+    pairs = np.full(plan.N * (plan.N - 1) // 2, 1e9) if per_pair else None
+    rc = lib().rbp_separation_host(C.byref(ms), C.byref(ps), plan.M, A.ptr(plan.T, A.c_double_p), A.ptr(plan.coef, A.c_double_p), depth,
+                                   refine_below, C.byref(out), A.ptr(pairs, A.c_double_p))
+    if rc:
+        raise ValueError(f"rbp_separation_host rc={rc}")
+    return (Separation.from_c(out), pairs) if per_pair else Separation.from_c(out)
 
 
 def write_coef_csv(directory, plan: PlanResult):

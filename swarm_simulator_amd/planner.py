@@ -11,7 +11,7 @@ import ctypes as C
 import os
 
 from . import _abi as A
-from .types import Clearance, DeviceWorld, Dynamics, Mission, Param, PlanResult, Report, World
+from .types import Clearance, DeviceWorld, Dynamics, Mission, Param, PlanResult, Report, Separation, World
 
 _lib = None
 
@@ -144,6 +144,11 @@ def lib():
                                             P(A.rbp_world), C.c_double, P(A.rbp_clearance), C.c_void_p]
             if L.rbp_sizeof(A.RBP_SIZEOF_CLEARANCE) != C.sizeof(A.rbp_clearance):
                 raise RbpLibraryMissing(f"{path}: sizeof(rbp_clearance) is {L.rbp_sizeof(A.RBP_SIZEOF_CLEARANCE)} in the library, {C.sizeof(A.rbp_clearance)} in this binding")
+            L.rbp_session_separation.argtypes = [C.c_void_p, C.c_int32, C.c_double, P(A.rbp_separation), C.c_void_p, C.c_void_p]
+            L.rbp_dev_separation.argtypes = [C.c_int, C.c_int32, C.c_int32, A.c_int32_p, C.c_int32, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p,
+                                             C.c_double, C.c_int32, C.c_double, P(A.rbp_separation), C.c_void_p]
+            if L.rbp_sizeof(A.RBP_SIZEOF_SEPARATION) != C.sizeof(A.rbp_separation):
+                raise RbpLibraryMissing(f"{path}: sizeof(rbp_separation) is {L.rbp_sizeof(A.RBP_SIZEOF_SEPARATION)} in the library, {C.sizeof(A.rbp_separation)} in this binding")
         except AttributeError:
             if not os.environ.get("RBP_HIP_LIB"):
                 raise
@@ -183,6 +188,7 @@ EXPORTED_SYMBOLS = [
     "rbp_session_report", "rbp_dev_report",
     "rbp_session_dynamics", "rbp_dev_dynamics",
     "rbp_session_clearance", "rbp_dev_clearance",
+    "rbp_session_separation", "rbp_dev_separation",
 ]
 
 
@@ -510,6 +516,35 @@ class Session:
             raise RuntimeError(f"rbp_session_clearance rc={rc}: {last_error()}")
         return [Clearance.from_c(r) for r in out], ag
 
+    def separation(self, depth=4, refine_below=2.0, per_pair=False, device_out=False, stream=None):
+        """a certified interval for the missions' smallest safety ratio in continuous time, computed where the plans lie
+        (rbp_session_separation): (records, pairs) -- K Separation records, the bits host.separation gives for the downloaded plans;
+        pairs [K][N (N-1) / 2], every pair's smallest lower ratio in the pair order of a plan (1e9 where there is none), or None unless
+        per_pair.  depth: the pieces of a refined item are 2^depth; refine_below: items whose depth-0 lower ratio is below it are
+        refined.  device_out: the array is a torch tensor on the session's device, written in place by the kernels; otherwise a numpy
+        array.  The row of a mission that is not computed keeps its 1e9.  Nothing of the session changes; a mission whose status is not 0
+        comes back with that status and nothing computed."""
+        import numpy as np
+        N = self.plans[0].N
+        npair = N * (N - 1) // 2
+        out = (A.rbp_separation * self.K)()
+        pl, pp = None, None
+        if per_pair and device_out:
+            import torch
+            dev = torch.device("cuda", self.device)
+            pl = torch.full((self.K, npair), 1e9, dtype=torch.float64, device=dev)
+            torch.cuda.synchronize(dev)   # (the fill is written on torch's stream, the kernels run on `stream`)
+            pp = pl.data_ptr()
+        elif per_pair:
+            pl = np.full((self.K, npair), 1e9)
+            pp = pl.ctypes.data
+        rc = lib().rbp_session_separation(self._h, depth, refine_below, out, C.c_void_p(pp), C.c_void_p(stream or 0))
+        if rc == A.RBP_ERR_BAD_ARGUMENT:
+            raise ValueError(f"rbp_session_separation rc={rc}: {last_error()}")
+        if rc:
+            raise RuntimeError(f"rbp_session_separation rc={rc}: {last_error()}")
+        return [Separation.from_c(r) for r in out], pl
+
     def reserve_workspace(self, stream=None):
         """reserve the QP workspace now (otherwise the first PLANNER run does)"""
         rc = lib().rbp_session_reserve_workspace(self._h, C.c_void_p(stream or 0))
@@ -661,6 +696,38 @@ def clearance_coefs(M, T, coef, radius, worlds, dt=0.1, time_scale=None, agent_c
     if rc:
         raise RuntimeError(f"rbp_dev_clearance rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
     return [Clearance.from_c(r) for r in out]
+
+
+def separation_coefs(M, T, coef, radius, downwash, depth=4, refine_below=2.0, time_scale=None, pair_lower=None, device=0):
+    """rbp_dev_separation: the separation kernels on the caller's arrays, uploaded once, in report_coefs' layout.  pair_lower: None, a
+    C-contiguous float64 numpy array [K][N (N-1) / 2] or a torch tensor of that shape on `device`, written in place.  Returns K Separation
+    records, the bits host.separation gives for the scaled times."""
+    import numpy as np
+    M = np.ascontiguousarray(M, np.int32).reshape(-1)
+    K = len(M)
+    T, coef, radius = A.as_f64(T).reshape(K, -1), A.as_f64(coef), A.as_f64(radius).reshape(K, -1)
+    S, N = T.shape[1] - 1, radius.shape[1]
+    npair = N * (N - 1) // 2
+    if coef.size != K * N * 3 * 6 * S:
+        raise ValueError(f"coef holds {coef.size} doubles, K * N * 3 * 6 * M_stride = {K * N * 3 * 6 * S}")
+    ts = None if time_scale is None else A.as_f64(time_scale).reshape(K)
+    pp = None
+    if isinstance(pair_lower, np.ndarray):
+        if pair_lower.dtype != np.float64 or not pair_lower.flags["C_CONTIGUOUS"] or pair_lower.size != K * npair:
+            raise ValueError(f"pair_lower must be a C-contiguous float64 array of {K * npair} elements")
+        pp = pair_lower.ctypes.data
+    elif pair_lower is not None:
+        if str(pair_lower.dtype) != "torch.float64" or not pair_lower.is_contiguous() or pair_lower.numel() != K * npair:
+            raise ValueError(f"pair_lower must be a contiguous float64 tensor of {K * npair} elements")
+        pp = pair_lower.data_ptr()
+    out = (A.rbp_separation * K)()
+    rc = lib().rbp_dev_separation(device, K, N, A.ptr(M, A.c_int32_p), S, A.ptr(T, A.c_double_p), A.ptr(ts, A.c_double_p), A.ptr(coef, A.c_double_p),
+                                  A.ptr(radius, A.c_double_p), downwash, depth, refine_below, out, C.c_void_p(pp))
+    if rc == A.RBP_ERR_BAD_ARGUMENT:
+        raise ValueError(f"rbp_dev_separation rc={rc}: {last_error()}")
+    if rc:
+        raise RuntimeError(f"rbp_dev_separation rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+    return [Separation.from_c(r) for r in out]
 
 
 def build_world(keys, res, param: Param, max_dist=1.0):

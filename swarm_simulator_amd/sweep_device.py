@@ -17,8 +17,11 @@ line per map with the largest |velocity| / max_vel and |acceleration| / max_acc 
 With --device-clearance (only with --device-worlds --mode batched; off by default) ONE planner.Session.clearance() on the resident plans and
 grids adds a line per map with the smallest clearance to the obstacles, where it lies, and how many (sample, agent) items hit an obstacle
 or left the grid (csrc/common/clearance_rules.h): whether the plan hits anything.
+With --device-separation (only with --device-worlds --mode batched; off by default) ONE planner.Session.separation() on the resident plans
+adds a line per map with a certified interval for the smallest safety ratio in CONTINUOUS time, where both ends lie, and how many (pair,
+segment) items are uncertified, colliding and refined (csrc/common/separation_rules.h): whether the plan is separated between the samples.
 
-usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]] [--device-report] [--device-dynamics] [--device-clearance]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
+usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]] [--device-report] [--device-dynamics] [--device-clearance] [--device-separation]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
        [--batch-size 4] [--iteration 1] [--joint] [--csv DIR]
 """
 import argparse
@@ -43,6 +46,9 @@ def main(argv=None):
                     "where they lie, from one dynamics call on the device (planner.Session.dynamics)")
     ap.add_argument("--device-clearance", action="store_true", help="with --device-worlds --mode batched: one more line per map with the smallest clearance "
                     "to the obstacles, where it lies, hits and outsides, from one clearance call on the device (planner.Session.clearance)")
+    ap.add_argument("--device-separation", action="store_true", help="with --device-worlds --mode batched: one more line per map with a certified interval "
+                    "for the smallest safety ratio in continuous time, where it lies, uncertified / colliding / refined items, from one separation "
+                    "call on the device (planner.Session.separation)")
     ap.add_argument("--mission", default="mission_64agents_15.json")
     ap.add_argument("--maps", default="1-50")
     ap.add_argument("--mode", choices=["serial", "batched"], default="serial")
@@ -57,6 +63,8 @@ def main(argv=None):
         ap.error("--device-dynamics needs --device-worlds --mode batched")
     if args.device_clearance and not (args.device_worlds and args.mode == "batched"):
         ap.error("--device-clearance needs --device-worlds --mode batched")
+    if args.device_separation and not (args.device_worlds and args.mode == "batched"):
+        ap.error("--device-separation needs --device-worlds --mode batched")
     if args.device_ecbs and not args.device_worlds:
         ap.error("--device-ecbs needs --device-worlds")
     if args.device_handoff and not (args.device_ecbs and args.mode == "batched"):
@@ -148,6 +156,7 @@ def run_and_report(args, sess, maps, plans, mission, param):
     records = sess.report() if args.device_report else [None] * sess.K
     peaks = sess.dynamics()[0] if args.device_dynamics else [None] * sess.K
     clear = sess.clearance()[0] if args.device_clearance else [None] * sess.K
+    separ = sess.separation()[0] if args.device_separation else [None] * sess.K
     dt = time.perf_counter() - t0
     print(f"BoxGenerator + SwarmPlanner runtime, {sess.K} maps in one session: {dt:.6f} "
           f"({sess.K * mission.qn / dt:.1f} agent-trajectories/s incl. {'download' if download else 'report'})")
@@ -156,7 +165,7 @@ def run_and_report(args, sess, maps, plans, mission, param):
         status = [r.status for r in records]
         plans = [SimpleNamespace(total_cost=float(c), time_scale=float(ts) if ts > 0 else 1.0, T=[r.end_time]) for (ts, c), r in zip(sc, records)]
     sess.close()
-    for i, p, st, rec, pk, cl in zip(maps, plans, status, records, peaks, clear):
+    for i, p, st, rec, pk, cl, sp in zip(maps, plans, status, records, peaks, clear, separ):
         if st:
             print(f"[ERROR] map{i}: status {st}")
             return -1
@@ -168,7 +177,19 @@ def run_and_report(args, sess, maps, plans, mission, param):
             dynamics_line(i, pk)
         if cl is not None:
             clearance_line(i, cl)
+        if sp is not None:
+            separation_line(i, sp)
     return 0
+
+
+def separation_line(i, s):
+    """--device-separation: both ends of a types.Separation's interval and where they lie (pair, segment, piece of depth), and the item
+    counts; `none` for a plan without a pair"""
+    def where(ratio, qi, qj, segment, piece, depth):
+        return f"{ratio:.5f} (agents {qi} {qj} segment {segment} piece {piece}/{1 << depth})" if segment >= 0 else "none"
+    print(f"map{i}: continuous safety ratio in [{where(s.lower_ratio, s.lower_qi, s.lower_qj, s.lower_segment, s.lower_piece, s.lower_depth)}, "
+          f"{where(s.upper_ratio, s.upper_qi, s.upper_qj, s.upper_segment, s.upper_piece, s.upper_depth)}]  "
+          f"uncertified {s.uncertified}  colliding {s.colliding}  refined {s.refined}")
 
 
 def clearance_line(i, c):

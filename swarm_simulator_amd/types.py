@@ -260,6 +260,43 @@ class Clearance:
         return tuple(int(x) for x in f) + tuple(getattr(self, n) for n in self.FIELDS[3:])
 
 
+@dataclass
+class Separation:
+    """rbp_separation (include/rbp.h): a certified interval for a mission's smallest safety ratio in continuous time --
+    lower_ratio <= the smallest ratio over all pairs at every instant <= upper_ratio -- with the (segment, piece, qi, qj) and the depth
+    of the piece each bound came from (-1: none, ratio 1e9), the items (pair, segment) whose lower ratio is below 1 (uncertified), whose
+    upper ratio is below 1 (colliding: a proven collision) and that were refined, and the end time.  status != 0: nothing computed."""
+    lower_ratio: float
+    upper_ratio: float
+    end_time: float
+    uncertified: int
+    colliding: int
+    refined: int
+    lower_segment: int
+    lower_piece: int
+    lower_qi: int
+    lower_qj: int
+    upper_segment: int
+    upper_piece: int
+    upper_qi: int
+    upper_qj: int
+    lower_depth: int
+    upper_depth: int
+    status: int = 0
+
+    FIELDS = ("lower_ratio", "upper_ratio", "end_time", "uncertified", "colliding", "refined", "lower_segment", "lower_piece", "lower_qi",
+              "lower_qj", "upper_segment", "upper_piece", "upper_qi", "upper_qj", "lower_depth", "upper_depth", "status")
+
+    @classmethod
+    def from_c(cls, r):
+        return cls(*[getattr(r, n) for n in cls.FIELDS])
+
+    def bits(self):
+        """the record with its doubles as bit patterns: what two evaluations of the one rule must agree on"""
+        f = np.array([getattr(self, n) for n in self.FIELDS[:3]], np.float64).view(np.uint64)
+        return tuple(int(x) for x in f) + tuple(getattr(self, n) for n in self.FIELDS[3:])
+
+
 class PlanResult:
     """sp_const.hpp:21-28 as flat arrays (include/rbp.h rbp_plan)."""
 
