@@ -598,7 +598,11 @@ static int ensure_planner_workspace(rbp_session* s, hipStream_t st) {
                                                   " agents (joint QP of a large mission) is not supported by the one-workgroup QP kernel "
                                                   "(rbp_solver_opts.joint_wide_min_agents selects the grid-wide solver)");
     }
-    const size_t per = joint_wide ? joint_workspace_bytes(N, M) : std::max(planner_workspace_bytes_w2(N, M, s->bs), planner_workspace_bytes_w4(N, M, s->bs));
+    // Every mission's workspace of the batch QP kernels starts on a 128-byte line: the knots' factors (QpWs::Lf, kernels/knot_factor_layout.h) are
+    // carved in whole lines from there.  planner_workspace_bytes_* round to 256 bytes already; the stride is rounded here all the same, and the
+    // base below, inside the 256 spare bytes of the allocation.
+    const size_t per = joint_wide ? joint_workspace_bytes(N, M)
+                                  : (std::max(planner_workspace_bytes_w2(N, M, s->bs), planner_workspace_bytes_w4(N, M, s->bs)) + 127) & ~size_t(127);
     s->joint_wide = joint_wide;
     if (s->qp_ws && s->ws_joint == joint_wide && s->qp_ws_per_mission == per) return RBP_OK;
     const size_t total = per * (size_t)K + 256;
@@ -631,7 +635,7 @@ static int ensure_planner_workspace(rbp_session* s, hipStream_t st) {
         base = s->ws_own;
     }
     HIP_TRY(hipMemsetAsync(base, 0, total, st));
-    s->qp_ws = base, s->qp_ws_per_mission = per, s->ws_joint = joint_wide;
+    s->qp_ws = base + (128 - (size_t)base % 128) % 128, s->qp_ws_per_mission = per, s->ws_joint = joint_wide;  // (hipMalloc returns 256-byte multiples: + 0)
     return RBP_OK;
 }
 

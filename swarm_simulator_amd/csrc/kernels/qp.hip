@@ -107,6 +107,19 @@
 #ifndef QP_MID_FOLLOW
 #define QP_MID_FOLLOW (QP_THREADS >= 512)  // see wave_factor_mid
 #endif
+// The knots' inverse factors M_j in global memory as contiguous triangles (knot_factor_layout.h), fetched by the staging threads of the
+// substitutions as runs of 16-byte pairs; 0 = the square image [NK][NK] fetched 8 bytes at a time, the parent of the A/B in
+// profiles/packed_m_ab.txt (one tree builds both sides).
+// The 256-thread build, whose missions share the memory system with 511 others: planner stage at 2000 missions 607.9 -> 585.3 ms in every one
+// of three passes, 200 GB fewer bytes fetched per launch.  One mission alone on the 512-thread build has no such pressure and measured 0.6 ms
+// (0.8 %) SLOWER with the packed layout in every pass: that build keeps the square.  (A factor is written and read inside one launch of one
+// build, so the two need not agree.)
+#ifndef QP_LF_PACKED
+#define QP_LF_PACKED (QP_THREADS >= 512 ? 0 : 1)
+#endif
+// (A second lever, QP_STAGE_EARLY -- the loads of a substitution's first stage(s) issued at the entry of solve_staged, ahead of the
+// right-hand side's, instead of behind the zero-fill barrier -- was built and measured with this one: no gain alone, 1.1 .. 1.7 ms slower on
+// top of the packed layout in every one of three passes (profiles/packed_m_ab.txt).  Its code is not kept.)
 // The predictor's forward substitution carried along the factorisation (blocks on the fused path, i.e. of order 36): a chain wave takes the
 // forward step of the block it has just factorised out of its own LDS area -- M_jp in MX, 1 / d_jp in I -- between the update of the next
 // block and the wait for that block's image, the middle block's step follows its factorisation, and the predictor's solve_staged runs the
@@ -136,7 +149,8 @@
 #endif
 // LDS doubles used by polish_qp: 2 blocks + packed factor + vectors + int arrays (see qp_polish.inc)
 #include "lh_layout.h"
-#define PL_NC 256    // polish: candidate rows
+#include "knot_factor_layout.h"  // QpWs::Lf: a knot's M_j and 1 / d_j as one contiguous run
+#define PL_NC 256   // polish: candidate rows
 #define PL_PMAX 160  // polish: rows simultaneously active in the dual solve (wide batches; 112 on the wave path, whose
                      // workgroups are meant to share a CU's LDS in pairs)
 #define PL_PBIG 192  // second attempt of a polish whose dual solve ran out of capacity: factor in global memory (rare: ~1 batch QP in 800)

@@ -71,7 +71,8 @@ struct QpWs {
     double *dx, *dxa, *cvec;        // [nb*3*oq]
     double *rbase, *rhs;            // [(M-1)*nk]
     double *Td, *To;                // [(M-1)][nk*nk], [(M-2)][nk*nk]
-    double *Lf;                     // [(M-1)][2][nk*nk]: L_jj and L_{j+1,j}, both stored [k][r] (element (r,k) at k*nk + r)
+    double *Lf;                     // wave path: [(M-1)] slots of M_j = L_j^-T (its triangle) and 1 / d_j, laid out by knot_factor_layout.h; on a
+                                    // 128-byte boundary inside a region of 2 (M-1) nk^2 doubles (nk <= 36), of which it uses a fraction
     double *boxlo, *boxhi;          // [nb][M][3]
     double *Lk, *Dk, *Ek;           // [M+1][9]
     double *segsc;                  // [M] dt^-5 (build_Q_p :349-351)
@@ -123,7 +124,9 @@ __device__ inline QpWs carve(double* base, const QpDims& d, int nbmax) {
     p += (4 - ((p - base) & 3)) & 3;  // 32-byte alignment of the blocks (vector loads of the tiled path)
     w.Td = p, p += (size_t)dm.nj * dm.ldb * dm.ldb;
     w.To = p, p += (size_t)(dm.nj > 1 ? dm.nj - 1 : 1) * dm.ldb * dm.ldb;
-    w.Lf = p, p += 2 * (size_t)dm.nj * (dm.nk < 36 ? dm.nk : 36) * (dm.nk < 36 ? dm.nk : 36);  // wave path only (a short last batch)
+    // wave path only (a short last batch).  The slots start on a 128-byte line (the mission's base is one: abi/session.hip): the region is
+    // more than twice what they need -- kf_stride(nk) <= nk^2 -- so the up to 15 doubles in front of them come out of it
+    w.Lf = p + ((16 - ((p - base) & 15)) & 15), p += 2 * (size_t)dm.nj * (dm.nk < 36 ? dm.nk : 36) * (dm.nk < 36 ? dm.nk : 36);
     w.boxlo = p, p += (size_t)nbmax * d.M * 3;
     w.boxhi = p, p += (size_t)nbmax * d.M * 3;
     w.Lk = p, p += (size_t)(d.M + 1) * 9;

@@ -459,7 +459,8 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
         flops += d.nk <= 36 ? (double)d.nj * ((7.0 / 6.0) * d.nk * (double)d.nk * d.nk + 6.0 * d.nk * (double)d.nk)
                             : (double)d.nj * (7.0 / 3.0) * d.nk * (double)d.nk * d.nk;
         PROF(4);
-        TRC(6, trc_sum(d.nk <= 36 ? w.Lf : w.Td, d.nk <= 36 ? (size_t)d.nj * 2 * d.nk * d.nk : (size_t)d.nj * d.ldb * d.ldb, red));
+        // (wave path: the knots' slots, as far as they go -- what a slot does not use stays as the workspace was cleared)
+        TRC(6, trc_sum(d.nk <= 36 ? w.Lf : w.Td, d.nk <= 36 ? (size_t)d.nj * (QP_LF_PACKED ? kf_stride(d.nk) : kf_sq_stride(d.nk)) : (size_t)d.nj * d.ldb * d.ldb, red));
         // ---- predictor
 #ifndef QP_TRACE
         if (d.nk <= 36) {

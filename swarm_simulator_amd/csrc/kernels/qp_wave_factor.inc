@@ -15,7 +15,7 @@
 // TWISTED ("burn at both ends") factorisation: wave 0 eliminates blocks 0 .. mid-1 upwards, wave 1 eliminates blocks
 // nj-1 .. mid+1 downwards, concurrently on two SIMDs; the middle block collects both Schur complements.  It halves the
 // length of the dependent chain (factor and substitutions alike) at no extra arithmetic.
-//   Lf[j] = M_j = L_j^-T (row r contiguous, zeros left of the diagonal), then 1 / d_j   (KF_STRIDE doubles per knot)
+//   Lf[j] = M_j = L_j^-T (the rows' triangle as one contiguous run), then 1 / d_j   (knot_factor_layout.h; KF_SLOT doubles per knot)
 __device__ __forceinline__ int twist_mid(int nj) { return nj / 2; }
 
 // Progress counters of the just-in-time block assembly (LDS ints behind the two chain areas): cnt[i] counts the helper waves that
@@ -69,7 +69,22 @@ __device__ __forceinline__ bool chol_rows(double (&a)[NK], double& dinv) {  // r
 // triangle + diagonal instead of the two full blocks (L_j, X_j: 20.7 KB) of the round-2 formulation; X never leaves the LDS.
 // The 36 x 36 blocks (kl_fused_path(NK)) do not store X at all: the chain forms S_j in the MFMA tiles straight from M_jp (kl_fused_update), each
 // operand element of X_j from three rows of M_jp and the knot's nine coupling coefficients, and the companion announces M_j before its read-back.
-#define KF_STRIDE(NK) ((NK) * (NK) + KL_I)  // doubles per knot in QpWs::Lf: M_j [NK][NK], then 1 / d_j
+// A knot's slot in QpWs::Lf (knot_factor_layout.h): the rows of M_j from the diagonal on (even NK: from the even column at or left of it, the
+// companion's 16-byte stores) one behind the other, then 1 / d_j -- 45 lines of 128 bytes for a 36 x 36 knot, which the staging threads of the
+// substitutions fetch as one run of 16-byte pairs, where the square image [NK][NK] spread the same triangle over 65 .. 69 lines (HBM moves
+// whole lines) and was fetched 8 bytes at a time.  QP_LF_PACKED = 0 keeps the square for the A/B (profiles/packed_m_ab.txt).
+#if QP_LF_PACKED
+#define KF_SLOT(NK) kf_stride(NK)           // doubles per knot
+#define KF_ELEM(NK, r, k) kf_elem(NK, r, k)  // M_j[r][k]
+#define KF_DINV(NK) kf_dinv(NK)             // 1 / d_j
+#else
+static_assert(KL_I == 40, "kf_sq_stride (knot_factor_layout.h) restates KL_I");
+#define KF_SLOT(NK) kf_sq_stride(NK)
+#define KF_ELEM(NK, r, k) kf_sq_elem(NK, r, k)
+#define KF_DINV(NK) kf_sq_dinv(NK)
+#endif
+static_assert(KF_SLOT(9) + 15 <= 2 * 81 && KF_SLOT(18) + 15 <= 2 * 324 && KF_SLOT(27) + 15 <= 2 * 729 && KF_SLOT(36) + 15 <= 2 * 1296,
+              "a knot's slot and the doubles in front of the first one fit the region carve() gives QpWs::Lf");
 
 // coefficients of row rr of the coupling block between knot j and the next knot of the chain: T_{j+dir,j}[rr][3g + q], g = rr / 3
 // (T_{j+1,j} = blockdiag(E_{knot j+1}'), T_{j-1,j} = T_{j,j-1}'; see assemble_blocks)
@@ -158,12 +173,12 @@ __device__ __forceinline__ void knot_inverse(const QpWs& w, int j, kl_lds* base,
     // (kl_inverse_rows announces *Mdone = done_value as soon as the chain may go on: after the read of 1 / d -- its next block overwrites I --, and on
     // the fused path BEFORE the read-back of the row that the stores below need)
     const double dinv = kl_inverse_rows<NK, FOLLOW>(m, C, I, MX, r, act, P, pbase, Mdone, done_value);
-    __attribute__((address_space(1))) double* Mg = QG(w.Lf + (size_t)j * KF_STRIDE(NK));
+    __attribute__((address_space(1))) double* Mg = QG(w.Lf + (size_t)j * KF_SLOT(NK));
     // (256-thread build: the next block's inputs, sent for a block ago by global_load_lds, are counted on this wave's memory counter; they have
     // long landed -- drain the counter HERE, so that the tiles' wait for them does not have to wait for the row stores below as well)
     if (FOLLOW && QP_FOLLOW_ASM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (act) {  // row r of M_j and 1 / d_j -> QpWs::Lf (16 bytes per lane and store instruction: the store path of a CU is issue bound)
-        __attribute__((address_space(1))) double* row = Mg + (size_t)r * NK;
+        __attribute__((address_space(1))) double* row = Mg + KF_ELEM(NK, r, 0);  // (where column 0 would be: only k >= kf_first(NK, r) is stored)
         if ((NK & 1) == 0) {
 #pragma unroll
             for (int k = 0; k < NK; k += 2)
@@ -173,7 +188,7 @@ __device__ __forceinline__ void knot_inverse(const QpWs& w, int j, kl_lds* base,
             for (int k = 0; k < NK; ++k)
                 if (k >= r) row[k] = m[k];
         }
-        Mg[NK * NK + r] = dinv;
+        Mg[KF_DINV(NK) + r] = dinv;
     }
 }
 

@@ -1,6 +1,6 @@
 // qp_wave_solve.inc — the wave-register path (nk <= 36), substitutions: products with the knots' M_j staged through LDS (KsPieces ..
-// solve_staged).  Included by qp.hip after qp_wave_factor.inc, whose twist_mid, KF_STRIDE and coupling_coef it needs; from qp.hip the levers
-// (QP_THREADS, QP_STAGE_BUFS, QP_STAGE_REGS, QP_CHAIN_PRIO) and QG / QGC; QpDims, QpWs (qp_base.inc); kl_lds, kl_sync, KL_LD, KL_I (knot_lds.inc).
+// solve_staged).  Included by qp.hip after qp_wave_factor.inc, whose twist_mid, KF_SLOT / KF_ELEM / KF_DINV and coupling_coef it needs; from qp.hip the levers
+// (QP_THREADS, QP_STAGE_BUFS, QP_STAGE_REGS, QP_LF_PACKED, QP_CHAIN_PRIO), knot_factor_layout.h and QG / QGC; QpDims, QpWs (qp_base.inc); kl_lds, kl_sync, KL_LD, KL_I (knot_lds.inc).
 
 // Substitutions T du = rhs for the twisted factorisation (round 3: matrix-vector products with the explicit M_j = L_j^-T instead of
 // 36-step dependent triangular solves).  With X_j = T_{j,jp} M_jp (jp = the chain's previous knot, never stored):
@@ -52,6 +52,91 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
     lds += KS::LEAD;                                   // (zero-filled with the stage buffers below)
     kl_lds* vec = (kl_lds*)(lds + QP_STAGE_BUFS * STG);  // nj*NK: rhs -> z -> x  (LDS pointers: through generic ones every access is a flat instruction)
     kl_lds* small = vec + ((nj * NK + 1) & ~1);        // [2 chains][A, Z, V][KS_VLEN], then [2 chains][64] partial sums
+    // block indices handled at step s by the left / right wave (-1: idle)
+    auto left_j = [&](int s) { return s < SF ? (s - (SF - nl) >= 0 ? s - (SF - nl) : -1) : (s == SF ? mid : (mid - 1 - (s - SF - 1) >= 0 ? mid - 1 - (s - SF - 1) : -1)); };
+    auto right_j = [&](int s) { return s < SF ? (s - (SF - nr) >= 0 ? nj - 1 - (s - (SF - nr)) : -1) : (s == SF ? -1 : (mid + 1 + (s - SF - 1) <= nj - 1 ? mid + 1 + (s - SF - 1) : -1)); };
+    // Staging (waves 2..): what a knot left for the substitutions -- the triangle of M_j, row behind row, then 1 / d_j -- is ONE RUN of
+    // QpWs::Lf (knot_factor_layout.h), and the staging threads share the two chains' runs in UNITS of 16 bytes (odd NK: 8), consecutive
+    // threads consecutive units: thread t has the units t, t + NST, ... of the left chain's run followed by the right chain's, the same for
+    // every step.  Their sources follow from the unit's number; their destinations inside a stage are mapped once per call, so that a
+    // step is ONE batch of loads in flight per thread and a batch of LDS stores.  What lies left of the diagonal in the stage buffers is
+    // zero-filled once per call (an odd row's first pair brings the zero left of its diagonal along).
+    // (QP_LF_PACKED = 0: the square image, a unit is one of the NE doubles of the triangle and 1 / d_j, and its source is mapped as well.)
+    constexpr bool PK = QP_LF_PACKED != 0;
+    constexpr int NTRI = NK * (NK + 1) / 2, NE = NTRI + NK;
+    constexpr int UN = PK ? kf_unit(NK) : 1, NU = PK ? kf_units(NK) : NE;  // doubles per unit, units per chain
+    constexpr int NST = QP_THREADS - 128, MAXE = (2 * NU + NST - 1) / NST;
+    typedef typename std::conditional<UN == 2, kl_d2, double>::type unit_t;
+    // (explicitly GLOBAL loads and LDS stores: through generic pointers they are flat instructions, which count on both memory counters
+    // and make the compiler wait for ALL of them at the first use -- no load would stay in flight across a barrier)
+    typedef __attribute__((address_space(1))) const double gdbl;
+    typedef __attribute__((address_space(1))) const unit_t gunit;
+    typedef __attribute__((address_space(3))) unit_t lunit;
+    static_assert(UN == 1 || (KL_LD % 2 == 0 && SM % 2 == 0 && SCH % 2 == 0 && STG % 2 == 0 && KS::LEAD % 2 == 0), "16-byte units: even offsets in a stage");
+    int doff[MAXE];                              // unit u of this thread: destination inside a stage (-1: none)
+    [[maybe_unused]] int soff[PK ? 1 : MAXE];    // square image: its source offset inside a knot's slot
+    if (ROLE == 1) {
+#pragma unroll
+        for (int u = 0; u < MAXE; ++u) {
+            const int e = (tid - 128) + u * NST;
+            doff[u] = -1;
+            if constexpr (!PK) soff[u] = 0;
+            if (e < 2 * NU) {
+                [[maybe_unused]] const int side = e >= NU, idx = side ? e - NU : e;
+                if constexpr (PK) {
+                    const int dd = kf_stage_dst(NK, kf_unit_off(NK, e), KL_LD, SM);  // (-1: the gap between an odd triangle and 1 / d)
+                    doff[u] = dd >= 0 ? kf_unit_side(NK, e) * SCH + dd : -1;
+                } else if (idx < NTRI) {
+                    int rw = (int)(((2 * NK + 1) - sqrtf((float)((2 * NK + 1) * (2 * NK + 1) - 8 * idx))) * 0.5f);
+                    if (rw * NK - rw * (rw - 1) / 2 > idx) rw--;
+                    if ((rw + 1) * NK - (rw + 1) * rw / 2 <= idx) rw++;
+                    const int k = rw + idx - (rw * NK - rw * (rw - 1) / 2);
+                    soff[u] = KF_ELEM(NK, rw, k), doff[u] = side * SCH + rw * KL_LD + k;
+                } else {
+                    soff[u] = KF_DINV(NK) + (idx - NTRI), doff[u] = side * SCH + SM + (idx - NTRI);
+                }
+            }
+        }
+    }
+    // unit u of this thread at the chains' slots srcl / srcr.  No predicates: a unit nobody needs (behind both runs; a chain that idles:
+    // the callers pass knot 0) reads a valid address and is never stored where a product sees it -- straight-line loads are what lets the
+    // compiler count them (s_waitcnt vmcnt(n), n > 0) instead of waiting for all
+    auto unit_src = [&](int u, gdbl* srcl, gdbl* srcr) {
+        if constexpr (PK) {
+            const int e = (tid - 128) + u * NST;
+            return (gunit*)((kf_unit_side(NK, e) ? srcr : srcl) + (e < 2 * NU ? kf_unit_off(NK, e) : 0));
+        } else {
+            return (gunit*)((doff[u] >= SCH ? srcr : srcl) + soff[u]);
+        }
+    };
+    auto stage_load = [&](int s, unit_t (&tmp)[MAXE]) {
+        if (s >= nsteps) return;
+        const int jl = left_j(s), jr = right_j(s);
+        gdbl* srcl = (gdbl*)(w.Lf + (size_t)(jl >= 0 ? jl : 0) * KF_SLOT(NK));
+        gdbl* srcr = (gdbl*)(w.Lf + (size_t)(jr >= 0 ? jr : 0) * KF_SLOT(NK));
+#pragma unroll
+        for (int u = 0; u < MAXE; ++u) tmp[u] = *unit_src(u, srcl, srcr);
+    };
+    auto stage_store = [&](int s, const unit_t (&tmp)[MAXE], double* buf) {
+        if (s >= nsteps) return;
+        const int jl = left_j(s), jr = right_j(s);
+        kl_lds* bl = (kl_lds*)buf;
+#pragma unroll
+        for (int u = 0; u < MAXE; ++u) {
+            const bool right = doff[u] >= SCH;
+            if (doff[u] >= 0 && (right ? jr >= 0 : jl >= 0)) *(lunit*)(bl + doff[u]) = tmp[u];
+        }
+    };
+    auto stage = [&](int s, double* buf) {  // one step's blocks, loaded and stored on the spot
+        unit_t tmp[MAXE];
+        stage_load(s, tmp);
+        stage_store(s, tmp, buf);
+    };
+    // (round 6) The two halves apart let a staging thread's loads stay in flight ACROSS step barriers: under full load a trip to global
+    // memory (3-5 us) is longer than a chain step (~1.5 us), and a staging wave that loads, waits and stores inside one step made every
+    // step as long as that trip however many stage buffers there were (which is why a third buffer never paid).  With QP_STAGE_REGS = R
+    // register sets the loads of step s + QP_STAGE_BUFS - 1 + R are issued at step s and stored R steps later.
+    // (Issuing the call's first loads up here, ahead of the right-hand side's own, was built and measured: no gain; profiles/packed_m_ab.txt.)
     if (FWD ? so.rhs_mode == 1 || so.rhs_mode == 2 : so.rhs_mode != 0) {  // rhs_from_acc into the LDS vector (same arithmetic): rhs = rbase + F'(G'v) of the sweep's accumulators
         constexpr int nu = NK / 3;
         const int oq = so.oq;
@@ -83,82 +168,11 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
         }
     }
     for (int i = tid; i < KS::VECS; i += QP_THREADS) small[i] = 0.0;
-    // block indices handled at step s by the left / right wave (-1: idle)
-    auto left_j = [&](int s) { return s < SF ? (s - (SF - nl) >= 0 ? s - (SF - nl) : -1) : (s == SF ? mid : (mid - 1 - (s - SF - 1) >= 0 ? mid - 1 - (s - SF - 1) : -1)); };
-    auto right_j = [&](int s) { return s < SF ? (s - (SF - nr) >= 0 ? nj - 1 - (s - (SF - nr)) : -1) : (s == SF ? -1 : (mid + 1 + (s - SF - 1) <= nj - 1 ? mid + 1 + (s - SF - 1) : -1)); };
-    // Staging (waves 2..): only the upper triangle of M_j and 1 / d_j are fetched -- NE elements per chain -- and every staging thread's
-    // elements (the same for every step) are mapped once per call, so that a step is ONE batch of loads in flight per thread and a
-    // batch of LDS stores.  What lies left of the diagonal in the stage buffers is zero-filled once per call.
-    constexpr int NTRI = NK * (NK + 1) / 2, NE = NTRI + NK, NST = QP_THREADS - 128, MAXE = (2 * NE + NST - 1) / NST;
-    int soff[MAXE], doff[MAXE];  // element u of this thread: source offset inside a knot's Lf slot, destination inside a stage (-1: none)
-    if (ROLE == 1) {
-#pragma unroll
-        for (int u = 0; u < MAXE; ++u) {
-            const int e = (tid - 128) + u * NST;
-            soff[u] = 0, doff[u] = -1;
-            if (e < 2 * NE) {
-                const int side = e >= NE, idx = side ? e - NE : e;
-                if (idx < NTRI) {
-                    int rw = (int)(((2 * NK + 1) - sqrtf((float)((2 * NK + 1) * (2 * NK + 1) - 8 * idx))) * 0.5f);
-                    if (rw * NK - rw * (rw - 1) / 2 > idx) rw--;
-                    if ((rw + 1) * NK - (rw + 1) * rw / 2 <= idx) rw++;
-                    const int k = rw + idx - (rw * NK - rw * (rw - 1) / 2);
-                    soff[u] = rw * NK + k, doff[u] = side * SCH + rw * KL_LD + k;
-                } else {
-                    soff[u] = NK * NK + (idx - NTRI), doff[u] = side * SCH + SM + (idx - NTRI);
-                }
-            }
-        }
-    }
     for (int i = tid; i < KS::LEAD + QP_STAGE_BUFS * STG; i += QP_THREADS) (lds - KS::LEAD)[i] = 0.0;
     __syncthreads();
     if (bwd_only && tid < NK) small[KS_VPAD + 2 * KS_VLEN + tid] = small[KS_VPAD + 5 * KS_VLEN + tid] = vec[mid * NK + tid];  // x_mid into both chains' V
-    auto stage = [&](int s, double* buf) {
-        const int jl = left_j(s), jr = right_j(s);
-        const double* srcl = w.Lf + (size_t)(jl >= 0 ? jl : 0) * KF_STRIDE(NK);
-        const double* srcr = w.Lf + (size_t)(jr >= 0 ? jr : 0) * KF_STRIDE(NK);
-        double tmp[MAXE];
-#pragma unroll
-        for (int u = 0; u < MAXE; ++u) {
-            const bool right = doff[u] >= SCH;
-            const bool on = doff[u] >= 0 && (right ? jr >= 0 : jl >= 0);
-            tmp[u] = on ? (right ? srcr : srcl)[soff[u]] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < MAXE; ++u) {
-            const bool right = doff[u] >= SCH;
-            if (doff[u] >= 0 && (right ? jr >= 0 : jl >= 0)) buf[doff[u]] = tmp[u];
-        }
-    };
-    // (round 6) the same in two halves, so that a staging thread's loads can stay in flight ACROSS step barriers: under full load a trip to global
-    // memory (3-5 us) is longer than a chain step (~1.5 us), and a staging wave that loads, waits and stores inside one step made every
-    // step as long as that trip however many stage buffers there were (which is why a third buffer never paid).  With QP_STAGE_REGS = R
-    // register sets the loads of step s + QP_STAGE_BUFS - 1 + R are issued at step s and stored R steps later.
-    auto stage_load = [&](int s, double (&tmp)[MAXE]) {
-        if (s >= nsteps) return;
-        const int jl = left_j(s), jr = right_j(s);
-        // (explicitly GLOBAL loads and LDS stores: through generic pointers they are flat instructions, which count on both memory counters
-        // and make the compiler wait for ALL of them at the first use -- no load would stay in flight across a barrier)
-        typedef __attribute__((address_space(1))) const double gdbl;
-        gdbl* srcl = (gdbl*)(w.Lf + (size_t)(jl >= 0 ? jl : 0) * KF_STRIDE(NK));
-        gdbl* srcr = (gdbl*)(w.Lf + (size_t)(jr >= 0 ? jr : 0) * KF_STRIDE(NK));
-        // no predicates: a load nobody needs reads a valid address (soff = 0, knot 0) and is never stored -- straight-line loads are what
-        // lets the compiler count them (s_waitcnt vmcnt(n), n > 0) instead of waiting for all
-#pragma unroll
-        for (int u = 0; u < MAXE; ++u) tmp[u] = (doff[u] >= SCH ? srcr : srcl)[soff[u]];
-    };
-    auto stage_store = [&](int s, const double (&tmp)[MAXE], double* buf) {
-        if (s >= nsteps) return;
-        const int jl = left_j(s), jr = right_j(s);
-        kl_lds* bl = (kl_lds*)buf;
-#pragma unroll
-        for (int u = 0; u < MAXE; ++u) {
-            const bool right = doff[u] >= SCH;
-            if (doff[u] >= 0 && (right ? jr >= 0 : jl >= 0)) bl[doff[u]] = tmp[u];
-        }
-    };
-    if (ROLE == 1)
-        for (int s0 = s_first; s0 < s_first + QP_STAGE_BUFS - 1 && s0 < nsteps; ++s0) stage(s0, lds + (bwd_only ? s0 % QP_STAGE_BUFS : s0) * STG);
+    if (ROLE == 1)  // the stages the chains start with
+        for (int s0 = s_first; s0 < s_first + QP_STAGE_BUFS - 1 && s0 < nsteps; ++s0) stage(s0, lds + (s0 % QP_STAGE_BUFS) * STG);
     __syncthreads();
     const int wave = ROLE == 0 ? (tid >> 6) & 1 : 2, r = tid & 63;  // (role 1 only needs "wave >= 2")
     const bool act = r < NK;
@@ -197,38 +211,39 @@ __device__ __forceinline__ void solve_staged(const QpDims& d, const QpWs& w, dou
 #endif
     if (ROLE == 1 && QP_STAGE_REGS > 0) {
         constexpr int R = QP_STAGE_REGS > 0 ? QP_STAGE_REGS : 1;
-        double tq[R][MAXE];
+        unit_t tq[R][MAXE];
 #pragma unroll
         for (int k = 0; k < R; ++k) stage_load(s_first + QP_STAGE_BUFS - 1 + k, tq[k]);
         // steady state, straight-line (no predicate, no branch between a load and its store: only then does the compiler count the loads in
-        // flight instead of waiting for all of them): every element is stored -- the ones a thread does not have go to a padding column
-        // nobody's products see (row 0, column KL_LD - 1, times the zero padding of the vectors), a chain that idles at a step gets knot 0's
-        // numbers into its half of the buffer, which it does not read
+        // flight instead of waiting for all of them): every unit is stored -- the ones a thread does not have go to padding columns
+        // nobody's products see (row 0, from column NK for a 16-byte unit, else column KL_LD - 1: times the zero padding of the vectors), a
+        // chain that idles at a step gets knot 0's numbers into its half of the buffer, which it does not read
+        constexpr int DUMP = UN == 2 ? NK : KL_LD - 1;
+        static_assert(DUMP + UN <= KL_LD, "the padding columns of row 0");
         int dsto[MAXE];
 #pragma unroll
-        for (int u = 0; u < MAXE; ++u) dsto[u] = doff[u] >= 0 ? doff[u] : KL_LD - 1;
-        typedef __attribute__((address_space(1))) const double gdbl;
+        for (int u = 0; u < MAXE; ++u) dsto[u] = doff[u] >= 0 ? doff[u] : DUMP;
         // The loads of the NEXT R steps are issued at the top of an iteration and first touched at its bottom, R step barriers later: the
         // compiler drains the memory counter completely wherever a loop-carried load is used (it does not count across a back edge), so the
         // one place where everything must have landed is made to be the place where it drains.
-        double nq[R][MAXE];
+        unit_t nq[R][MAXE];
         int s = s_first;
         for (; s + 2 * R + QP_STAGE_BUFS - 1 <= nsteps; s += R) {
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 const int sl = s + R + k + QP_STAGE_BUFS - 1;
                 const int jl = left_j(sl), jr = right_j(sl);
-                gdbl* srcl = (gdbl*)(w.Lf + (size_t)(jl >= 0 ? jl : 0) * KF_STRIDE(NK));
-                gdbl* srcr = (gdbl*)(w.Lf + (size_t)(jr >= 0 ? jr : 0) * KF_STRIDE(NK));
+                gdbl* srcl = (gdbl*)(w.Lf + (size_t)(jl >= 0 ? jl : 0) * KF_SLOT(NK));
+                gdbl* srcr = (gdbl*)(w.Lf + (size_t)(jr >= 0 ? jr : 0) * KF_SLOT(NK));
 #pragma unroll
-                for (int u = 0; u < MAXE; ++u) nq[k][u] = (doff[u] >= SCH ? srcr : srcl)[soff[u]];
+                for (int u = 0; u < MAXE; ++u) nq[k][u] = *unit_src(u, srcl, srcr);
             }
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 const int sp = s + k + QP_STAGE_BUFS - 1;
                 kl_lds* bl = (kl_lds*)(lds + (sp % QP_STAGE_BUFS) * STG);
 #pragma unroll
-                for (int u = 0; u < MAXE; ++u) bl[dsto[u]] = tq[k][u];
+                for (int u = 0; u < MAXE; ++u) *(lunit*)(bl + dsto[u]) = tq[k][u];
                 __syncthreads();
             }
 #pragma unroll
