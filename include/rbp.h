@@ -346,7 +346,8 @@ void rbp_release_thread_context(void);
                               4: rbp_solver_opts (the library no longer reads environment variables); 5: rbp_session_shard_joint, RBP_ERR_EXCHANGE;
                               6: rbp_param.timescale_rule, rbp_plan.time_scale_alt */
 enum { RBP_SIZEOF_WORLD = 0, RBP_SIZEOF_MISSION = 1, RBP_SIZEOF_PARAM = 2, RBP_SIZEOF_PLAN = 3, RBP_SIZEOF_COUNTERS = 4, RBP_SIZEOF_DEVICE_ARRAYS = 5,
-       RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7, RBP_SIZEOF_REPORT = 8, RBP_SIZEOF_DYNAMICS = 9, RBP_SIZEOF_CLEARANCE = 10, RBP_SIZEOF_SEPARATION = 11 };
+       RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7, RBP_SIZEOF_REPORT = 8, RBP_SIZEOF_DYNAMICS = 9, RBP_SIZEOF_CLEARANCE = 10, RBP_SIZEOF_SEPARATION = 11,
+       RBP_SIZEOF_SWEPT_CLEARANCE = 12 };
 int rbp_abi_version(void);
 size_t rbp_sizeof(int which);
 const char* rbp_version(void);
@@ -607,6 +608,60 @@ int rbp_session_separation(rbp_session* s, int32_t depth, double refine_below, r
 int rbp_dev_separation(int device, int32_t K, int32_t N, const int32_t* M, int32_t M_stride, const double* T,
                        const double* time_scale, const double* coef, const double* radius, double downwash,
                        int32_t depth, double refine_below, rbp_separation* out, double* pair_lower);
+
+/* ---- a certified interval for the smallest clearance of resident plans to the obstacles in CONTINUOUS time ----
+ * rbp_clearance reads the distance grid under every agent at the samples t = j * dt; between two samples a fast agent crosses many cells.
+ * For an agent a and a segment m (an ITEM) every axis of the position is a polynomial of degree 5; a PIECE of the segment (piece p of
+ * depth D covers [p / 2^D, (p+1) / 2^D] of it) lies in the box of its Bernstein control points.  The grid's lookup (rbp_world) is monotone
+ * per axis, so the keys of the box's corners, each corner moved outwards by a counted rounding term, enclose the key of every point of
+ * the piece, and the smallest grid value over that box of cells (d_lo) bounds every reading on the piece from below.  The smaller of
+ * the two lookups at the piece's first and last control point (d_up) is a reading on the curve.  A piece whose box leaves the grid is
+ * OUTSIDE and one whose box holds more than RBP_SWEPT_MAX_CELLS cells is OVER BUDGET: neither is scanned, and d_lo is -1.  All of it
+ * -- the Bernstein form, the halving, the widening e = (20 + 5 D) 2^-53 A with its derivation, the keys, the order of the minima -- is
+ * the rule of csrc/common/swept_rules.h, which the kernels (kernels/swept.hip) and rbp_swept_clearance_host of rbp_host.h share: both
+ * return the same bits.  The promise, for the polynomials the double coefficients define and a grid whose values are >= -1:
+ *     every reading lookup(p_a(t)) - radius_a, at every instant t of [0, Ts[M]], is >= lower_clearance;
+ * lower_clearance > -1e-6, that is uncertified == 0, certifies the plan against the reference's own hit test (d < radius - 1e-6).
+ * upper_clearance is a reading at a point the rule computed on the curve, within e of it: a witness (hitting > 0 shows a hit there),
+ * not a bound on the exact polynomial.  The lookup is a step function of the position, so nothing stronger is claimed.
+ * Refinement is fixed: every item is evaluated at depth 0; an item whose depth-0 box is outside or over budget, or whose lower
+ * clearance there is not >= refine_below (a NaN goes too), is evaluated again on all 2^depth pieces of depth `depth`, which replace its
+ * depth-0 readings and flags.  depth in 0 .. RBP_SWEPT_MAX_DEPTH; refine_below any number (1e9 refines everything; -2 only what is
+ * outside or over budget).  The minima name the lexicographically first (segment, piece, agent) among equal clearances -- grid values
+ * are quantised and clamped, so ties are common; a NaN, or 1e9 and more, is never a minimum.
+ * agent_lower [K][N] (NULL: not wanted): an agent's smallest lower clearance over its segments, 1e9 where none is a number; the row of a
+ * mission with a status is left untouched.  It may be a host pointer or a device pointer on the plans' device (classified as
+ * rbp_world.dist is; another device: RBP_ERR_BAD_ARGUMENT): a device destination is written in place by the kernels, a host
+ * destination goes through one staging buffer and one copy.
+ * Memory: items that are refined go through a work list of one uint32 per item, sized for the worst case (every item), of at most
+ * RBP_SWEPT_LIST_BYTES; missions are processed in chunks where all of them would need more (a single mission always is one chunk, and
+ * one of more than 2^32 - 64 items is refused).  No allocation depends on the data.
+ * rbp_session_swept_clearance: of a session's K missions, from its own coef, T, time scale, radius, status and worlds, all of which stay
+ *   in HBM; waits for an asynchronous solve like every call, enqueues its kernels on `stream`, copies K structs back in one copy and
+ *   returns when they have arrived.  Nothing of the session changes.  A mission whose status is not 0 gets that status and nothing
+ *   computed.  RBP_ERR_BAD_ARGUMENT: a session whose last run did not include the PLANNER stage; and, before a device is looked for, a
+ *   null pointer, a depth outside 0 .. RBP_SWEPT_MAX_DEPTH, a refine_below that is no number.
+ * rbp_dev_swept_clearance: the same kernels on a caller's host arrays in rbp_dev_clearance's layout, uploaded once; worlds[k].dist may be
+ *   a host or a device pointer.  Argument errors (those above, K, N <= 0, an M[k] outside 1..M_stride, a time scale <= 0, a world
+ *   without a grid, with a res <= 0 or a dim <= 0) are RBP_ERR_BAD_ARGUMENT before a device is looked for. */
+#define RBP_SWEPT_MAX_DEPTH 8
+#define RBP_SWEPT_MAX_CELLS 4096             /* the most cells of one piece's box that are scanned */
+#define RBP_SWEPT_LIST_BYTES (64u << 20)     /* the work list's budget: 16 Mi items of a chunk of missions */
+typedef struct rbp_swept_clearance {
+    double  lower_clearance, upper_clearance;   /* 1e9: none */
+    double  lower_dist, upper_dist;             /* the readings d_lo and d_up at the two minima (-1: outside or over budget) */
+    double  end_time;                           /* Ts[M]: the mission's last segment time, scaled */
+    int64_t uncertified, hitting, outside, over_budget, refined;   /* items (agent, segment) */
+    int32_t lower_segment, lower_piece, lower_agent, lower_depth;   /* -1: none */
+    int32_t upper_segment, upper_piece, upper_agent, upper_depth;
+    int32_t status, reserved;                   /* the mission's status; != 0: nothing computed, zeros, indices -1 */
+} rbp_swept_clearance;
+int rbp_session_swept_clearance(rbp_session* s, int32_t depth, double refine_below, rbp_swept_clearance* out /* [K] */,
+                                double* agent_lower /* [K][N] or NULL; host or device pointer */, void* stream);
+int rbp_dev_swept_clearance(int device, int32_t K, int32_t N, const int32_t* M, int32_t M_stride, const double* T,
+                            const double* time_scale, const double* coef, const double* radius,
+                            const rbp_world* worlds /* [K]; dist host or device */, int32_t depth, double refine_below,
+                            rbp_swept_clearance* out, double* agent_lower);
 
 const char* rbp_last_error(void);
 int rbp_device_count(void);

@@ -111,6 +111,14 @@ int rbp_clearance_host(const rbp_world* world, const rbp_mission* mission, int32
 int rbp_separation_host(const rbp_mission* mission, const rbp_param* param, int32_t M, const double* T, const double* coef,
                         int32_t depth, double refine_below, rbp_separation* out, double* pair_lower /* [N (N-1) / 2] or NULL */);
 
+/* The certified interval of one plan's smallest clearance to the obstacles of `world` in continuous time as an rbp_swept_clearance (rbp.h),
+ * by the sequential loop of csrc/common/swept_rules.h that the device shares: what rbp_session_swept_clearance / rbp_dev_swept_clearance
+ * return for the same plan and grid, bit for bit, and their reference.  T as downloaded (scaled); radius is the mission's; world->dist a
+ * host grid.  depth in 0 .. RBP_SWEPT_MAX_DEPTH and refine_below a number, otherwise RBP_ERR_BAD_ARGUMENT.  agent_lower [N] may be NULL.
+ * out->status is 0. */
+int rbp_swept_clearance_host(const rbp_world* world, const rbp_mission* mission, int32_t M, const double* T, const double* coef,
+                             int32_t depth, double refine_below, rbp_swept_clearance* out, double* agent_lower /* [N] or NULL */);
+
 /* crazyswarm CSV of rbp_planner.hpp:295-324 (one file per agent: <dir>/coef<qi+1>.csv) */
 int rbp_write_coef_csv(const char* dir, int32_t N, int32_t M, const double* T, const double* coef);
 

@@ -137,6 +137,20 @@ class rbp_separation(C.Structure):
                 ("lower_depth", C.c_int32), ("upper_depth", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+RBP_SIZEOF_SWEPT_CLEARANCE = 12
+RBP_SWEPT_MAX_DEPTH = 8
+RBP_SWEPT_MAX_CELLS = 4096
+
+
+class rbp_swept_clearance(C.Structure):
+    _fields_ = [("lower_clearance", C.c_double), ("upper_clearance", C.c_double), ("lower_dist", C.c_double), ("upper_dist", C.c_double),
+                ("end_time", C.c_double),
+                ("uncertified", C.c_int64), ("hitting", C.c_int64), ("outside", C.c_int64), ("over_budget", C.c_int64), ("refined", C.c_int64),
+                ("lower_segment", C.c_int32), ("lower_piece", C.c_int32), ("lower_agent", C.c_int32), ("lower_depth", C.c_int32),
+                ("upper_segment", C.c_int32), ("upper_piece", C.c_int32), ("upper_agent", C.c_int32), ("upper_depth", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class rbp_mission_buf(C.Structure):
     _fields_ = [("N", C.c_int32), ("start", c_double_p), ("goal", c_double_p), ("radius", c_double_p),
                 ("speed", c_double_p), ("max_vel", c_double_p), ("max_acc", c_double_p)]

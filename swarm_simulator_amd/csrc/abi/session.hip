@@ -112,6 +112,7 @@ struct rbp_session {
     char* dynamics_buf = nullptr;  // rbp_session_dynamics: K structs and the state kernel's partial peaks (dynamics_workspace_bytes), reserved by the first call
     char* separation_buf = nullptr;  // rbp_session_separation: K structs, one chunk's work list and partial tallies (separation_workspace_bytes), reserved by the first call
     char* clearance_buf = nullptr;  // rbp_session_clearance: K structs and the agent kernel's records (clearance_workspace_bytes), reserved by the first call
+    char* swept_buf = nullptr;  // rbp_session_swept_clearance: K structs, one chunk's work list, item clearances and partial tallies (swept_workspace_bytes), reserved by the first call
 };
 
 // waits for the session's asynchronous joint run, if one is in flight; reports its error once
@@ -141,6 +142,7 @@ size_t rbp_sizeof(int which) {
         case RBP_SIZEOF_DYNAMICS: return sizeof(rbp_dynamics);
         case RBP_SIZEOF_CLEARANCE: return sizeof(rbp_clearance);
         case RBP_SIZEOF_SEPARATION: return sizeof(rbp_separation);
+        case RBP_SIZEOF_SWEPT_CLEARANCE: return sizeof(rbp_swept_clearance);
         default: return 0;
     }
 }
@@ -968,6 +970,33 @@ int rbp_session_separation(rbp_session* s, int32_t depth, double refine_below, r
     return separation_run("rbp_session_separation", s->device, in, out, pair_lower, s->separation_buf, (hipStream_t)stream);
 }
 
+// A certified interval for the missions' smallest clearance to the obstacles in continuous time from where the plans and the grids lie
+// (kernels/swept.hip): the report's inputs and the session's worlds are read in place, K structs come back in one copy, the agents' lower
+// clearances go where the caller wants them, and nothing of the session is written.
+int rbp_session_swept_clearance(rbp_session* s, int32_t depth, double refine_below, rbp_swept_clearance* out, double* agent_lower, void* stream) {
+    if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_swept_clearance: null argument");
+    if (int rc = swept_check_arguments("rbp_session_swept_clearance", depth, refine_below)) return rc;
+    if (int jrc = join_worker(s)) return jrc;
+    if (!(s->last_stages & RBP_STAGE_PLANNER))
+        return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_swept_clearance: the session's last run did not include the PLANNER stage: there are no coefficients to bound");
+    const DevSession& d = s->d;
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->swept_buf) {
+        const hipError_t e = hipMalloc((void**)&s->swept_buf, swept_workspace_bytes(d.K, d.N, d.M));
+        if (e != hipSuccess) {
+            s->swept_buf = nullptr;
+            return fail(RBP_ERR_HIP, std::string("rbp_session_swept_clearance: workspace: ") + hipGetErrorString(e));
+        }
+    }
+    SweptInputs in{};
+    in.r.K = d.K, in.r.N = d.N, in.r.M_stride = d.M, in.r.Mk = d.Mk, in.r.T = d.T, in.r.coef = d.coef, in.r.radius = d.radius;
+    in.r.ts = d.scalars + SC_TIME_SCALE, in.r.ts_stride = SC_N, in.r.status = d.status;
+    in.r.downwash = d.p.downwash, in.r.dt = 0.0;
+    in.worlds = d.worlds;
+    in.depth = depth, in.refine_below = refine_below;
+    return swept_run("rbp_session_swept_clearance", s->device, in, out, agent_lower, s->swept_buf, (hipStream_t)stream);
+}
+
 int rbp_session_device_arrays(rbp_session* s, int32_t mission, rbp_device_arrays* out) {
     if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "null argument");
     const DevSession& d = s->d;
@@ -1049,6 +1078,10 @@ void rbp_session_destroy(rbp_session* s) {
     if (s->separation_buf) {
         (void)hipSetDevice(s->device);
         (void)hipFree(s->separation_buf);
+    }
+    if (s->swept_buf) {
+        (void)hipSetDevice(s->device);
+        (void)hipFree(s->swept_buf);
     }
     if (s->ctx) {
         s->ctx->busy = false;  // the arena (and the QP workspace) stay with the context

@@ -9,6 +9,7 @@
 #include "common/report_rules.h"
 #include "common/separation_rules.h"
 #include "common/state_rules.h"
+#include "common/swept_rules.h"
 
 #include <cmath>
 #include <cstdio>
@@ -127,6 +128,25 @@ extern "C" int rbp_separation_host(const rbp_mission* mission, const rbp_param* 
     out->lower_segment = t.lower.segment, out->lower_piece = t.lower.piece, out->lower_qi = t.lower.qi, out->lower_qj = t.lower.qj;
     out->upper_segment = t.upper.segment, out->upper_piece = t.upper.piece, out->upper_qi = t.upper.qi, out->upper_qj = t.upper.qj;
     out->lower_depth = t.lower.depth, out->upper_depth = t.upper.depth;
+    out->status = 0, out->reserved = 0;
+    return RBP_OK;
+}
+
+// The certified interval of the plan's smallest clearance to the obstacles in continuous time by the rule of common/swept_rules.h, which
+// the device's swept kernels (kernels/swept.hip) share.  T arrives scaled, so the scale is 1.
+extern "C" int rbp_swept_clearance_host(const rbp_world* world, const rbp_mission* mission, int32_t M, const double* T, const double* coef,
+                                        int32_t depth, double refine_below, rbp_swept_clearance* out, double* agent_lower) {
+    if (!world || !mission || !T || !coef || !out || !world->dist || !mission->radius || mission->N <= 0 || M <= 0 || depth < 0 ||
+        depth > RBP_SWEPT_MAX_DEPTH || refine_below != refine_below || !(world->res > 0) || world->dim[0] <= 0 || world->dim[1] <= 0 ||
+        world->dim[2] <= 0)
+        return RBP_ERR_BAD_ARGUMENT;
+    const swept_rules::Tally t = swept_rules::swept_sequential(mission->N, M, T, 1.0, coef, mission->radius, world->dim, world->key_min, world->res,
+                                                               world->dist, depth, refine_below, agent_lower);
+    out->lower_clearance = t.lower.clearance, out->upper_clearance = t.upper.clearance;
+    out->lower_dist = t.lower.dist, out->upper_dist = t.upper.dist, out->end_time = T[M];
+    out->uncertified = t.uncertified, out->hitting = t.hitting, out->outside = t.outside, out->over_budget = t.over_budget, out->refined = t.refined;
+    out->lower_segment = t.lower.segment, out->lower_piece = t.lower.piece, out->lower_agent = t.lower.agent, out->lower_depth = t.lower.depth;
+    out->upper_segment = t.upper.segment, out->upper_piece = t.upper.piece, out->upper_agent = t.upper.agent, out->upper_depth = t.upper.depth;
     out->status = 0, out->reserved = 0;
     return RBP_OK;
 }

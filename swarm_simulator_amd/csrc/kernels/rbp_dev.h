@@ -268,6 +268,25 @@ size_t separation_workspace_bytes(int K, int N, int M_stride);
 int launch_separation(const SeparationInputs& in, double* pair_lower, void* workspace, hipStream_t st);
 int separation_run(const char* who, int device, const SeparationInputs& in, rbp_separation* out, double* pair_lower, void* workspace, hipStream_t st);
 
+// kernels/swept.hip: a certified interval for the smallest clearance of K missions to the obstacles in continuous time
+// (rbp_swept_clearance of include/rbp.h) from device arrays in a session's layout and a device array of K worlds whose grids lie on the
+// device.  launch_swept enqueues its kernels on `st` and allocates nothing; agent_lower [K][N] is a device pointer or null; the K structs
+// are then at the front of `workspace` (swept_workspace_bytes(K, N, M_stride) bytes of device memory, nothing to initialise: the structs,
+// and one chunk's work-list counters, work list, item clearances and partial tallies, sized by the shapes alone).  swept_run: the same
+// with `agent_lower` wherever the caller has it -- on `device` (the current one), written in place, or on the host, through one staging
+// buffer -- and the structs copied to `out` on the host; it returns when all has arrived.  swept_check_arguments: depth and refine_below,
+// no device work.  (r.dt and r.downwash are not read.)
+struct SweptInputs {
+    ReportInputs r;
+    const DevWorld* worlds;  // [K] on the device
+    int depth;
+    double refine_below;
+};
+int swept_check_arguments(const char* who, int32_t depth, double refine_below);
+size_t swept_workspace_bytes(int K, int N, int M_stride);
+int launch_swept(const SweptInputs& in, double* agent_lower, void* workspace, hipStream_t st);
+int swept_run(const char* who, int device, const SweptInputs& in, rbp_swept_clearance* out, double* agent_lower, void* workspace, hipStream_t st);
+
 // launchers (defined in the .hip files)
 int launch_corridor(const DevSession& s, hipStream_t st);
 size_t corridor_lds_bytes(const DevSession& s);  // dynamic LDS of sfc_kernel for this session's shapes

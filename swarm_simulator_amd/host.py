@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _abi as A
-from .types import Clearance, Dynamics, Mission, Param, PlanResult, Report, Separation, World
+from .types import Clearance, Dynamics, Mission, Param, PlanResult, Report, Separation, SweptClearance, World
 
 _lib = None
 
@@ -51,6 +51,8 @@ def lib():
                                          C.POINTER(A.rbp_clearance), A.c_double_p]
         L.rbp_separation_host.argtypes = [C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.c_int32, A.c_double_p, A.c_double_p, C.c_int32,
                                           C.c_double, C.POINTER(A.rbp_separation), A.c_double_p]
+        L.rbp_swept_clearance_host.argtypes = [C.POINTER(A.rbp_world), C.POINTER(A.rbp_mission), C.c_int32, A.c_double_p, A.c_double_p, C.c_int32,
+                                               C.c_double, C.POINTER(A.rbp_swept_clearance), A.c_double_p]
         L.rbp_write_coef_csv.argtypes =[C.c_char_p, C.c_int32, C.c_int32, A.c_double_p, A.c_double_p]
         L.rbp_write_qp_lp.argtypes = [C.c_char_p, C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.POINTER(A.rbp_plan), C.c_int32,
                                       A.c_double_p]
@@ -248,6 +250,21 @@ def separation(mission: Mission, param: Param, plan: PlanResult, depth=4, refine
     if rc:
         raise ValueError(f"rbp_separation_host rc={rc}")
     return (Separation.from_c(out), pairs) if per_pair else Separation.from_c(out)
+
+
+def swept_clearance(world: World, mission: Mission, plan: PlanResult, depth=4, refine_below=0.5, per_agent=False):
+    """a certified interval for the plan's smallest clearance to the obstacles of `world` in continuous time as a SweptClearance, by the
+    sequential loop the device shares (csrc/common/swept_rules.h): what planner.Session.swept_clearance / planner.swept_clearance_coefs
+    return for this plan and grid, bit for bit.  per_agent: returns (SweptClearance, [N] array of every agent's smallest lower clearance,
+    1e9 where there is none)."""
+    ws, ms = world.c_struct(), mission.c_struct()
+    out = A.rbp_swept_clearance()
+    agents = np.full(plan.N, 1e9) if per_agent else None
+    rc = lib().rbp_swept_clearance_host(C.byref(ws), C.byref(ms), plan.M, A.ptr(plan.T, A.c_double_p), A.ptr(plan.coef, A.c_double_p), depth,
+                                        refine_below, C.byref(out), A.ptr(agents, A.c_double_p))
+    if rc:
+        raise ValueError(f"rbp_swept_clearance_host rc={rc}")
+    return (SweptClearance.from_c(out), agents) if per_agent else SweptClearance.from_c(out)
 
 
 def write_coef_csv(directory, plan: PlanResult):

@@ -11,7 +11,7 @@ import ctypes as C
 import os
 
 from . import _abi as A
-from .types import Clearance, DeviceWorld, Dynamics, Mission, Param, PlanResult, Report, Separation, World
+from .types import Clearance, DeviceWorld, Dynamics, Mission, Param, PlanResult, Report, Separation, SweptClearance, World
 
 _lib = None
 
@@ -149,6 +149,11 @@ def lib():
                                              C.c_double, C.c_int32, C.c_double, P(A.rbp_separation), C.c_void_p]
             if L.rbp_sizeof(A.RBP_SIZEOF_SEPARATION) != C.sizeof(A.rbp_separation):
                 raise RbpLibraryMissing(f"{path}: sizeof(rbp_separation) is {L.rbp_sizeof(A.RBP_SIZEOF_SEPARATION)} in the library, {C.sizeof(A.rbp_separation)} in this binding")
+            L.rbp_session_swept_clearance.argtypes = [C.c_void_p, C.c_int32, C.c_double, P(A.rbp_swept_clearance), C.c_void_p, C.c_void_p]
+            L.rbp_dev_swept_clearance.argtypes = [C.c_int, C.c_int32, C.c_int32, A.c_int32_p, C.c_int32, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p,
+                                                  P(A.rbp_world), C.c_int32, C.c_double, P(A.rbp_swept_clearance), C.c_void_p]
+            if L.rbp_sizeof(A.RBP_SIZEOF_SWEPT_CLEARANCE) != C.sizeof(A.rbp_swept_clearance):
+                raise RbpLibraryMissing(f"{path}: sizeof(rbp_swept_clearance) is {L.rbp_sizeof(A.RBP_SIZEOF_SWEPT_CLEARANCE)} in the library, {C.sizeof(A.rbp_swept_clearance)} in this binding")
         except AttributeError:
             if not os.environ.get("RBP_HIP_LIB"):
                 raise
@@ -189,6 +194,7 @@ EXPORTED_SYMBOLS = [
     "rbp_session_dynamics", "rbp_dev_dynamics",
     "rbp_session_clearance", "rbp_dev_clearance",
     "rbp_session_separation", "rbp_dev_separation",
+    "rbp_session_swept_clearance", "rbp_dev_swept_clearance",
 ]
 
 
@@ -545,6 +551,34 @@ class Session:
             raise RuntimeError(f"rbp_session_separation rc={rc}: {last_error()}")
         return [Separation.from_c(r) for r in out], pl
 
+    def swept_clearance(self, depth=4, refine_below=0.5, per_agent=False, device_out=False, stream=None):
+        """a certified interval for the missions' smallest clearance to the obstacles in continuous time, computed where the plans and the
+        grids lie (rbp_session_swept_clearance): (records, agents) -- K SweptClearance records, the bits host.swept_clearance gives for the
+        downloaded plans on the downloaded grids; agents [K][N], every agent's smallest lower clearance (1e9 where there is none), or None
+        unless per_agent.  depth: the pieces of a refined item are 2^depth; refine_below: items whose depth-0 lower clearance is below it,
+        or whose depth-0 box leaves the grid or the cell budget, are refined (1e9: all).  device_out: the array is a torch tensor on the
+        session's device, written in place by the kernels; otherwise a numpy array.  The row of a mission that is not computed keeps its
+        1e9.  Nothing of the session changes; a mission whose status is not 0 comes back with that status and nothing computed."""
+        import numpy as np
+        N = self.plans[0].N
+        out = (A.rbp_swept_clearance * self.K)()
+        ag, ap = None, None
+        if per_agent and device_out:
+            import torch
+            dev = torch.device("cuda", self.device)
+            ag = torch.full((self.K, N), 1e9, dtype=torch.float64, device=dev)
+            torch.cuda.synchronize(dev)   # (the fill is written on torch's stream, the kernels run on `stream`)
+            ap = ag.data_ptr()
+        elif per_agent:
+            ag = np.full((self.K, N), 1e9)
+            ap = ag.ctypes.data
+        rc = lib().rbp_session_swept_clearance(self._h, depth, refine_below, out, C.c_void_p(ap), C.c_void_p(stream or 0))
+        if rc == A.RBP_ERR_BAD_ARGUMENT:
+            raise ValueError(f"rbp_session_swept_clearance rc={rc}: {last_error()}")
+        if rc:
+            raise RuntimeError(f"rbp_session_swept_clearance rc={rc}: {last_error()}")
+        return [SweptClearance.from_c(r) for r in out], ag
+
     def reserve_workspace(self, stream=None):
         """reserve the QP workspace now (otherwise the first PLANNER run does)"""
         rc = lib().rbp_session_reserve_workspace(self._h, C.c_void_p(stream or 0))
@@ -696,6 +730,41 @@ def clearance_coefs(M, T, coef, radius, worlds, dt=0.1, time_scale=None, agent_c
     if rc:
         raise RuntimeError(f"rbp_dev_clearance rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
     return [Clearance.from_c(r) for r in out]
+
+
+def swept_clearance_coefs(M, T, coef, radius, worlds, depth=4, refine_below=0.5, time_scale=None, agent_lower=None, device=0):
+    """rbp_dev_swept_clearance: the swept clearance kernels on the caller's arrays, uploaded once, in report_coefs' layout, and K worlds
+    (World: a host grid, uploaded once per distinct grid; DeviceWorld: referenced in place).  agent_lower: None, a C-contiguous float64
+    numpy array [K][N] or a torch tensor of that shape on `device`, written in place.  Returns K SweptClearance records, the bits
+    host.swept_clearance gives for the scaled times."""
+    import numpy as np
+    M = np.ascontiguousarray(M, np.int32).reshape(-1)
+    K = len(M)
+    T, coef, radius = A.as_f64(T).reshape(K, -1), A.as_f64(coef), A.as_f64(radius).reshape(K, -1)
+    S, N = T.shape[1] - 1, radius.shape[1]
+    if coef.size != K * N * 3 * 6 * S:
+        raise ValueError(f"coef holds {coef.size} doubles, K * N * 3 * 6 * M_stride = {K * N * 3 * 6 * S}")
+    if len(worlds) != K:
+        raise ValueError(f"{len(worlds)} worlds for {K} missions")
+    ts = None if time_scale is None else A.as_f64(time_scale).reshape(K)
+    ap = None
+    if isinstance(agent_lower, np.ndarray):
+        if agent_lower.dtype != np.float64 or not agent_lower.flags["C_CONTIGUOUS"] or agent_lower.size != K * N:
+            raise ValueError(f"agent_lower must be a C-contiguous float64 array of {K * N} elements")
+        ap = agent_lower.ctypes.data
+    elif agent_lower is not None:
+        if str(agent_lower.dtype) != "torch.float64" or not agent_lower.is_contiguous() or agent_lower.numel() != K * N:
+            raise ValueError(f"agent_lower must be a contiguous float64 tensor of {K * N} elements")
+        ap = agent_lower.data_ptr()
+    ws = (A.rbp_world * K)(*[w.c_struct() for w in worlds])
+    out = (A.rbp_swept_clearance * K)()
+    rc = lib().rbp_dev_swept_clearance(device, K, N, A.ptr(M, A.c_int32_p), S, A.ptr(T, A.c_double_p), A.ptr(ts, A.c_double_p),
+                                       A.ptr(coef, A.c_double_p), A.ptr(radius, A.c_double_p), ws, depth, refine_below, out, C.c_void_p(ap))
+    if rc == A.RBP_ERR_BAD_ARGUMENT:
+        raise ValueError(f"rbp_dev_swept_clearance rc={rc}: {last_error()}")
+    if rc:
+        raise RuntimeError(f"rbp_dev_swept_clearance rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+    return [SweptClearance.from_c(r) for r in out]
 
 
 def separation_coefs(M, T, coef, radius, downwash, depth=4, refine_below=2.0, time_scale=None, pair_lower=None, device=0):

@@ -20,8 +20,12 @@ or left the grid (csrc/common/clearance_rules.h): whether the plan hits anything
 With --device-separation (only with --device-worlds --mode batched; off by default) ONE planner.Session.separation() on the resident plans
 adds a line per map with a certified interval for the smallest safety ratio in CONTINUOUS time, where both ends lie, and how many (pair,
 segment) items are uncertified, colliding and refined (csrc/common/separation_rules.h): whether the plan is separated between the samples.
+With --device-swept-clearance (only with --device-worlds --mode batched; off by default) ONE planner.Session.swept_clearance() on the resident
+plans and grids adds a line per map with a certified interval for the smallest clearance to the obstacles in CONTINUOUS time, where both
+ends lie, and how many (agent, segment) items are uncertified, hitting, outside, over budget and refined (csrc/common/swept_rules.h):
+whether the plan is clear of the obstacles between the samples.
 
-usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]] [--device-report] [--device-dynamics] [--device-clearance] [--device-separation]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
+usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]] [--device-report] [--device-dynamics] [--device-clearance] [--device-separation] [--device-swept-clearance]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
        [--batch-size 4] [--iteration 1] [--joint] [--csv DIR]
 """
 import argparse
@@ -49,6 +53,9 @@ def main(argv=None):
     ap.add_argument("--device-separation", action="store_true", help="with --device-worlds --mode batched: one more line per map with a certified interval "
                     "for the smallest safety ratio in continuous time, where it lies, uncertified / colliding / refined items, from one separation "
                     "call on the device (planner.Session.separation)")
+    ap.add_argument("--device-swept-clearance", action="store_true", help="with --device-worlds --mode batched: one more line per map with a certified "
+                    "interval for the smallest clearance to the obstacles in continuous time, where it lies, uncertified / hitting / outside / "
+                    "over-budget / refined items, from one swept clearance call on the device (planner.Session.swept_clearance)")
     ap.add_argument("--mission", default="mission_64agents_15.json")
     ap.add_argument("--maps", default="1-50")
     ap.add_argument("--mode", choices=["serial", "batched"], default="serial")
@@ -65,6 +72,8 @@ def main(argv=None):
         ap.error("--device-clearance needs --device-worlds --mode batched")
     if args.device_separation and not (args.device_worlds and args.mode == "batched"):
         ap.error("--device-separation needs --device-worlds --mode batched")
+    if args.device_swept_clearance and not (args.device_worlds and args.mode == "batched"):
+        ap.error("--device-swept-clearance needs --device-worlds --mode batched")
     if args.device_ecbs and not args.device_worlds:
         ap.error("--device-ecbs needs --device-worlds")
     if args.device_handoff and not (args.device_ecbs and args.mode == "batched"):
@@ -157,6 +166,7 @@ def run_and_report(args, sess, maps, plans, mission, param):
     peaks = sess.dynamics()[0] if args.device_dynamics else [None] * sess.K
     clear = sess.clearance()[0] if args.device_clearance else [None] * sess.K
     separ = sess.separation()[0] if args.device_separation else [None] * sess.K
+    swept = sess.swept_clearance()[0] if args.device_swept_clearance else [None] * sess.K
     dt = time.perf_counter() - t0
     print(f"BoxGenerator + SwarmPlanner runtime, {sess.K} maps in one session: {dt:.6f} "
           f"({sess.K * mission.qn / dt:.1f} agent-trajectories/s incl. {'download' if download else 'report'})")
@@ -165,7 +175,7 @@ def run_and_report(args, sess, maps, plans, mission, param):
         status = [r.status for r in records]
         plans = [SimpleNamespace(total_cost=float(c), time_scale=float(ts) if ts > 0 else 1.0, T=[r.end_time]) for (ts, c), r in zip(sc, records)]
     sess.close()
-    for i, p, st, rec, pk, cl, sp in zip(maps, plans, status, records, peaks, clear, separ):
+    for i, p, st, rec, pk, cl, sp, sw in zip(maps, plans, status, records, peaks, clear, separ, swept):
         if st:
             print(f"[ERROR] map{i}: status {st}")
             return -1
@@ -179,7 +189,19 @@ def run_and_report(args, sess, maps, plans, mission, param):
             clearance_line(i, cl)
         if sp is not None:
             separation_line(i, sp)
+        if sw is not None:
+            swept_clearance_line(i, sw)
     return 0
+
+
+def swept_clearance_line(i, s):
+    """--device-swept-clearance: both ends of a types.SweptClearance's interval and where they lie (agent, segment, piece of depth), and the
+    item counts; `none` for an end that no piece gave"""
+    def where(clearance, agent, segment, piece, depth):
+        return f"{clearance:.5f} (agent {agent} segment {segment} piece {piece}/{1 << depth})" if segment >= 0 else "none"
+    print(f"map{i}: continuous clearance in [{where(s.lower_clearance, s.lower_agent, s.lower_segment, s.lower_piece, s.lower_depth)}, "
+          f"{where(s.upper_clearance, s.upper_agent, s.upper_segment, s.upper_piece, s.upper_depth)}]  "
+          f"uncertified {s.uncertified}  hitting {s.hitting}  outside {s.outside}  over budget {s.over_budget}  refined {s.refined}")
 
 
 def separation_line(i, s):

@@ -297,6 +297,48 @@ class Separation:
         return tuple(int(x) for x in f) + tuple(getattr(self, n) for n in self.FIELDS[3:])
 
 
+@dataclass
+class SweptClearance:
+    """rbp_swept_clearance (include/rbp.h): a certified interval for a mission's smallest clearance to the obstacles in continuous time --
+    every reading of the grid under an agent less its radius, at every instant, is >= lower_clearance; upper_clearance is a reading at a
+    point the rule computed on the curve (a witness) -- with the readings there (-1: outside or over budget), the (segment, piece, agent)
+    and the depth of the piece each came from (-1: none, clearance 1e9), the items (agent, segment) whose lower reading is a hit
+    (uncertified), whose upper reading is a hit (hitting), that have a piece outside the grid or over the cell budget and that were
+    refined, and the end time.  status != 0: nothing computed."""
+    lower_clearance: float
+    upper_clearance: float
+    lower_dist: float
+    upper_dist: float
+    end_time: float
+    uncertified: int
+    hitting: int
+    outside: int
+    over_budget: int
+    refined: int
+    lower_segment: int
+    lower_piece: int
+    lower_agent: int
+    lower_depth: int
+    upper_segment: int
+    upper_piece: int
+    upper_agent: int
+    upper_depth: int
+    status: int = 0
+
+    FIELDS = ("lower_clearance", "upper_clearance", "lower_dist", "upper_dist", "end_time", "uncertified", "hitting", "outside", "over_budget",
+              "refined", "lower_segment", "lower_piece", "lower_agent", "lower_depth", "upper_segment", "upper_piece", "upper_agent",
+              "upper_depth", "status")
+
+    @classmethod
+    def from_c(cls, r):
+        return cls(*[getattr(r, n) for n in cls.FIELDS])
+
+    def bits(self):
+        """the record with its doubles as bit patterns: what two evaluations of the one rule must agree on"""
+        f = np.array([getattr(self, n) for n in self.FIELDS[:5]], np.float64).view(np.uint64)
+        return tuple(int(x) for x in f) + tuple(getattr(self, n) for n in self.FIELDS[5:])
+
+
 class PlanResult:
     """sp_const.hpp:21-28 as flat arrays (include/rbp.h rbp_plan)."""
 
