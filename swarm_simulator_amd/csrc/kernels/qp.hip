@@ -39,6 +39,7 @@
 
 #include "knot_lds.inc"  // (below the pragma: its multiply-adds must contract)
 #include "common/ipm_rows.h"  // the arithmetic of a row, shared with jqp.hip
+#include "common/reduce_order.h"  // the order of operations of a workgroup-wide reduction, shared with its host restatement
 
 #ifndef QP_THREADS
 #define QP_THREADS 512

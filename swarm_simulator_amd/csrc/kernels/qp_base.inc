@@ -69,7 +69,9 @@ struct QpWs {
                                     // that the passes that read three or six of the twelve (rbase, rhs, assembly) fetch only those
     double *pwgt;                   // [npb*oq] Newton weight of every in-batch pair row (off-diagonal blocks of the knot matrices)
     double *dx, *dxa, *cvec;        // [nb*3*oq]
-    double *rbase, *rhs;            // [(M-1)*nk]
+    double *rbase, *rhs;            // [(M-1)*nk]  (blocks of order 36: rhs is LIVE from rbase_from_acc, which leaves the predictor's right-hand side
+                                    // there, until the factorisation chains have consumed it; a refused polish, which uses it for its primal
+                                    // steps in that window, is followed by rhs_from_acc -- any other use of it there needs the same)
     double *Td, *To;                // [(M-1)][nk*nk], [(M-2)][nk*nk]
     double *Lf;                     // wave path: [(M-1)] slots of M_j = L_j^-T (its triangle) and 1 / d_j, laid out by knot_factor_layout.h; on a
                                     // 128-byte boundary inside a region of 2 (M-1) nk^2 doubles (nk <= 36), of which it uses a fraction
@@ -163,10 +165,11 @@ __device__ __forceinline__ double rl(double v, int lane) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
 }
 __device__ __forceinline__ double wave_red(double v, int op /*0 sum,1 max,2 min*/) {
-    v = red_op(v, dpp_f64<0xB1>(v), op);   // quad_perm [1,0,3,2]
-    v = red_op(v, dpp_f64<0x4E>(v), op);   // quad_perm [2,3,0,1]
-    v = red_op(v, dpp_f64<0x141>(v), op);  // row_half_mirror
-    v = red_op(v, dpp_f64<0x140>(v), op);  // row_mirror: every lane of a row holds the row's result
+    using namespace red_order;  // (common/reduce_order.h: the order of operations, shared with its host restatement)
+    v = red_op(v, dpp_f64<DPP_CTRL[0]>(v), op);  // quad_perm [1,0,3,2]
+    v = red_op(v, dpp_f64<DPP_CTRL[1]>(v), op);  // quad_perm [2,3,0,1]
+    v = red_op(v, dpp_f64<DPP_CTRL[2]>(v), op);  // row_half_mirror
+    v = red_op(v, dpp_f64<DPP_CTRL[3]>(v), op);  // row_mirror: every lane of a row holds the row's result
     return red_op(red_op(rl(v, 0), rl(v, 16), op), red_op(rl(v, 32), rl(v, 48), op), op);
 }
 // Block-wide: the wave reduction, then across the waves through `red`.  Two barriers: the one in front of the write would only protect
@@ -180,6 +183,42 @@ __device__ inline double block_reduce(double v, int op /*0 sum,1 max,2 min*/, do
     for (int i = 1; i < QP_THREADS / 64; ++i) r = red_op(r, red[i], op);
     __syncthreads();
     return r;
+}
+// K reductions that happen together: every value keeps its own operation and its own order of operations -- the wave steps of wave_red and
+// the left-to-right walk over the wavefronts' results, so each result is block_reduce's bit for bit --, but the K DPP chains are
+// interleaved step by step (independent instructions fill each other's latency) and ONE pair of barriers serves a chunk of values
+// (common/reduce_order.h: four values on the 256-thread build, two on the 512-thread build; a K above that takes a pair of barriers more).
+template <int K>
+__device__ __forceinline__ void block_reduce_n(double (&v)[K], const int (&op)[K], double* red) {
+    using namespace red_order;
+    constexpr int NW = QP_THREADS / 64, CH = chunk(NW);
+    static_assert(CH >= 1, "a value's partial results fit the reduction scratch");
+#pragma unroll
+    for (int q = 0; q < K; ++q) v[q] = red_op(v[q], dpp_f64<DPP_CTRL[0]>(v[q]), op[q]);
+#pragma unroll
+    for (int q = 0; q < K; ++q) v[q] = red_op(v[q], dpp_f64<DPP_CTRL[1]>(v[q]), op[q]);
+#pragma unroll
+    for (int q = 0; q < K; ++q) v[q] = red_op(v[q], dpp_f64<DPP_CTRL[2]>(v[q]), op[q]);
+#pragma unroll
+    for (int q = 0; q < K; ++q) v[q] = red_op(v[q], dpp_f64<DPP_CTRL[3]>(v[q]), op[q]);
+#pragma unroll
+    for (int q = 0; q < K; ++q) v[q] = red_op(red_op(rl(v[q], 0), rl(v[q], 16), op[q]), red_op(rl(v[q], 32), rl(v[q], 48), op[q]), op[q]);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int q0 = 0; q0 < K; q0 += CH) {
+        if (lane == 0) {
+#pragma unroll
+            for (int q = q0; q < K && q < q0 + CH; ++q) red[slot(q - q0, wave, NW)] = v[q];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = q0; q < K && q < q0 + CH; ++q) {
+            double r = red[slot(q - q0, 0, NW)];
+            for (int i = 1; i < NW; ++i) r = red_op(r, red[slot(q - q0, i, NW)], op[q]);
+            v[q] = r;
+        }
+        __syncthreads();
+    }
 }
 
 // ---- wave-uniform arguments ------------------------------------------------------------------------------------

@@ -98,6 +98,11 @@ __device__ __forceinline__ bool qp_setup_batch(const DevSession& S, RowCtx& c, d
     // its slack is positive for EVERY x_a in the box; such rows cannot be active and are dropped (exact: the feasible
     // set is unchanged).  Per (agent, segment) the surviving neighbours are listed; ~72 % of the rows go away on the
     // 64-agent missions.
+    // (the work area is free here: the box stage's last reader is behind the barriers above; wide batches of the tiled path: global memory)
+    const bool cnt_lds = (3 * nb * M + 1) / 2 <= c.lds_avail;
+    int* fc_l = cnt_lds ? (int*)lds : w.fcnt;            // [nb][M]  fcnt
+    int* fn_l = cnt_lds ? (int*)lds + nb * M : w.fnear;  // [nb][M]  fnear
+    int* fp_l = cnt_lds ? (int*)lds + 2 * nb * M : w.fperm;  // [nb * M]  fperm
     for (int it = tid; it < nb * M; it += QP_THREADS) {
         const int a = it / M, seg = it % M, qa = first + a;
         const double ra = c.radius[qa];
@@ -161,51 +166,47 @@ __device__ __forceinline__ bool qp_setup_batch(const DevSession& S, RowCtx& c, d
         }
         w.fnear[it] = cnt;
         w.fcnt[it] = cnt + nfar_g;
+        if (cnt_lds) fc_l[it] = cnt + nfar_g, fn_l[it] = cnt;
     }
+    // The groups' counts go on through LDS (fc_l, fn_l: written above next to the global arrays; fp_l: the rank sort's permutation): the two
+    // prefix sums and the rank sort below read every group's count -- 144 loads per thread, which from global memory were trips --, and with
+    // the counts there the first prefix sum and the rank sort have no global dependency between them: one phase, two barriers fewer.
+    if (tid == 0) flag[0] = 0, flag[1] = 0;
     __threadfence_block();
     __syncthreads();
     // offsets of the groups' normal lists (exclusive prefix sum of the counts) and the number of non-constant frozen rows: every group
-    // sums its predecessors itself -- loads only, all in flight together; one thread walking the 144 groups with a store per step made
-    // 144 trips to memory in a row
-    if (tid == 0) flag[0] = 0, flag[1] = 0;
-    __syncthreads();
+    // sums its predecessors itself.  Sweep work order: the threads of a wavefront walk the row lists of their control points in lockstep, so
+    // a wave costs as much as its longest list.  Handing out the (agent, segment) groups by falling row count puts lists of
+    // similar length into the same wave (and the long ones into the first round).  Rank sort, one thread per group.
     for (int it = tid; it < nb * M; it += QP_THREADS) {
-        int acc = 0;
-        for (int o = 0; o < it; ++o) acc += w.fcnt[o];
+        const int ci = fc_l[it], cn = fn_l[it];
+        int acc = 0, rank = 0;
+        for (int o = 0; o < nb * M; ++o) {
+            const int co = fc_l[o];
+            acc += o < it ? co : 0;
+            rank += (co > ci || (co == ci && o < it)) ? 1 : 0;
+        }
         w.fbase[it] = acc;
         const int seg = it % M;
-        atomicAdd(flag, w.fnear[it] * ((seg == 0 || seg == M - 1) ? (M == 1 ? 0 : 3) : 6));  // (rows of the interior-point phase: the near ones)
-        atomicAdd(flag + 1, w.fcnt[it] - w.fnear[it]);
+        atomicAdd(flag, cn * ((seg == 0 || seg == M - 1) ? (M == 1 ? 0 : 3) : 6));  // (rows of the interior-point phase: the near ones)
+        atomicAdd(flag + 1, ci - cn);
+        w.fperm[rank] = it;
+        if (cnt_lds) fp_l[rank] = it;
+        w.frank[it] = rank;
     }
     __threadfence_block();
     __syncthreads();
     frozen_free_rows = *flag;
     nfar = flag[1];
-    __syncthreads();
-    // sweep work order: the threads of a wavefront walk the row lists of their control points in lockstep, so a wave
-    // costs as much as its longest list.  Handing out the (agent, segment) groups by falling row count puts lists of
-    // similar length into the same wave (and the long ones into the first round).  Rank sort, one thread per group.
-    for (int it = tid; it < nb * M; it += QP_THREADS) {
-        const int ci = w.fcnt[it];
-        int rank = 0;
-        for (int o = 0; o < nb * M; ++o) {
-            const int co = w.fcnt[o];
-            rank += (co > ci || (co == ci && o < it)) ? 1 : 0;
-        }
-        w.fperm[rank] = it;
-        w.frank[it] = rank;
-    }
-    __threadfence_block();
-    __syncthreads();
     // row storage (see the note above QpWs): tile t holds the control points wi = 64 t .. 64 t + 63; its columns are as long as
     // its first (= longest) one
-    for (int t = tid; t <= d.ntile; t += QP_THREADS) {  // (every tile sums its predecessors: see fbase above)
+    for (int t = tid; t <= d.ntile; t += QP_THREADS) {  // (every tile sums its predecessors)
         int base = 0;
-        for (int o = 0; o < t; ++o) base += 64 * (d.ncol0 + w.fcnt[w.fperm[(64 * o) / 6]]);
+        for (int o = 0; o < t; ++o) base += 64 * (d.ncol0 + fc_l[fp_l[(64 * o) / 6]]);
         w.tile_base[t] = base;
     }
     for (int wi = tid; wi < nb * d.oq; wi += QP_THREADS) {
-        const int grp = w.fperm[wi / 6], a = grp / M, seg = grp - a * M;
+        const int grp = fp_l[wi / 6], a = grp / M, seg = grp - a * M;
         w.wi_of[a * d.oq + 6 * seg + wi % 6] = wi;
     }
     __threadfence_block();
@@ -379,13 +380,22 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
             SWEEP(PASS_BUILD);
         }
         PROF(1);
-        const double gap = iter == 0 ? block_reduce(io.sum0, 0, red) : gap_next;
-        const double pres = iter == 0 ? block_reduce(io.vmax, 1, red) : pres_next;
+        if (iter == 0) {
+            double rv[2] = {io.sum0, io.vmax};
+            block_reduce_n<2>(rv, {0, 1}, red);
+            gap_next = rv[0], pres_next = rv[1];
+        }
+        const double gap = gap_next, pres = pres_next;
         __threadfence_block();
         __syncthreads();
         double dmax, gmax;
-        rbase_from_acc(c, dmax, gmax);  // rbase = -F'(2Qx + G'z)
-        const double dres = block_reduce(dmax, 1, red) / (1.0 + block_reduce(gmax, 1, red));
+        // rbase = -F'(2Qx + G'z); on the QP_FWD36 path also the predictor's rhs = rbase + F'G'v, which the chains consume block by block while
+        // they factorise (an iteration that ends below in a termination test or an accepted polish leaves it unused)
+        constexpr bool rhs_early = QP_FWD36;
+        rbase_from_acc(c, dmax, gmax, rhs_early && d.nk == 36);
+        double dg[2] = {dmax, gmax};
+        block_reduce_n<2>(dg, {1, 1}, red);
+        const double dres = dg[0] / (1.0 + dg[1]);
         const double mu = gap / nrows_free;
         rows_swept += nrows_free;
         kkt_ipm = fmax(pres, fmax(dres, mu));
@@ -432,6 +442,8 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
                 ok = true, polished = 1;
                 break;
             }
+            // (a refused attempt has used QpWs::rhs for its primal steps: the predictor's right-hand side once more, from rbase and the accumulators)
+            if (rhs_early && d.nk == 36) rhs_from_acc(c, false, 0.0);
         }
         // ---- Newton matrix and factorisation
         // wave path, 512 threads: assembled behind the factorisation chains by waves 4.. (twisted_factor); the 256-thread build has no
@@ -442,9 +454,7 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
             assemble_blocks_lds(asm_args(c), d.nj, lds);  // (256-thread build, round 6: the chains' companion waves assemble just in time instead)
         // QP_FWD_IN_FACTOR: the predictor's right-hand side is known now -- rbase + F'G'v of the build sweep's accumulators, the arithmetic the
         // rhs_mode 1 prologue of solve_staged repeats -- and the chains consume it block by block while they factorise
-#if QP_FWD36
-        if (d.nk == 36) rhs_from_acc(c, false, 0.0);
-#endif
+        // (rbase_from_acc has left it already)
         PROF(3);
         __threadfence_block();
         __syncthreads();
@@ -491,8 +501,10 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
         PROF(5);
         SWEEP(PASS_AFF);
         PROF(7);
-        const double a_aff = 1.0 / block_reduce(io.vmax, 1, red);
-        const double q0 = block_reduce(io.sum0, 0, red), q1 = block_reduce(io.sum1, 0, red), q2 = block_reduce(io.sum2, 0, red);
+        double av[4] = {io.vmax, io.sum0, io.sum1, io.sum2};
+        block_reduce_n<4>(av, {1, 0, 0, 0}, red);
+        const double a_aff = 1.0 / av[0];
+        const double q0 = av[1], q1 = av[2], q2 = av[3];
         const double mu_aff = (q0 + a_aff * q1 + a_aff * a_aff * q2) / nrows_free;
         TRC(9, a_aff); TRC(10, mu_aff);
         double sigma = mu_aff / mu;
@@ -538,18 +550,20 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
         double applied = 0;
         for (int bt = 0; bt < 40; ++bt) {
             const double delta = alpha - applied;
-            {  // (the batch agents' control points are contiguous: [first .. first + nb) x 3 x oq; four entries per thread and round, loads first)
+            {  // (the batch agents' control points are contiguous: [first .. first + nb) x 3 x oq; XU entries per thread and round, loads first:
+               // 3072 entries per round, so the 2592 of a batch of four at M = 36 are ONE trip to memory where rounds of four were three)
                 double* xb = ctrl + (size_t)first * 3 * d.oq;
                 const int nx = d.nb * 3 * d.oq;
-                for (int i0 = tid; i0 < nx; i0 += 4 * QP_THREADS) {
-                    double xv[4], dv4[4];
+                constexpr int XU = 3072 / QP_THREADS;
+                for (int i0 = tid; i0 < nx; i0 += XU * QP_THREADS) {
+                    double xv[XU], dv4[XU];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
+                    for (int q = 0; q < XU; ++q) {
                         const int i = i0 + q * QP_THREADS;
                         xv[q] = i < nx ? xb[i] : 0.0, dv4[q] = i < nx ? w.dx[i] : 0.0;
                     }
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
+                    for (int q = 0; q < XU; ++q) {
                         const int i = i0 + q * QP_THREADS;
                         if (i < nx) xb[i] = xv[q] + delta * dv4[q];
                     }
@@ -560,9 +574,10 @@ __device__ __forceinline__ int qp_batch_body(const DevSession& S, double* ws_bas
             io.alpha = alpha, io.sum0 = 0, io.vmax = 0, io.vmin = 1e300;
             SWEEP(PASS_UPBUILD);
             applied = alpha;
-            gap_next = block_reduce(io.sum0, 0, red);
-            pres_next = block_reduce(io.vmax, 1, red);
-            const double pmin = block_reduce(io.vmin, 2, red);
+            double uv[3] = {io.sum0, io.vmax, io.vmin};
+            block_reduce_n<3>(uv, {0, 1, 2}, red);
+            gap_next = uv[0], pres_next = uv[1];
+            const double pmin = uv[2];
             rows_swept += nrows_free;
             __threadfence_block();
             __syncthreads();

@@ -44,35 +44,68 @@ __device__ void apply_F(const QpDims& d, const QpWs& w, const double* du, double
 
 // rbase = -F'(2Qx + G'z) in one pass (grad_ctrl + apply_FT fused, as in rhs_from_acc below); also returns this thread's
 // share of max|rbase| and max|2Qx + G'z| for the dual-residual test
-__device__ void rbase_from_acc(const RowCtx& c, double& dmax, double& gmax) {
+// with_rhs (uniform): the predictor's right-hand side in the same pass -- rhs = rbase + F'(G'v), rhs_from_acc(c, false, 0)'s expression on the
+// value this thread has just stored, where that function walks the same items with the same thread map and reads the store back.  Both
+// inputs exist once the build sweep is done.  The corrector still reads rbase.
+// 256-thread build: two items per thread and round, the operands of both requested before the first is worked on: a batch of four has
+// 35 * 12 = 420 items for 256 threads, and the second round's loads cannot move above the first round's stores -- one trip to memory
+// per iteration instead of two.  Same items per thread, same order, same arithmetic per item.
+struct RbaseItem {
+    double x[12], gz[6], yv[6], sc[2], L[9];  // control points of the two segments at the knot, G'z and G'v at its six points, segsc, L_j
+};
+__device__ void rbase_from_acc(const RowCtx& c, double& dmax, double& gmax, bool with_rhs) {
     const QpDims& d = c.d;
     const QpWs& w = c.w;
-    const int oq = d.oq, nu = 3 * d.nb;
+    const int oq = d.oq, nu = 3 * d.nb, nit = d.nj * nu;
     dmax = gmax = 0;
-    for (int it = threadIdx.x; it < d.nj * nu; it += QP_THREADS) {
+    auto load = [&](int it, RbaseItem& t) {
         const int j = it / nu + 1, u = it % nu, a = u / 3, k = u % 3;
-        const double* xb = c.ctrl + ((size_t)(d.first + a) * 3 + k) * oq;
+        const double* xs = c.ctrl + ((size_t)(d.first + a) * 3 + k) * oq + 6 * (j - 1);  // segments j - 1 and j
+#pragma unroll
+        for (int q = 0; q < 12; ++q) t.x[q] = xs[q];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const int j6 = 6 * (j - 1) + 3 + q;
+            t.gz[q] = w.cpacc[(size_t)(9 + k) * (d.nb * oq) + (size_t)a * oq + j6];  // G'z of ALL rows of this control point (bounds, pairs, frozen)
+            t.yv[q] = with_rhs ? w.cpacc[(size_t)(6 + k) * (d.nb * oq) + (size_t)a * oq + j6] : 0.0;  // G'v at the same six control points
+        }
+        t.sc[0] = w.segsc[j - 1], t.sc[1] = w.segsc[j];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) t.L[e] = w.Lk[9 * j + e];
+    };
+    auto work = [&](int it, const RbaseItem& t) {
+        const int j = it / nu + 1, u = it % nu;
         double g[6];
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
-            const int j6 = 6 * (j - 1) + 3 + q, m = j6 / 6, i = j6 % 6;
-            const double* xs = xb + 6 * m;
+            const int i = (3 + q) % 6, ms = (3 + q) / 6;  // control point 6 (j - 1) + 3 + q: point i of segment j - 1 + ms
             double gv = 0;
 #pragma unroll
-            for (int jj = 0; jj < 6; ++jj) gv += Qbase[6 * i + jj] * xs[jj];
-            gv *= 2 * w.segsc[m];
-            gv += w.cpacc[(size_t)(9 + k) * (d.nb * oq) + (size_t)a * oq + j6];  // G'z of ALL rows of this control point (bounds, pairs, frozen)
+            for (int jj = 0; jj < 6; ++jj) gv += Qbase[6 * i + jj] * t.x[6 * ms + jj];
+            gv *= 2 * t.sc[ms];
+            gv += t.gz[q];
             g[q] = -gv;
             gmax = fmax(gmax, fabs(gv));
         }
-        const double* L = w.Lk + 9 * j;
+        const double* L = t.L;
         const size_t o0 = (size_t)(j - 1) * d.nk + u * 3;
 #pragma unroll
         for (int e = 0; e < 3; ++e) {
             const double r = g[3 + e] + L[0 + e] * g[0] + L[3 + e] * g[1] + L[6 + e] * g[2];
             w.rbase[o0 + e] = r;
             dmax = fmax(dmax, fabs(r));
+            if (with_rhs) w.rhs[o0 + e] = r + t.yv[3 + e] + L[0 + e] * t.yv[0] + L[3 + e] * t.yv[1] + L[6 + e] * t.yv[2];
         }
+    };
+    // (the 512-thread build has a thread per item of a batch of four up to M = 43: it keeps one item per round)
+    constexpr int NI = QP_THREADS >= 512 ? 1 : 2;
+    for (int it = threadIdx.x; it < nit; it += NI * QP_THREADS) {
+        RbaseItem t[NI];
+#pragma unroll
+        for (int q = 0; q < NI; ++q) load(it + q * QP_THREADS < nit ? it + q * QP_THREADS : it, t[q]);  // (past the end: the first item again, not worked on)
+#pragma unroll
+        for (int q = 0; q < NI; ++q)
+            if (it + q * QP_THREADS < nit) work(it + q * QP_THREADS, t[q]);
     }
 }
 // rhs = rbase + F'(G'v) in one pass: gtv_ctrl + apply_FT + the add fused (every control-space entry of G'v is used by
