@@ -347,7 +347,7 @@ void rbp_release_thread_context(void);
                               6: rbp_param.timescale_rule, rbp_plan.time_scale_alt */
 enum { RBP_SIZEOF_WORLD = 0, RBP_SIZEOF_MISSION = 1, RBP_SIZEOF_PARAM = 2, RBP_SIZEOF_PLAN = 3, RBP_SIZEOF_COUNTERS = 4, RBP_SIZEOF_DEVICE_ARRAYS = 5,
        RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7, RBP_SIZEOF_REPORT = 8, RBP_SIZEOF_DYNAMICS = 9, RBP_SIZEOF_CLEARANCE = 10, RBP_SIZEOF_SEPARATION = 11,
-       RBP_SIZEOF_SWEPT_CLEARANCE = 12 };
+       RBP_SIZEOF_SWEPT_CLEARANCE = 12, RBP_SIZEOF_LIMITS = 13 };
 int rbp_abi_version(void);
 size_t rbp_sizeof(int which);
 const char* rbp_version(void);
@@ -662,6 +662,59 @@ int rbp_dev_swept_clearance(int device, int32_t K, int32_t N, const int32_t* M, 
                             const double* time_scale, const double* coef, const double* radius,
                             const rbp_world* worlds /* [K]; dist host or device */, int32_t depth, double refine_below,
                             rbp_swept_clearance* out, double* agent_lower);
+
+/* ---- certified intervals for the largest velocity and acceleration of resident plans in CONTINUOUS time ----
+ * rbp_dynamics looks at the samples t = j * dt; a peak between two samples is not seen, and timeScale pushes every plan up against its
+ * limits (the literal rule RBP_TIMESCALE_FIRST_EIGENVALUES can leave a segment above max_vel).  For an agent a and a segment m (an ITEM)
+ * the velocity of an axis is a polynomial of degree 4 and the acceleration one of degree 3; on a PIECE of the segment (piece p of depth D
+ * covers [p / 2^D, (p+1) / 2^D] of it) the polynomial lies in the hull of its Bernstein control points and passes through the first and
+ * the last one.  So, per axis and derivative, (max_i |b_i| + err) / limit is an upper bound of |X_k(t)| / limit on the piece and
+ * max(0, max(|b_0|, |b_n|) - err) / limit a value the curve reaches, err = (16 + 4 D) 2^-53 V a counted rounding term.  All of it -- the
+ * derivative's coefficients (the products rbp_dynamics forms), the Bernstein form, the halving, err with its derivation, the order of the
+ * peaks -- is the rule of csrc/common/limits_rules.h, which the kernels (kernels/limits.hip) and rbp_limits_host of rbp_host.h share: both
+ * return the same bits.  The promise, for the polynomials the double coefficients define and positive limits:
+ *     lower_X_ratio <= sup over agents, axes and instants of |X_k(t)| / max_X[a][k] <= upper_X_ratio,   X = vel, acc.
+ * upper <= 1 certifies the limit; lower > 1 proves a violation.  uncertified: the items with a piece whose upper ratio, vel or acc, is not
+ * <= 1 (a NaN and an infinity count: uncertified == 0 certifies the mission); violating: those with a piece whose lower ratio is > 1.
+ * Refinement is fixed: every item is evaluated at depth 0; an item with a depth-0 upper ratio that is not <= refine_above (a NaN goes
+ * too) is evaluated again on all 2^depth pieces of depth `depth`, which replace its depth-0 bounds.  depth in 0 .. RBP_LIMITS_MAX_DEPTH;
+ * refine_above any number (negative: everything is refined; 1e9: only what is no number below it).  The peaks name the largest ratio
+ * and among equal ratios the lexicographically first (segment, piece, agent, axis); a ratio of 0, a negative one or a NaN is never a
+ * peak (ratio 0, indices -1: none).  A limit that is not a positive number bounds nothing: its items are uncertified.
+ * agent_upper [K][N][2] (NULL: not wanted): an agent's largest upper velocity ratio and largest upper acceleration ratio over its
+ * segments and axes, 0 where none, +infinity where one is no number; the row of a mission with a status is left untouched.  It may be
+ * a host pointer or a device pointer on the plans' device (classified as rbp_world.dist is; another device: RBP_ERR_BAD_ARGUMENT): a
+ * device destination is written in place by the kernels, a host destination goes through one staging buffer and one copy.
+ * Memory: items that are refined go through a work list of one uint32 per item, sized for the worst case (every item), of at most
+ * RBP_LIMITS_LIST_BYTES; missions are processed in chunks where all of them would need more (a single mission always is one chunk, and
+ * one of more than 2^32 - 64 items is refused).  No allocation depends on the data.
+ * rbp_session_limits: of a session's K missions, from its own coef, T, time scale, max_vel, max_acc and status, all of which stay in
+ *   HBM; waits for an asynchronous solve like every call, enqueues its kernels on `stream`, copies K structs back in one copy and returns
+ *   when they have arrived.  Nothing of the session changes.  A mission whose status is not 0 gets that status and nothing computed.
+ *   RBP_ERR_BAD_ARGUMENT: a session whose last run did not include the PLANNER stage; and, before a device is looked for, a null
+ *   pointer, a depth outside 0 .. RBP_LIMITS_MAX_DEPTH, a refine_above that is no number.  The session's limits are not refused.
+ * rbp_dev_limits: the same kernels on a caller's host arrays in rbp_dev_dynamics' layout, uploaded once.  Argument errors (those above,
+ *   K, N <= 0, an M[k] outside 1..M_stride, a time scale <= 0, a limit that is not a positive number) are RBP_ERR_BAD_ARGUMENT before a
+ *   device is looked for. */
+#define RBP_LIMITS_MAX_DEPTH 8
+#define RBP_LIMITS_LIST_BYTES (64u << 20)    /* the work list's budget: 16 Mi items of a chunk of missions */
+typedef struct rbp_limits {
+    double  lower_vel_ratio, upper_vel_ratio;   /* 0: none */
+    double  lower_acc_ratio, upper_acc_ratio;
+    double  end_time;                           /* Ts[M]: the mission's last segment time, scaled */
+    int64_t uncertified, violating, refined;    /* items (agent, segment) */
+    int32_t lower_vel_segment, lower_vel_piece, lower_vel_agent, lower_vel_axis, lower_vel_depth;   /* -1: none */
+    int32_t upper_vel_segment, upper_vel_piece, upper_vel_agent, upper_vel_axis, upper_vel_depth;
+    int32_t lower_acc_segment, lower_acc_piece, lower_acc_agent, lower_acc_axis, lower_acc_depth;
+    int32_t upper_acc_segment, upper_acc_piece, upper_acc_agent, upper_acc_axis, upper_acc_depth;
+    int32_t status, reserved;                   /* the mission's status; != 0: nothing computed, zeros, indices -1 */
+} rbp_limits;
+int rbp_session_limits(rbp_session* s, int32_t depth, double refine_above, rbp_limits* out /* [K] */,
+                       double* agent_upper /* [K][N][2] or NULL; host or device pointer */, void* stream);
+int rbp_dev_limits(int device, int32_t K, int32_t N, const int32_t* M, int32_t M_stride, const double* T,
+                   const double* time_scale, const double* coef, const double* max_vel /* [K][N][3] */,
+                   const double* max_acc /* [K][N][3] */, int32_t depth, double refine_above, rbp_limits* out,
+                   double* agent_upper);
 
 const char* rbp_last_error(void);
 int rbp_device_count(void);

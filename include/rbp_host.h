@@ -119,6 +119,13 @@ int rbp_separation_host(const rbp_mission* mission, const rbp_param* param, int3
 int rbp_swept_clearance_host(const rbp_world* world, const rbp_mission* mission, int32_t M, const double* T, const double* coef,
                              int32_t depth, double refine_below, rbp_swept_clearance* out, double* agent_lower /* [N] or NULL */);
 
+/* The certified intervals of one plan's largest velocity and acceleration, as fractions of the mission's max_vel / max_acc, in continuous
+ * time as an rbp_limits (rbp.h), by the sequential loop of csrc/common/limits_rules.h that the device shares: what rbp_session_limits /
+ * rbp_dev_limits return for the same plan, bit for bit, and their reference.  T as downloaded (scaled).  depth in
+ * 0 .. RBP_LIMITS_MAX_DEPTH and refine_above a number, otherwise RBP_ERR_BAD_ARGUMENT.  agent_upper [N][2] may be NULL.  out->status is 0. */
+int rbp_limits_host(const rbp_mission* mission, int32_t M, const double* T, const double* coef, int32_t depth, double refine_above,
+                    rbp_limits* out, double* agent_upper /* [N][2] or NULL */);
+
 /* crazyswarm CSV of rbp_planner.hpp:295-324 (one file per agent: <dir>/coef<qi+1>.csv) */
 int rbp_write_coef_csv(const char* dir, int32_t N, int32_t M, const double* T, const double* coef);
 

@@ -151,6 +151,21 @@ class rbp_swept_clearance(C.Structure):
                 ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+RBP_SIZEOF_LIMITS = 13
+RBP_LIMITS_MAX_DEPTH = 8
+
+
+class rbp_limits(C.Structure):
+    _fields_ = [("lower_vel_ratio", C.c_double), ("upper_vel_ratio", C.c_double), ("lower_acc_ratio", C.c_double), ("upper_acc_ratio", C.c_double),
+                ("end_time", C.c_double),
+                ("uncertified", C.c_int64), ("violating", C.c_int64), ("refined", C.c_int64),
+                ("lower_vel_segment", C.c_int32), ("lower_vel_piece", C.c_int32), ("lower_vel_agent", C.c_int32), ("lower_vel_axis", C.c_int32), ("lower_vel_depth", C.c_int32),
+                ("upper_vel_segment", C.c_int32), ("upper_vel_piece", C.c_int32), ("upper_vel_agent", C.c_int32), ("upper_vel_axis", C.c_int32), ("upper_vel_depth", C.c_int32),
+                ("lower_acc_segment", C.c_int32), ("lower_acc_piece", C.c_int32), ("lower_acc_agent", C.c_int32), ("lower_acc_axis", C.c_int32), ("lower_acc_depth", C.c_int32),
+                ("upper_acc_segment", C.c_int32), ("upper_acc_piece", C.c_int32), ("upper_acc_agent", C.c_int32), ("upper_acc_axis", C.c_int32), ("upper_acc_depth", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class rbp_mission_buf(C.Structure):
     _fields_ = [("N", C.c_int32), ("start", c_double_p), ("goal", c_double_p), ("radius", c_double_p),
                 ("speed", c_double_p), ("max_vel", c_double_p), ("max_acc", c_double_p)]

@@ -113,6 +113,7 @@ struct rbp_session {
     char* separation_buf = nullptr;  // rbp_session_separation: K structs, one chunk's work list and partial tallies (separation_workspace_bytes), reserved by the first call
     char* clearance_buf = nullptr;  // rbp_session_clearance: K structs and the agent kernel's records (clearance_workspace_bytes), reserved by the first call
     char* swept_buf = nullptr;  // rbp_session_swept_clearance: K structs, one chunk's work list, item clearances and partial tallies (swept_workspace_bytes), reserved by the first call
+    char* limits_buf = nullptr;  // rbp_session_limits: K structs, one chunk's work list, item ratios and partial tallies (limits_workspace_bytes), reserved by the first call
 };
 
 // waits for the session's asynchronous joint run, if one is in flight; reports its error once
@@ -143,6 +144,7 @@ size_t rbp_sizeof(int which) {
         case RBP_SIZEOF_CLEARANCE: return sizeof(rbp_clearance);
         case RBP_SIZEOF_SEPARATION: return sizeof(rbp_separation);
         case RBP_SIZEOF_SWEPT_CLEARANCE: return sizeof(rbp_swept_clearance);
+        case RBP_SIZEOF_LIMITS: return sizeof(rbp_limits);
         default: return 0;
     }
 }
@@ -997,6 +999,33 @@ int rbp_session_swept_clearance(rbp_session* s, int32_t depth, double refine_bel
     return swept_run("rbp_session_swept_clearance", s->device, in, out, agent_lower, s->swept_buf, (hipStream_t)stream);
 }
 
+// Certified intervals for the missions' largest velocity and acceleration ratios in continuous time from where the plans lie
+// (kernels/limits.hip): the report's inputs and the session's limits are read in place, K structs come back in one copy, the agents' upper
+// ratios go where the caller wants them, and nothing of the session is written.
+int rbp_session_limits(rbp_session* s, int32_t depth, double refine_above, rbp_limits* out, double* agent_upper, void* stream) {
+    if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_limits: null argument");
+    if (int rc = limits_check_arguments("rbp_session_limits", depth, refine_above)) return rc;
+    if (int jrc = join_worker(s)) return jrc;
+    if (!(s->last_stages & RBP_STAGE_PLANNER))
+        return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_limits: the session's last run did not include the PLANNER stage: there are no coefficients to bound");
+    const DevSession& d = s->d;
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->limits_buf) {
+        const hipError_t e = hipMalloc((void**)&s->limits_buf, limits_workspace_bytes(d.K, d.N, d.M));
+        if (e != hipSuccess) {
+            s->limits_buf = nullptr;
+            return fail(RBP_ERR_HIP, std::string("rbp_session_limits: workspace: ") + hipGetErrorString(e));
+        }
+    }
+    LimitsInputs in{};
+    in.r.K = d.K, in.r.N = d.N, in.r.M_stride = d.M, in.r.Mk = d.Mk, in.r.T = d.T, in.r.coef = d.coef, in.r.radius = d.radius;
+    in.r.ts = d.scalars + SC_TIME_SCALE, in.r.ts_stride = SC_N, in.r.status = d.status;
+    in.r.downwash = d.p.downwash, in.r.dt = 0.0;
+    in.max_vel = d.max_vel, in.max_acc = d.max_acc;
+    in.depth = depth, in.refine_above = refine_above;
+    return limits_run("rbp_session_limits", s->device, in, out, agent_upper, s->limits_buf, (hipStream_t)stream);
+}
+
 int rbp_session_device_arrays(rbp_session* s, int32_t mission, rbp_device_arrays* out) {
     if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "null argument");
     const DevSession& d = s->d;
@@ -1082,6 +1111,10 @@ void rbp_session_destroy(rbp_session* s) {
     if (s->swept_buf) {
         (void)hipSetDevice(s->device);
         (void)hipFree(s->swept_buf);
+    }
+    if (s->limits_buf) {
+        (void)hipSetDevice(s->device);
+        (void)hipFree(s->limits_buf);
     }
     if (s->ctx) {
         s->ctx->busy = false;  // the arena (and the QP workspace) stay with the context

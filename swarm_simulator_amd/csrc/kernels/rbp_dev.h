@@ -287,6 +287,25 @@ size_t swept_workspace_bytes(int K, int N, int M_stride);
 int launch_swept(const SweptInputs& in, double* agent_lower, void* workspace, hipStream_t st);
 int swept_run(const char* who, int device, const SweptInputs& in, rbp_swept_clearance* out, double* agent_lower, void* workspace, hipStream_t st);
 
+// kernels/limits.hip: certified intervals for the largest velocity and acceleration ratios of K missions in continuous time (rbp_limits of
+// include/rbp.h) from device arrays in a session's layout.  launch_limits enqueues its kernels on `st` and allocates nothing; agent_upper
+// [K][N][2] is a device pointer or null; the K structs are then at the front of `workspace` (limits_workspace_bytes(K, N, M_stride) bytes
+// of device memory, nothing to initialise: the structs, and one chunk's work-list counters, work list, item ratios and partial tallies,
+// sized by the shapes alone).  limits_run: the same with `agent_upper` wherever the caller has it -- on `device` (the current one), written
+// in place, or on the host, through one staging buffer -- and the structs copied to `out` on the host; it returns when all has arrived.
+// limits_check_arguments: depth and refine_above, no device work.  (r.radius, r.dt and r.downwash are not read.)
+struct LimitsInputs {
+    ReportInputs r;
+    const double* max_vel;  // [K][N][3]
+    const double* max_acc;  // [K][N][3]
+    int depth;
+    double refine_above;
+};
+int limits_check_arguments(const char* who, int32_t depth, double refine_above);
+size_t limits_workspace_bytes(int K, int N, int M_stride);
+int launch_limits(const LimitsInputs& in, double* agent_upper, void* workspace, hipStream_t st);
+int limits_run(const char* who, int device, const LimitsInputs& in, rbp_limits* out, double* agent_upper, void* workspace, hipStream_t st);
+
 // launchers (defined in the .hip files)
 int launch_corridor(const DevSession& s, hipStream_t st);
 size_t corridor_lds_bytes(const DevSession& s);  // dynamic LDS of sfc_kernel for this session's shapes

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _abi as A
-from .types import Clearance, Dynamics, Mission, Param, PlanResult, Report, Separation, SweptClearance, World
+from .types import Clearance, Dynamics, Limits, Mission, Param, PlanResult, Report, Separation, SweptClearance, World
 
 _lib = None
 
@@ -53,6 +53,8 @@ def lib():
                                           C.c_double, C.POINTER(A.rbp_separation), A.c_double_p]
         L.rbp_swept_clearance_host.argtypes = [C.POINTER(A.rbp_world), C.POINTER(A.rbp_mission), C.c_int32, A.c_double_p, A.c_double_p, C.c_int32,
                                                C.c_double, C.POINTER(A.rbp_swept_clearance), A.c_double_p]
+        L.rbp_limits_host.argtypes = [C.POINTER(A.rbp_mission), C.c_int32, A.c_double_p, A.c_double_p, C.c_int32, C.c_double,
+                                      C.POINTER(A.rbp_limits), A.c_double_p]
         L.rbp_write_coef_csv.argtypes =[C.c_char_p, C.c_int32, C.c_int32, A.c_double_p, A.c_double_p]
         L.rbp_write_qp_lp.argtypes = [C.c_char_p, C.POINTER(A.rbp_mission), C.POINTER(A.rbp_param), C.POINTER(A.rbp_plan), C.c_int32,
                                       A.c_double_p]
@@ -265,6 +267,21 @@ def swept_clearance(world: World, mission: Mission, plan: PlanResult, depth=4, r
     if rc:
         raise ValueError(f"rbp_swept_clearance_host rc={rc}")
     return (SweptClearance.from_c(out), agents) if per_agent else SweptClearance.from_c(out)
+
+
+def limits(mission: Mission, plan: PlanResult, depth=4, refine_above=0.5, per_agent=False):
+    """certified intervals for the plan's largest velocity and acceleration, as fractions of the mission's max_vel / max_acc, in continuous
+    time as a Limits, by the sequential loop the device shares (csrc/common/limits_rules.h): what planner.Session.limits /
+    planner.limits_coefs return for this plan, bit for bit.  per_agent: returns (Limits, [N][2] array of every agent's largest upper
+    velocity and acceleration ratio, 0 where there is none)."""
+    ms = mission.c_struct()
+    out = A.rbp_limits()
+    agents = np.zeros((plan.N, 2)) if per_agent else None
+    rc = lib().rbp_limits_host(C.byref(ms), plan.M, A.ptr(plan.T, A.c_double_p), A.ptr(plan.coef, A.c_double_p), depth, refine_above,
+                               C.byref(out), A.ptr(agents, A.c_double_p))
+    if rc:
+        raise ValueError(f"rbp_limits_host rc={rc}")
+    return (Limits.from_c(out), agents) if per_agent else Limits.from_c(out)
 
 
 def write_coef_csv(directory, plan: PlanResult):

@@ -11,7 +11,7 @@ import ctypes as C
 import os
 
 from . import _abi as A
-from .types import Clearance, DeviceWorld, Dynamics, Mission, Param, PlanResult, Report, Separation, SweptClearance, World
+from .types import Clearance, DeviceWorld, Dynamics, Limits, Mission, Param, PlanResult, Report, Separation, SweptClearance, World
 
 _lib = None
 
@@ -154,6 +154,11 @@ def lib():
                                                   P(A.rbp_world), C.c_int32, C.c_double, P(A.rbp_swept_clearance), C.c_void_p]
             if L.rbp_sizeof(A.RBP_SIZEOF_SWEPT_CLEARANCE) != C.sizeof(A.rbp_swept_clearance):
                 raise RbpLibraryMissing(f"{path}: sizeof(rbp_swept_clearance) is {L.rbp_sizeof(A.RBP_SIZEOF_SWEPT_CLEARANCE)} in the library, {C.sizeof(A.rbp_swept_clearance)} in this binding")
+            L.rbp_session_limits.argtypes = [C.c_void_p, C.c_int32, C.c_double, P(A.rbp_limits), C.c_void_p, C.c_void_p]
+            L.rbp_dev_limits.argtypes = [C.c_int, C.c_int32, C.c_int32, A.c_int32_p, C.c_int32, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p,
+                                         A.c_double_p, C.c_int32, C.c_double, P(A.rbp_limits), C.c_void_p]
+            if L.rbp_sizeof(A.RBP_SIZEOF_LIMITS) != C.sizeof(A.rbp_limits):
+                raise RbpLibraryMissing(f"{path}: sizeof(rbp_limits) is {L.rbp_sizeof(A.RBP_SIZEOF_LIMITS)} in the library, {C.sizeof(A.rbp_limits)} in this binding")
         except AttributeError:
             if not os.environ.get("RBP_HIP_LIB"):
                 raise
@@ -195,6 +200,7 @@ EXPORTED_SYMBOLS = [
     "rbp_session_clearance", "rbp_dev_clearance",
     "rbp_session_separation", "rbp_dev_separation",
     "rbp_session_swept_clearance", "rbp_dev_swept_clearance",
+    "rbp_session_limits", "rbp_dev_limits",
 ]
 
 
@@ -579,6 +585,34 @@ class Session:
             raise RuntimeError(f"rbp_session_swept_clearance rc={rc}: {last_error()}")
         return [SweptClearance.from_c(r) for r in out], ag
 
+    def limits(self, depth=4, refine_above=0.5, per_agent=False, device_out=False, stream=None):
+        """certified intervals for the missions' largest velocity and acceleration, as fractions of the agents' limits, in continuous time,
+        computed where the plans lie (rbp_session_limits): (records, agents) -- K Limits records, the bits host.limits gives for the
+        downloaded plans; agents [K][N][2], every agent's largest upper velocity and acceleration ratio (0 where there is none), or None
+        unless per_agent.  depth: the pieces of a refined item are 2^depth; refine_above: items with a depth-0 upper ratio above it are
+        refined (negative: all).  device_out: the array is a torch tensor on the session's device, written in place by the kernels;
+        otherwise a numpy array.  The row of a mission that is not computed keeps its zeros.  Nothing of the session changes; a mission
+        whose status is not 0 comes back with that status and nothing computed."""
+        import numpy as np
+        N = self.plans[0].N
+        out = (A.rbp_limits * self.K)()
+        ag, ap = None, None
+        if per_agent and device_out:
+            import torch
+            dev = torch.device("cuda", self.device)
+            ag = torch.zeros((self.K, N, 2), dtype=torch.float64, device=dev)
+            torch.cuda.synchronize(dev)   # (the fill is written on torch's stream, the kernels run on `stream`)
+            ap = ag.data_ptr()
+        elif per_agent:
+            ag = np.zeros((self.K, N, 2))
+            ap = ag.ctypes.data
+        rc = lib().rbp_session_limits(self._h, depth, refine_above, out, C.c_void_p(ap), C.c_void_p(stream or 0))
+        if rc == A.RBP_ERR_BAD_ARGUMENT:
+            raise ValueError(f"rbp_session_limits rc={rc}: {last_error()}")
+        if rc:
+            raise RuntimeError(f"rbp_session_limits rc={rc}: {last_error()}")
+        return [Limits.from_c(r) for r in out], ag
+
     def reserve_workspace(self, stream=None):
         """reserve the QP workspace now (otherwise the first PLANNER run does)"""
         rc = lib().rbp_session_reserve_workspace(self._h, C.c_void_p(stream or 0))
@@ -765,6 +799,38 @@ def swept_clearance_coefs(M, T, coef, radius, worlds, depth=4, refine_below=0.5,
     if rc:
         raise RuntimeError(f"rbp_dev_swept_clearance rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
     return [SweptClearance.from_c(r) for r in out]
+
+
+def limits_coefs(M, T, coef, max_vel, max_acc, depth=4, refine_above=0.5, time_scale=None, agent_upper=None, device=0):
+    """rbp_dev_limits: the limits kernels on the caller's arrays, uploaded once, in report_coefs' layout with max_vel / max_acc [K][N][3].
+    agent_upper: None, a C-contiguous float64 numpy array [K][N][2] or a torch tensor of that shape on `device`, written in place.
+    Returns K Limits records, the bits host.limits gives for the scaled times."""
+    import numpy as np
+    M = np.ascontiguousarray(M, np.int32).reshape(-1)
+    K = len(M)
+    T, coef, max_vel = A.as_f64(T).reshape(K, -1), A.as_f64(coef), A.as_f64(max_vel).reshape(K, -1, 3)
+    S, N = T.shape[1] - 1, max_vel.shape[1]
+    max_acc = A.as_f64(max_acc).reshape(K, N, 3)
+    if coef.size != K * N * 3 * 6 * S:
+        raise ValueError(f"coef holds {coef.size} doubles, K * N * 3 * 6 * M_stride = {K * N * 3 * 6 * S}")
+    ts = None if time_scale is None else A.as_f64(time_scale).reshape(K)
+    ap = None
+    if isinstance(agent_upper, np.ndarray):
+        if agent_upper.dtype != np.float64 or not agent_upper.flags["C_CONTIGUOUS"] or agent_upper.size != K * N * 2:
+            raise ValueError(f"agent_upper must be a C-contiguous float64 array of {K * N * 2} elements")
+        ap = agent_upper.ctypes.data
+    elif agent_upper is not None:
+        if str(agent_upper.dtype) != "torch.float64" or not agent_upper.is_contiguous() or agent_upper.numel() != K * N * 2:
+            raise ValueError(f"agent_upper must be a contiguous float64 tensor of {K * N * 2} elements")
+        ap = agent_upper.data_ptr()
+    out = (A.rbp_limits * K)()
+    rc = lib().rbp_dev_limits(device, K, N, A.ptr(M, A.c_int32_p), S, A.ptr(T, A.c_double_p), A.ptr(ts, A.c_double_p), A.ptr(coef, A.c_double_p),
+                              A.ptr(max_vel, A.c_double_p), A.ptr(max_acc, A.c_double_p), depth, refine_above, out, C.c_void_p(ap))
+    if rc == A.RBP_ERR_BAD_ARGUMENT:
+        raise ValueError(f"rbp_dev_limits rc={rc}: {last_error()}")
+    if rc:
+        raise RuntimeError(f"rbp_dev_limits rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+    return [Limits.from_c(r) for r in out]
 
 
 def separation_coefs(M, T, coef, radius, downwash, depth=4, refine_below=2.0, time_scale=None, pair_lower=None, device=0):

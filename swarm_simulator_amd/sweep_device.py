@@ -24,8 +24,12 @@ With --device-swept-clearance (only with --device-worlds --mode batched; off by 
 plans and grids adds a line per map with a certified interval for the smallest clearance to the obstacles in CONTINUOUS time, where both
 ends lie, and how many (agent, segment) items are uncertified, hitting, outside, over budget and refined (csrc/common/swept_rules.h):
 whether the plan is clear of the obstacles between the samples.
+With --device-limits (only with --device-worlds --mode batched; off by default) ONE planner.Session.limits() on the resident plans adds a
+line per map with certified intervals for the largest velocity and acceleration, as fractions of the agents' limits, in CONTINUOUS time,
+and how many (agent, segment) items are uncertified, violating and refined (csrc/common/limits_rules.h): whether the plan keeps max_vel and
+max_acc between the samples.
 
-usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]] [--device-report] [--device-dynamics] [--device-clearance] [--device-separation] [--device-swept-clearance]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
+usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]] [--device-report] [--device-dynamics] [--device-clearance] [--device-separation] [--device-swept-clearance] [--device-limits]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
        [--batch-size 4] [--iteration 1] [--joint] [--csv DIR]
 """
 import argparse
@@ -56,6 +60,9 @@ def main(argv=None):
     ap.add_argument("--device-swept-clearance", action="store_true", help="with --device-worlds --mode batched: one more line per map with a certified "
                     "interval for the smallest clearance to the obstacles in continuous time, where it lies, uncertified / hitting / outside / "
                     "over-budget / refined items, from one swept clearance call on the device (planner.Session.swept_clearance)")
+    ap.add_argument("--device-limits", action="store_true", help="with --device-worlds --mode batched: one more line per map with certified intervals "
+                    "for the largest velocity and acceleration ratios in continuous time, uncertified / violating / refined items, from one "
+                    "limits call on the device (planner.Session.limits)")
     ap.add_argument("--mission", default="mission_64agents_15.json")
     ap.add_argument("--maps", default="1-50")
     ap.add_argument("--mode", choices=["serial", "batched"], default="serial")
@@ -74,6 +81,8 @@ def main(argv=None):
         ap.error("--device-separation needs --device-worlds --mode batched")
     if args.device_swept_clearance and not (args.device_worlds and args.mode == "batched"):
         ap.error("--device-swept-clearance needs --device-worlds --mode batched")
+    if args.device_limits and not (args.device_worlds and args.mode == "batched"):
+        ap.error("--device-limits needs --device-worlds --mode batched")
     if args.device_ecbs and not args.device_worlds:
         ap.error("--device-ecbs needs --device-worlds")
     if args.device_handoff and not (args.device_ecbs and args.mode == "batched"):
@@ -167,6 +176,7 @@ def run_and_report(args, sess, maps, plans, mission, param):
     clear = sess.clearance()[0] if args.device_clearance else [None] * sess.K
     separ = sess.separation()[0] if args.device_separation else [None] * sess.K
     swept = sess.swept_clearance()[0] if args.device_swept_clearance else [None] * sess.K
+    limit = sess.limits()[0] if args.device_limits else [None] * sess.K
     dt = time.perf_counter() - t0
     print(f"BoxGenerator + SwarmPlanner runtime, {sess.K} maps in one session: {dt:.6f} "
           f"({sess.K * mission.qn / dt:.1f} agent-trajectories/s incl. {'download' if download else 'report'})")
@@ -175,7 +185,7 @@ def run_and_report(args, sess, maps, plans, mission, param):
         status = [r.status for r in records]
         plans = [SimpleNamespace(total_cost=float(c), time_scale=float(ts) if ts > 0 else 1.0, T=[r.end_time]) for (ts, c), r in zip(sc, records)]
     sess.close()
-    for i, p, st, rec, pk, cl, sp, sw in zip(maps, plans, status, records, peaks, clear, separ, swept):
+    for i, p, st, rec, pk, cl, sp, sw, lm in zip(maps, plans, status, records, peaks, clear, separ, swept, limit):
         if st:
             print(f"[ERROR] map{i}: status {st}")
             return -1
@@ -191,7 +201,21 @@ def run_and_report(args, sess, maps, plans, mission, param):
             separation_line(i, sp)
         if sw is not None:
             swept_clearance_line(i, sw)
+        if lm is not None:
+            limits_line(i, lm)
     return 0
+
+
+def limits_line(i, s):
+    """--device-limits: the two intervals of a types.Limits, where their upper ends lie (agent, axis, segment, piece of depth), and the item
+    counts; `none` for an end that no piece gave"""
+    def where(ratio, agent, axis, segment, piece, depth):
+        return f"{ratio:.5f} (agent {agent} axis {axis} segment {segment} piece {piece}/{1 << depth})" if segment >= 0 else "none"
+    print(f"map{i}: continuous velocity ratio in [{s.lower_vel_ratio:.5f}, "
+          f"{where(s.upper_vel_ratio, s.upper_vel_agent, s.upper_vel_axis, s.upper_vel_segment, s.upper_vel_piece, s.upper_vel_depth)}]  "
+          f"acceleration ratio in [{s.lower_acc_ratio:.5f}, "
+          f"{where(s.upper_acc_ratio, s.upper_acc_agent, s.upper_acc_axis, s.upper_acc_segment, s.upper_acc_piece, s.upper_acc_depth)}]  "
+          f"uncertified {s.uncertified}  violating {s.violating}  refined {s.refined}")
 
 
 def swept_clearance_line(i, s):

@@ -339,6 +339,56 @@ class SweptClearance:
         return tuple(int(x) for x in f) + tuple(getattr(self, n) for n in self.FIELDS[5:])
 
 
+@dataclass
+class Limits:
+    """rbp_limits (include/rbp.h): certified intervals for a mission's largest velocity and largest acceleration, as fractions of the agents'
+    max_vel / max_acc, in continuous time -- lower_X_ratio <= sup |X_k(t)| / max_X[a][k] <= upper_X_ratio over agents, axes and instants
+    (upper <= 1 certifies the limit, lower > 1 proves a violation) -- with the (segment, piece, agent, axis) and the depth of the piece each
+    of the four peaks came from (-1: none, ratio 0), the items (agent, segment) with a piece whose upper ratio is not <= 1 (uncertified),
+    with a piece whose lower ratio is > 1 (violating) and that were refined, and the end time.  status != 0: nothing computed."""
+    lower_vel_ratio: float
+    upper_vel_ratio: float
+    lower_acc_ratio: float
+    upper_acc_ratio: float
+    end_time: float
+    uncertified: int
+    violating: int
+    refined: int
+    lower_vel_segment: int
+    lower_vel_piece: int
+    lower_vel_agent: int
+    lower_vel_axis: int
+    lower_vel_depth: int
+    upper_vel_segment: int
+    upper_vel_piece: int
+    upper_vel_agent: int
+    upper_vel_axis: int
+    upper_vel_depth: int
+    lower_acc_segment: int
+    lower_acc_piece: int
+    lower_acc_agent: int
+    lower_acc_axis: int
+    lower_acc_depth: int
+    upper_acc_segment: int
+    upper_acc_piece: int
+    upper_acc_agent: int
+    upper_acc_axis: int
+    upper_acc_depth: int
+    status: int = 0
+
+    FIELDS = ("lower_vel_ratio", "upper_vel_ratio", "lower_acc_ratio", "upper_acc_ratio", "end_time", "uncertified", "violating", "refined",
+              "lower_vel_segment", "lower_vel_piece", "lower_vel_agent", "lower_vel_axis", "lower_vel_depth", "upper_vel_segment", "upper_vel_piece", "upper_vel_agent", "upper_vel_axis", "upper_vel_depth", "lower_acc_segment", "lower_acc_piece", "lower_acc_agent", "lower_acc_axis", "lower_acc_depth", "upper_acc_segment", "upper_acc_piece", "upper_acc_agent", "upper_acc_axis", "upper_acc_depth", "status")
+
+    @classmethod
+    def from_c(cls, r):
+        return cls(*[getattr(r, n) for n in cls.FIELDS])
+
+    def bits(self):
+        """the record with its doubles as bit patterns: what two evaluations of the one rule must agree on"""
+        f = np.array([getattr(self, n) for n in self.FIELDS[:5]], np.float64).view(np.uint64)
+        return tuple(int(x) for x in f) + tuple(getattr(self, n) for n in self.FIELDS[5:])
+
+
 class PlanResult:
     """sp_const.hpp:21-28 as flat arrays (include/rbp.h rbp_plan)."""
 
