@@ -347,7 +347,7 @@ void rbp_release_thread_context(void);
                               6: rbp_param.timescale_rule, rbp_plan.time_scale_alt */
 enum { RBP_SIZEOF_WORLD = 0, RBP_SIZEOF_MISSION = 1, RBP_SIZEOF_PARAM = 2, RBP_SIZEOF_PLAN = 3, RBP_SIZEOF_COUNTERS = 4, RBP_SIZEOF_DEVICE_ARRAYS = 5,
        RBP_SIZEOF_SOLVER_OPTS = 6, RBP_SIZEOF_ECBS_OUT = 7, RBP_SIZEOF_REPORT = 8, RBP_SIZEOF_DYNAMICS = 9, RBP_SIZEOF_CLEARANCE = 10, RBP_SIZEOF_SEPARATION = 11,
-       RBP_SIZEOF_SWEPT_CLEARANCE = 12, RBP_SIZEOF_LIMITS = 13 };
+       RBP_SIZEOF_SWEPT_CLEARANCE = 12, RBP_SIZEOF_LIMITS = 13, RBP_SIZEOF_SESSION_CAPACITY = 14 };
 int rbp_abi_version(void);
 size_t rbp_sizeof(int which);
 const char* rbp_version(void);
@@ -448,6 +448,40 @@ void rbp_dev_ecbs_destroy(rbp_dev_ecbs* e);
  * run_async, download, reset, device_arrays, set_solver_opts ... work as on a session of rbp_session_create.  A search whose missions
  * came without max_vel / max_acc is refused. */
 int  rbp_session_create_from_ecbs(rbp_session** out, const rbp_dev_ecbs* e, const rbp_param* param, int32_t max_boxes, int32_t* slot_of);
+
+/* ---- a session that outlives its missions: refilled from the next search, allocating nothing ---------
+ * A session's CAPACITY is what its arena was laid out for: K missions of N agents, slots of M segments and max_boxes boxes per agent.
+ * rbp_session_capacity_of returns it for every session: the K, N and the largest M / max_boxes a session of rbp_session_create,
+ * rbp_session_create_in or rbp_session_create_from_ecbs was created with, or what rbp_session_create_reserved was given.
+ * rbp_session_create_reserved builds an EMPTY session of that capacity on the device of `ws`, whose grids it will reference in place
+ *   (the set must outlive the session): the arena, the pinned staging block of the refills (K source indices, K M, K max_boxes and K
+ *   world descriptors, with its device twin and an event) and nothing else; the QP workspace and the reports' buffers are reserved by the
+ *   first call that needs them, as in every session, for the CAPACITY, and kept across refills.  Until it has been refilled the session
+ *   holds no mission: run, run_async, download and the reports are RBP_ERR_BAD_ARGUMENT ("holds no mission").  Null out / ws / cap / param,
+ *   K or N < 1, M < 2, max_boxes < 1 and the refusals of rbp_param known from rbp_session_create are RBP_ERR_BAD_ARGUMENT before a device
+ *   is looked for.
+ * rbp_session_refill_from_ecbs replaces the session's missions by those of `e` whose status is 0: they become slots 0 .. K'-1 in ascending
+ *   order, every mission keeps its own M, max_boxes <= 0 means each mission's M, and slot_of is written as by
+ *   rbp_session_create_from_ecbs.  The slot strides stay the capacity's; only the number of missions and their M / max_boxes change.  The
+ *   session is then as a fresh session of those missions: status, scalars and counters are cleared, it has no corridor inputs, and the
+ *   reports refuse until the next PLANNER run, after which every output has the bits a session of rbp_session_create_from_ecbs gives.
+ *   The call ALLOCATES NOTHING and frees nothing: source list, M, max_boxes and the K' world descriptors go up in ONE asynchronous copy
+ *   of the session's pinned staging block, one kernel (kernels/handoff.hip session_refill_kernel) on `stream` writes T, init_traj and the
+ *   mission arrays from what the handle holds and clears what a run reads or a download hands out of the slots' previous missions, and one
+ *   asynchronous clear on `stream` covers the K' blocks of the QP workspace if one has been reserved.  Everything is COPIED: the handle
+ *   may be destroyed as soon as the kernel has run (after a synchronisation of `stream`).  The call first joins an asynchronous solve, like
+ *   every session call, and it does NOT synchronise, with one exception: the staging block is reused, so a refill waits on the event
+ *   recorded behind the PREVIOUS refill's copy -- which has long completed when a run lies between the two.  The refill must be enqueued
+ *   on the stream the session's runs use, or ordered after them by the caller.  A session that was not created reserved reserves its
+ *   staging block in its first refill; it is refillable when all its grids are grids of the handle's set of worlds.
+ *   RBP_ERR_BAD_ARGUMENT, with the session left exactly as it was: a null session or handle (before a device is looked for); a handle on
+ *   another device or another set of worlds than the session's; e's N differs from the session's; no mission with status 0, or more than
+ *   the capacity's K; a mission's M or box capacity above the strides; a search whose missions came without max_vel / max_acc; a session
+ *   sharded over two ranks (rbp_session_shard_joint*); a session whose asynchronous solve failed (that error is returned). */
+typedef struct rbp_session_capacity { int32_t K, N, M, max_boxes; } rbp_session_capacity;
+int  rbp_session_create_reserved(rbp_session** out, const rbp_dev_worlds* ws, const rbp_session_capacity* cap, const rbp_param* param);
+int  rbp_session_capacity_of(const rbp_session* s, rbp_session_capacity* out);
+int  rbp_session_refill_from_ecbs(rbp_session* s, const rbp_dev_ecbs* e, int32_t max_boxes, int32_t* slot_of, void* stream);
 
 /* ---- a mission's acceptance signals on the device ---------------------------
  * The two numbers the reference prints per plan (rbp_publisher.hpp:685-695, 769-798): the smallest safety ratio -- downwash-scaled

@@ -166,6 +166,13 @@ class rbp_limits(C.Structure):
                 ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+RBP_SIZEOF_SESSION_CAPACITY = 14
+
+
+class rbp_session_capacity(C.Structure):
+    _fields_ = [("K", C.c_int32), ("N", C.c_int32), ("M", C.c_int32), ("max_boxes", C.c_int32)]
+
+
 class rbp_mission_buf(C.Structure):
     _fields_ = [("N", C.c_int32), ("start", c_double_p), ("goal", c_double_p), ("radius", c_double_p),
                 ("speed", c_double_p), ("max_vel", c_double_p), ("max_acc", c_double_p)]

@@ -114,7 +114,23 @@ struct rbp_session {
     char* clearance_buf = nullptr;  // rbp_session_clearance: K structs and the agent kernel's records (clearance_workspace_bytes), reserved by the first call
     char* swept_buf = nullptr;  // rbp_session_swept_clearance: K structs, one chunk's work list, item clearances and partial tallies (swept_workspace_bytes), reserved by the first call
     char* limits_buf = nullptr;  // rbp_session_limits: K structs, one chunk's work list, item ratios and partial tallies (limits_workspace_bytes), reserved by the first call
+    // rbp_session_refill_from_ecbs: the capacity the arena was laid out for (session_describe; after a refill d.K <= cap.K, and d.M, d.max_boxes
+    // stay cap's: the strides), the set of worlds the grids belong to (known for sessions that were created reserved or from a search, found
+    // by the first refill of any other), and the staging block of the refills (RefillStage of kernels/rbp_dev.h: pinned, its device twin, and
+    // the event behind the last copy out of it).  The QP workspace and the reports' buffers are sized for cap.K.
+    rbp_session_capacity cap{};
+    const rbp_dev_worlds* ws = nullptr;
+    bool empty = false;  // created reserved and not refilled yet: the session holds no mission
+    int lds_max = 0;     // the device's LDS per workgroup, as session_describe read it
+    char *stage_h = nullptr, *stage_d = nullptr;
+    hipEvent_t stage_ev = nullptr;
+    bool stage_busy = false;  // stage_ev has been recorded
 };
+
+// what run, download and the reports answer for a reserved session that has not been refilled
+static int no_mission(const rbp_session* s, const char* who) {
+    return s->empty ? fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + ": the session holds no mission (created reserved and not refilled yet: rbp_session_refill_from_ecbs)") : RBP_OK;
+}
 
 // waits for the session's asynchronous joint run, if one is in flight; reports its error once
 static int join_worker(rbp_session* s) {
@@ -145,6 +161,7 @@ size_t rbp_sizeof(int which) {
         case RBP_SIZEOF_SEPARATION: return sizeof(rbp_separation);
         case RBP_SIZEOF_SWEPT_CLEARANCE: return sizeof(rbp_swept_clearance);
         case RBP_SIZEOF_LIMITS: return sizeof(rbp_limits);
+        case RBP_SIZEOF_SESSION_CAPACITY: return sizeof(rbp_session_capacity);
         default: return 0;
     }
 }
@@ -245,7 +262,18 @@ static int session_reserve_arena(rbp_session* s, rbp_ctx* ctx, int device, size_
     return RBP_OK;
 }
 
-// the shapes and parameters of DevSession (everything but its pointers) for K missions on `worlds`, strides M and MB
+// words of LDS sfc_kernel reserves for the occupancy mask: the largest grid of the K worlds that fits
+static int session_mask_words(const rbp_world* worlds, int K) {
+    int mask_words = 0;
+    for (int k = 0; k < K; ++k) {
+        const size_t nc = (size_t)worlds[k].dim[0] * worlds[k].dim[1] * worlds[k].dim[2];
+        const size_t words = ((((nc + 63) >> 6) * 2 + 2) + 3) & ~size_t(3);
+        if (words <= SFC_MASK_WORDS) mask_words = std::max(mask_words, (int)words);
+    }
+    return mask_words;
+}
+
+// the shapes and parameters of DevSession (everything but its pointers) for K missions on `worlds`, strides M and MB; the session's capacity
 static int session_describe(rbp_session* s, int device, const rbp_param* param, const rbp_world* worlds, int K, int N, int M, int MB) {
     const int npair = N * (N - 1) / 2;
     DevSession& d = s->d;
@@ -255,17 +283,14 @@ static int session_describe(rbp_session* s, int device, const rbp_param* param, 
         const double bres = a < 2 ? param->box_xy_res : param->box_z_res;
         d.sfc_cap[a] = std::min(SFC_MAXS, (int)std::ceil((param->world_max[a] - param->world_min[a]) / bres) + 4);
     }
-    d.sfc_mask_words = 0;
-    for (int k = 0; k < K; ++k) {
-        const size_t nc = (size_t)worlds[k].dim[0] * worlds[k].dim[1] * worlds[k].dim[2];
-        const size_t words = ((((nc + 63) >> 6) * 2 + 2) + 3) & ~size_t(3);
-        if (words <= SFC_MASK_WORDS) d.sfc_mask_words = std::max(d.sfc_mask_words, (int)words);
-    }
+    s->cap.K = K, s->cap.N = N, s->cap.M = M, s->cap.max_boxes = MB;
+    d.sfc_mask_words = session_mask_words(worlds, K);
     {   // sfc_kernel keeps box_log [max_boxes][M + 1] per agent of a workgroup in LDS, beside the mask and the key lists: refuse here, with the
         // numbers, what the launch would refuse with a generic HIP error (the QP kernels take M <= QP_MAX_M = 128; the corridor's
         // bound depends on max_boxes, which defaults to M)
         int lds_max = 160 * 1024;
         (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
+        s->lds_max = lds_max;
         const size_t need = corridor_lds_bytes(d);
         if (need > (size_t)std::max(lds_max, 64 * 1024))
             return fail(RBP_ERR_BAD_ARGUMENT, "Corridor: " + std::to_string(need) + " bytes of LDS per workgroup for max_boxes = " + std::to_string(MB) +
@@ -540,10 +565,152 @@ int rbp_session_create_from_ecbs(rbp_session** out, const rbp_dev_ecbs* e, const
     if (int rc = launch_ecbs_plan_write(*e, K, d_src, in.Mk, M + 1, true, in.T, in.init_traj, nullptr)) return rc;
     if (int rc = launch_ecbs_mission_gather(*e, K, d_src, in.start, in.goal, in.radius, in.max_vel, in.max_acc, nullptr)) return rc;
     s->have_corridor_inputs = false;
+    s->ws = e->ws;
     if (int rc = rbp_session_reset(s, nullptr)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     guard.s = nullptr;
     *out = s;
+    return RBP_OK;
+}
+
+// The staging block of the refills and its device twin, sized for the capacity, and the event a refill waits on before it reuses the block.
+static int session_reserve_stage(rbp_session* s) {
+    if (s->stage_h) return RBP_OK;
+    const size_t bytes = RefillStage(s->cap.K).bytes();
+    HIP_TRY(hipHostMalloc((void**)&s->stage_h, bytes, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void**)&s->stage_d, bytes));
+    HIP_TRY(hipEventCreateWithFlags(&s->stage_ev, hipEventDisableTiming));
+    return RBP_OK;
+}
+
+// An empty session of a stated capacity on the device of a set of worlds: the arena, laid out and cleared as both constructors above do it,
+// and the refills' staging block.  rbp_session_refill_from_ecbs gives it its missions.
+int rbp_session_create_reserved(rbp_session** out, const rbp_dev_worlds* ws, const rbp_session_capacity* cap, const rbp_param* param) {
+    const char* who = "rbp_session_create_reserved: ";
+    if (out) *out = nullptr;
+    if (!out || !ws || !cap || !param) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "need out, the set of worlds, the capacity and param");
+    if (cap->K < 1 || cap->N < 1 || cap->M < 2 || cap->max_boxes < 1) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "need K >= 1, N >= 1, M >= 2, max_boxes >= 1");
+    if (int rc = check_session_param(param)) return rc;
+    const int K = cap->K, N = cap->N, M = cap->M, MB = cap->max_boxes, W = rbp_dev_worlds_count(ws);
+    if (W < 1) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "the set of worlds is empty");
+    const int device = dev_worlds_device(ws);
+    // the shapes session_describe looks at (the occupancy mask's words, the LDS of sfc_kernel) for the set's grids; a refill states them again
+    // for the worlds of its missions
+    std::vector<rbp_world> worlds(K);
+    for (int k = 0; k < K; ++k)
+        if (int rc = rbp_dev_worlds_get(ws, k % W, &worlds[k])) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const BatchSchedule sched = batch_schedule(param->sequential, param->batch_size, param->batch_iter, N);
+
+    struct Guard {  // every error path below releases the session (and with it the arena)
+        rbp_session* s;
+        ~Guard() {
+            if (s) rbp_session_destroy(s);
+        }
+    } guard{new rbp_session()};
+    rbp_session* s = guard.s;
+    s->device = device;
+    s->param = *param;
+    s->bs = sched.bs, s->biter = sched.biter;
+    {
+        hipDeviceProp_t prop;
+        s->n_cu = hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 256;
+    }
+    if (int rc = session_reserve_arena(s, nullptr, device, session_arena_bytes(0, K, N, M, MB))) return rc;  // (cleared, and the clear complete)
+    if (int rc = session_describe(s, device, param, worlds.data(), K, N, M, MB)) return rc;
+    SessionInputs in;
+    if (int rc = session_carve(s, in)) return rc;
+    if (int rc = session_reserve_stage(s)) return rc;
+    s->d.K = 0, s->empty = true;  // no mission yet
+    s->ws = ws;
+    s->have_corridor_inputs = false;
+    guard.s = nullptr;
+    *out = s;
+    return RBP_OK;
+}
+
+int rbp_session_capacity_of(const rbp_session* s, rbp_session_capacity* out) {
+    if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_capacity_of: null argument");
+    *out = s->cap;
+    return RBP_OK;
+}
+
+// The missions of a search into the slots 0 .. K'-1 of a session that exists.  Every check comes before anything of the session changes;
+// then the host's copy of the per-mission state follows, the staging block goes up in one asynchronous copy, and one kernel does the rest.
+int rbp_session_refill_from_ecbs(rbp_session* s, const rbp_dev_ecbs* e, int32_t max_boxes, int32_t* slot_of, void* stream) {
+    const char* who = "rbp_session_refill_from_ecbs: ";
+    if (!s || !e) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "need the session and the search's handle");
+    if (int jrc = join_worker(s)) return jrc;  // (a failed asynchronous solve: its error, and the session stays as it is)
+    if (!e->have_limits) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "the search's missions came without max_vel / max_acc");
+    if (s->shard.nranks == 2) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "a session sharded over two ranks (rbp_session_shard_joint) is not refilled");
+    if (e->device != s->device)
+        return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "the search lies on device " + std::to_string(e->device) + ", the session on device " + std::to_string(s->device));
+    const rbp_session_capacity& cap = s->cap;
+    if (e->N != cap.N) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "the search's missions have " + std::to_string(e->N) + " agents, the session's " + std::to_string(cap.N));
+    if (s->ws && e->ws != s->ws) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "the search ran on another set of worlds than the session's");
+    if (!s->ws) {  // a session of rbp_session_create / _create_in: refillable when every grid it plans on is a grid of the search's set
+        const int W = rbp_dev_worlds_count(e->ws);
+        for (const DevWorld& w : s->worlds_h) {
+            bool found = false;
+            for (int i = 0; i < W && !found; ++i) {
+                rbp_world g;
+                found = rbp_dev_worlds_get(e->ws, i, &g) == RBP_OK && g.dist == w.dist;
+            }
+            if (!found) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "the session's grids are not those of the search's set of worlds (rbp_dev_worlds)");
+        }
+    }
+    std::vector<int> src, slots(e->K);
+    for (int k = 0; k < e->K; ++k) {
+        slots[k] = e->status_h[k] == 0 ? (int)src.size() : -1;
+        if (e->status_h[k] == 0) src.push_back(k);
+    }
+    if (slot_of) std::copy(slots.begin(), slots.end(), slot_of);
+    const int K = (int)src.size();
+    if (K == 0) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "no mission of the search has status 0");
+    if (K > cap.K) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + std::to_string(K) + " missions with status 0, the session's capacity is " + std::to_string(cap.K));
+    std::vector<rbp_world> worlds(K);
+    std::vector<int> Mk(K), MBk(K);
+    for (int j = 0; j < K; ++j) {
+        Mk[j] = e->M_h[src[j]], MBk[j] = max_boxes > 0 ? max_boxes : Mk[j];
+        if (Mk[j] > cap.M || MBk[j] > cap.max_boxes)
+            return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "mission " + std::to_string(src[j]) + ": M = " + std::to_string(Mk[j]) + ", max_boxes = " + std::to_string(MBk[j]) +
+                                                  " exceed the session's strides M = " + std::to_string(cap.M) + ", max_boxes = " + std::to_string(cap.max_boxes));
+        if (int rc = rbp_dev_worlds_get(e->ws, e->world_index[src[j]], &worlds[j])) return rc;
+    }
+    DevSession nd = s->d;  // the occupancy mask's words are those of the new missions' worlds, as in a fresh session of them
+    nd.K = K, nd.sfc_mask_words = session_mask_words(worlds.data(), K);
+    if (corridor_lds_bytes(nd) > (size_t)std::max(s->lds_max, 64 * 1024))
+        return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "Corridor: " + std::to_string(corridor_lds_bytes(nd)) + " bytes of LDS per workgroup for the new missions' grids exceed the device's " +
+                                              std::to_string(s->lds_max));
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(s->device));
+    if (int rc = session_reserve_stage(s)) return rc;  // (a session that was not created reserved: its first refill)
+    if (s->stage_busy) HIP_TRY(hipEventSynchronize(s->stage_ev));  // the previous refill's copy has left the staging block
+    const RefillStage L(cap.K);
+    DevWorld* wd = reinterpret_cast<DevWorld*>(s->stage_h + L.worlds());
+    for (int j = 0; j < K; ++j) {
+        DevWorld& w = wd[j];
+        for (int a = 0; a < 3; ++a) w.dim[a] = worlds[j].dim[a], w.key_min[a] = worlds[j].key_min[a];
+        w.res = worlds[j].res;
+        w.dist = worlds[j].dist;  // referenced in place: the set of worlds outlives the session (include/rbp.h)
+    }
+    memcpy(s->stage_h + L.src(), src.data(), sizeof(int) * K);
+    memcpy(s->stage_h + L.Mk(), Mk.data(), sizeof(int) * K);
+    memcpy(s->stage_h + L.MBk(), MBk.data(), sizeof(int) * K);
+    HIP_TRY(hipMemcpyAsync(s->stage_d, s->stage_h, L.bytes(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(s->stage_ev, st));
+    s->stage_busy = true;
+    if (int rc = launch_session_refill(*e, nd, K, s->stage_d, cap.K, 8 * s->n_cu, st)) return rc;
+    // The batch QP kernels leave parts of a mission's workspace as the reservation cleared them (kernels/qp_batch.inc), and which parts
+    // depends on the mission: the blocks of the refilled slots are cleared again, on the stream, as a fresh session's would be
+    if (s->qp_ws) HIP_TRY(hipMemsetAsync(s->qp_ws, 0, s->qp_ws_per_mission * (size_t)K, st));
+    s->d = nd;
+    s->Mk = Mk, s->MBk = MBk;
+    s->worlds_h.assign(wd, wd + K);
+    s->ws = e->ws;
+    s->have_corridor_inputs = false;
+    s->last_stages = 0;
+    s->empty = false;
     return RBP_OK;
 }
 
@@ -584,7 +751,7 @@ int rbp_session_set_agent_range(rbp_session* s, int32_t agent_begin, int32_t age
 // session's own allocation or its context's (kept across the context's sessions, grown on demand), and cleared once.
 static int ensure_planner_workspace(rbp_session* s, hipStream_t st) {
     const DevSession& d = s->d;
-    const int N = d.N, M = d.M, K = d.K;
+    const int N = d.N, M = d.M, K = s->cap.K;  // (reserved for the capacity: a refill may bring up to cap.K missions)
     const rbp_solver_opts& o = s->opts;
     // The joint QP of a mission (plan/sequential = false: one batch of all N agents) is spread over the whole chip by kernels/jqp.hip when it
     // is wide enough to pay for a launch per phase (default: 16 agents or more, i.e. knot blocks of order >= 144).  Measured
@@ -665,6 +832,7 @@ int rbp_session_set_solver_opts(rbp_session* s, const rbp_solver_opts* o) {
 static int run_impl(rbp_session* s, int stages, void* stream, bool async) {
     if (!s) return fail(RBP_ERR_BAD_ARGUMENT, "null session");
     if (int jrc = join_worker(s)) return jrc;
+    if (int rc = no_mission(s, "rbp_session_run")) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(s->device));
     const rbp_solver_opts& o = s->opts;
@@ -780,6 +948,7 @@ int rbp_session_shard_joint_stream(rbp_session* s, int32_t rank, int32_t nranks,
 int rbp_session_download(rbp_session* s, rbp_plan* plans, int32_t* status, void* stream) {
     if (!s || !plans) return fail(RBP_ERR_BAD_ARGUMENT, "null argument");
     if (int jrc = join_worker(s)) return jrc;
+    if (int rc = no_mission(s, "rbp_session_download")) return rc;
     hipStream_t st = (hipStream_t)stream;
     const DevSession& d = s->d;
     const int K = d.K, N = d.N, M = d.M, MB = d.max_boxes, P = M + 1, oq = 6 * M;
@@ -867,6 +1036,7 @@ int rbp_session_report(rbp_session* s, double dt, rbp_report* out, void* stream)
     if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_report: null argument");
     if (!(dt > 0)) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_report: dt must be positive");
     if (int jrc = join_worker(s)) return jrc;
+    if (int rc = no_mission(s, "rbp_session_report")) return rc;
     if (!(s->last_stages & RBP_STAGE_PLANNER))
         return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_report: the session's last run did not include the PLANNER stage: there are no coefficients to report on");
     const DevSession& d = s->d;
@@ -875,7 +1045,7 @@ int rbp_session_report(rbp_session* s, double dt, rbp_report* out, void* stream)
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(s->device));
     if (!s->report_buf) {
-        const hipError_t e = hipMalloc((void**)&s->report_buf, report_workspace_bytes(d.K));
+        const hipError_t e = hipMalloc((void**)&s->report_buf, report_workspace_bytes(s->cap.K));
         if (e != hipSuccess) {
             s->report_buf = nullptr;
             return fail(RBP_ERR_HIP, std::string("rbp_session_report: workspace: ") + hipGetErrorString(e));
@@ -899,6 +1069,7 @@ int rbp_session_dynamics(rbp_session* s, double dt, rbp_dynamics* out, double* s
     if (!(dt > 0)) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_dynamics: dt must be positive");
     if ((states || curves) && S_stride < 1) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_dynamics: S_stride must be at least 1 where states or curves are given");
     if (int jrc = join_worker(s)) return jrc;
+    if (int rc = no_mission(s, "rbp_session_dynamics")) return rc;
     if (!(s->last_stages & RBP_STAGE_PLANNER))
         return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_dynamics: the session's last run did not include the PLANNER stage: there are no coefficients to sample");
     const DevSession& d = s->d;
@@ -906,7 +1077,7 @@ int rbp_session_dynamics(rbp_session* s, double dt, rbp_dynamics* out, double* s
         return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_dynamics: " + std::to_string(d.N) + " agents: the positions of one sample do not fit the curve kernel's LDS budget");
     HIP_TRY(hipSetDevice(s->device));
     if (!s->dynamics_buf) {
-        const hipError_t e = hipMalloc((void**)&s->dynamics_buf, dynamics_workspace_bytes(d.K));
+        const hipError_t e = hipMalloc((void**)&s->dynamics_buf, dynamics_workspace_bytes(s->cap.K));
         if (e != hipSuccess) {
             s->dynamics_buf = nullptr;
             return fail(RBP_ERR_HIP, std::string("rbp_session_dynamics: workspace: ") + hipGetErrorString(e));
@@ -927,12 +1098,13 @@ int rbp_session_clearance(rbp_session* s, double dt, rbp_clearance* out, double*
     if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_clearance: null argument");
     if (!(dt > 0)) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_clearance: dt must be positive");
     if (int jrc = join_worker(s)) return jrc;
+    if (int rc = no_mission(s, "rbp_session_clearance")) return rc;
     if (!(s->last_stages & RBP_STAGE_PLANNER))
         return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_clearance: the session's last run did not include the PLANNER stage: there are no coefficients to look up");
     const DevSession& d = s->d;
     HIP_TRY(hipSetDevice(s->device));
     if (!s->clearance_buf) {
-        const hipError_t e = hipMalloc((void**)&s->clearance_buf, clearance_workspace_bytes(d.K, d.N));
+        const hipError_t e = hipMalloc((void**)&s->clearance_buf, clearance_workspace_bytes(s->cap.K, d.N));
         if (e != hipSuccess) {
             s->clearance_buf = nullptr;
             return fail(RBP_ERR_HIP, std::string("rbp_session_clearance: workspace: ") + hipGetErrorString(e));
@@ -953,12 +1125,13 @@ int rbp_session_separation(rbp_session* s, int32_t depth, double refine_below, r
     if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_separation: null argument");
     if (int rc = separation_check_arguments("rbp_session_separation", depth, refine_below)) return rc;
     if (int jrc = join_worker(s)) return jrc;
+    if (int rc = no_mission(s, "rbp_session_separation")) return rc;
     if (!(s->last_stages & RBP_STAGE_PLANNER))
         return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_separation: the session's last run did not include the PLANNER stage: there are no coefficients to bound");
     const DevSession& d = s->d;
     HIP_TRY(hipSetDevice(s->device));
     if (!s->separation_buf) {
-        const hipError_t e = hipMalloc((void**)&s->separation_buf, separation_workspace_bytes(d.K, d.N, d.M));
+        const hipError_t e = hipMalloc((void**)&s->separation_buf, separation_workspace_bytes(s->cap.K, d.N, d.M));
         if (e != hipSuccess) {
             s->separation_buf = nullptr;
             return fail(RBP_ERR_HIP, std::string("rbp_session_separation: workspace: ") + hipGetErrorString(e));
@@ -979,12 +1152,13 @@ int rbp_session_swept_clearance(rbp_session* s, int32_t depth, double refine_bel
     if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_swept_clearance: null argument");
     if (int rc = swept_check_arguments("rbp_session_swept_clearance", depth, refine_below)) return rc;
     if (int jrc = join_worker(s)) return jrc;
+    if (int rc = no_mission(s, "rbp_session_swept_clearance")) return rc;
     if (!(s->last_stages & RBP_STAGE_PLANNER))
         return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_swept_clearance: the session's last run did not include the PLANNER stage: there are no coefficients to bound");
     const DevSession& d = s->d;
     HIP_TRY(hipSetDevice(s->device));
     if (!s->swept_buf) {
-        const hipError_t e = hipMalloc((void**)&s->swept_buf, swept_workspace_bytes(d.K, d.N, d.M));
+        const hipError_t e = hipMalloc((void**)&s->swept_buf, swept_workspace_bytes(s->cap.K, d.N, d.M));
         if (e != hipSuccess) {
             s->swept_buf = nullptr;
             return fail(RBP_ERR_HIP, std::string("rbp_session_swept_clearance: workspace: ") + hipGetErrorString(e));
@@ -1006,12 +1180,13 @@ int rbp_session_limits(rbp_session* s, int32_t depth, double refine_above, rbp_l
     if (!s || !out) return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_limits: null argument");
     if (int rc = limits_check_arguments("rbp_session_limits", depth, refine_above)) return rc;
     if (int jrc = join_worker(s)) return jrc;
+    if (int rc = no_mission(s, "rbp_session_limits")) return rc;
     if (!(s->last_stages & RBP_STAGE_PLANNER))
         return fail(RBP_ERR_BAD_ARGUMENT, "rbp_session_limits: the session's last run did not include the PLANNER stage: there are no coefficients to bound");
     const DevSession& d = s->d;
     HIP_TRY(hipSetDevice(s->device));
     if (!s->limits_buf) {
-        const hipError_t e = hipMalloc((void**)&s->limits_buf, limits_workspace_bytes(d.K, d.N, d.M));
+        const hipError_t e = hipMalloc((void**)&s->limits_buf, limits_workspace_bytes(s->cap.K, d.N, d.M));
         if (e != hipSuccess) {
             s->limits_buf = nullptr;
             return fail(RBP_ERR_HIP, std::string("rbp_session_limits: workspace: ") + hipGetErrorString(e));
@@ -1115,6 +1290,12 @@ void rbp_session_destroy(rbp_session* s) {
     if (s->limits_buf) {
         (void)hipSetDevice(s->device);
         (void)hipFree(s->limits_buf);
+    }
+    if (s->stage_h || s->stage_d || s->stage_ev) {
+        (void)hipSetDevice(s->device);
+        if (s->stage_ev) (void)hipEventDestroy(s->stage_ev);
+        if (s->stage_h) (void)hipHostFree(s->stage_h);
+        if (s->stage_d) (void)hipFree(s->stage_d);
     }
     if (s->ctx) {
         s->ctx->busy = false;  // the arena (and the QP workspace) stay with the context

@@ -416,6 +416,7 @@ extern "C" int rbp_dev_worlds_create(rbp_dev_worlds** out, int device, int32_t W
 }
 
 extern "C" int rbp_dev_worlds_count(const rbp_dev_worlds* ws) { return ws ? (int)ws->desc.size() : 0; }
+int dev_worlds_device(const rbp_dev_worlds* ws) { return ws->device; }
 
 extern "C" int rbp_dev_worlds_get(const rbp_dev_worlds* ws, int32_t w, rbp_world* out) {
     if (!ws || !out || w < 0 || w >= (int)ws->desc.size()) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "rbp_dev_worlds_get: null argument or world index out of range");

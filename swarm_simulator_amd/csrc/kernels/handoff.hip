@@ -7,7 +7,10 @@
 //                               stride = the largest M + 1 of the missions it holds, and inside its slot every mission is laid out with
 //                               its own M + 1, as kernels/rbp_dev.h says of a session);
 //   ecbs_mission_gather_kernel  start / goal / radius / max_vel / max_acc of the chosen missions into the session's [n][N][...] arrays.
-// Both are one element per lane, consecutive lanes on consecutive elements of a row: plain vector loads and stores, no LDS, no atomics.
+//   session_refill_kernel       both of the above for the slots 0 .. n-1 of a session that already exists (rbp_session_refill_from_ecbs), with the
+//                               slots' descriptors and the clears a fresh arena would have provided, in one launch.
+// All are one element per lane, consecutive lanes on consecutive elements of a row: plain vector loads and stores, no LDS, no atomics.  The
+// element bodies (plan_time_element, plan_traj_element, mission_gather_element) are stated once and called by the kernels that need them.
 // Every value of the first is a rule of common/ecbs_rules.h (plan_time, plan_waypoint) -- the text the host's write_plan loops over -- and
 // that header's `#pragma clang fp contract(off)` holds for this whole file, so the device rounds each operation as the host does.
 #include "rbp_dev.h"
@@ -34,20 +37,14 @@ struct PlanWrite {
     float* init_traj;               // [n][N * stride * 3]
 };
 
-// The first n * chunks blocks write the slots of init_traj, one float per lane and a slot `chunks` blocks wide; the last n * t_chunks
-// blocks write the rows of T.  Every element of the destination is written: what lies beyond a mission's own M is zero.
-__global__ __launch_bounds__(HANDOFF_THREADS) void ecbs_plan_write_kernel(PlanWrite w) {
-    const int traj_blocks = w.n * w.chunks;
-    if ((int)blockIdx.x >= traj_blocks) {
-        const int tb = (int)blockIdx.x - traj_blocks, j = tb / w.t_chunks;
-        const int i = (tb - j * w.t_chunks) * HANDOFF_THREADS + (int)threadIdx.x;
-        if (i < w.stride) w.T[(size_t)j * w.stride + i] = i <= w.Mj[j] ? ecbs_rules::plan_time(i, w.time_step) : 0.0;
-        return;
-    }
-    const int j = (int)blockIdx.x / w.chunks;
-    const int f = ((int)blockIdx.x - j * w.chunks) * HANDOFF_THREADS + (int)threadIdx.x;   // float of slot j
+// element i of row j of T: what lies beyond a mission's own M is zero
+__device__ __forceinline__ void plan_time_element(const PlanWrite& w, int j, int i) {
+    w.T[(size_t)j * w.stride + i] = i <= w.Mj[j] ? ecbs_rules::plan_time(i, w.time_step) : 0.0;
+}
+
+// float f (< 3 N stride) of slot j of init_traj: what lies beyond a mission's own M is zero
+__device__ __forceinline__ void plan_traj_element(const PlanWrite& w, int j, int f) {
     const int slot = 3 * w.N * w.stride;
-    if (f >= slot) return;
     const int M = w.Mj[j], row = 3 * (w.compact && M >= 0 ? M + 1 : w.stride);
     const int a = f / row, e = f - a * row, wp = e / 3, axis = e - 3 * wp;
     float v = 0.0f;
@@ -59,6 +56,22 @@ __global__ __launch_bounds__(HANDOFF_THREADS) void ecbs_plan_write_kernel(PlanWr
     w.init_traj[(size_t)j * slot + f] = v;
 }
 
+// The first n * chunks blocks write the slots of init_traj, one float per lane and a slot `chunks` blocks wide; the last n * t_chunks
+// blocks write the rows of T.  Every element of the destination is written: what lies beyond a mission's own M is zero.
+__global__ __launch_bounds__(HANDOFF_THREADS) void ecbs_plan_write_kernel(PlanWrite w) {
+    const int traj_blocks = w.n * w.chunks;
+    if ((int)blockIdx.x >= traj_blocks) {
+        const int tb = (int)blockIdx.x - traj_blocks, j = tb / w.t_chunks;
+        const int i = (tb - j * w.t_chunks) * HANDOFF_THREADS + (int)threadIdx.x;
+        if (i < w.stride) plan_time_element(w, j, i);
+        return;
+    }
+    const int j = (int)blockIdx.x / w.chunks;
+    const int f = ((int)blockIdx.x - j * w.chunks) * HANDOFF_THREADS + (int)threadIdx.x;   // float of slot j
+    if (f >= 3 * w.N * w.stride) return;
+    plan_traj_element(w, j, f);
+}
+
 struct MissionGather {
     int n, N;
     const int* src;                                            // [n]
@@ -66,13 +79,8 @@ struct MissionGather {
     double *d_start, *d_goal, *d_radius, *d_max_vel, *d_max_acc;  // [n][N][9 9 1 3 3]
 };
 
-// 25 N doubles per mission: its [N][9] start, [N][9] goal, [N] radius, [N][3] max_vel, [N][3] max_acc, one double per lane
-__global__ __launch_bounds__(HANDOFF_THREADS) void ecbs_mission_gather_kernel(MissionGather g) {
-    const long long t = (long long)blockIdx.x * HANDOFF_THREADS + threadIdx.x;
-    const int per = 25 * g.N;
-    if (t >= (long long)g.n * per) return;
-    const int j = (int)(t / per);
-    int r = (int)(t - (long long)j * per);
+// double r (< 25 N) of mission j: its [N][9] start, [N][9] goal, [N] radius, [N][3] max_vel, [N][3] max_acc
+__device__ __forceinline__ void mission_gather_element(const MissionGather& g, int j, int r) {
     const size_t s = (size_t)g.src[j] * g.N, d = (size_t)j * g.N;
     if (r < 9 * g.N) {
         g.d_start[d * 9 + r] = g.start[s * 9 + r];
@@ -95,6 +103,84 @@ __global__ __launch_bounds__(HANDOFF_THREADS) void ecbs_mission_gather_kernel(Mi
     }
     r -= 3 * g.N;
     g.d_max_acc[d * 3 + r] = g.max_acc[s * 3 + r];
+}
+
+// 25 N doubles per mission, one double per lane
+__global__ __launch_bounds__(HANDOFF_THREADS) void ecbs_mission_gather_kernel(MissionGather g) {
+    const long long t = (long long)blockIdx.x * HANDOFF_THREADS + threadIdx.x;
+    const int per = 25 * g.N;
+    if (t >= (long long)g.n * per) return;
+    const int j = (int)(t / per);
+    mission_gather_element(g, j, (int)(t - (long long)j * per));
+}
+
+// ---- the refill of a session that exists ------------------------------------------------------------------------------------------------
+constexpr int REFILL_THREADS = 256;
+constexpr int REFILL_Z64 = 8;  // ranges of 8-byte words cleared from their base: scalars, counters, qp_cost, sfc_box, sfc_time, rsfc_time, ctrl, coef
+
+struct SessionRefill {
+    PlanWrite w;      // n slots, compact, stride = the session's M + 1; src and Mj are the STAGED lists
+    MissionGather g;  // (src: the staged list)
+    const unsigned long long* st_worlds;  // staged descriptors, WORLD_WORDS words each
+    const int* st_MBk;
+    unsigned long long* worlds;
+    int *Mk, *MBk, *status, *qp_order, *sfc_count;
+    float* rsfc_normal;
+    unsigned long long* z64[REFILL_Z64];
+    long long n64[REFILL_Z64];
+    long long n_traj, n_T, n_gather, n_desc, n_count, n_normal, total;
+};
+constexpr int WORLD_WORDS = (int)(sizeof(DevWorld) / sizeof(unsigned long long));
+static_assert(sizeof(DevWorld) % sizeof(unsigned long long) == 0, "a descriptor is copied in 8-byte words");
+
+// One flat index space, walked by a grid-stride loop, one element per lane and step: the floats of init_traj, the doubles of T, the
+// gathered doubles, the descriptors' words with each slot's Mk / MBk / status / qp_order, sfc_count, the floats of rsfc_normal, and the
+// 8-byte ranges.  Slots 0 .. n-1 of every array are contiguous from its base, so every clear is a range from the base.
+__global__ __launch_bounds__(REFILL_THREADS) void session_refill_kernel(SessionRefill r) {
+    const long long step = (long long)gridDim.x * REFILL_THREADS;
+    for (long long t = (long long)blockIdx.x * REFILL_THREADS + threadIdx.x; t < r.total; t += step) {
+        long long i = t;
+        if (i < r.n_traj) {
+            const int slot = 3 * r.w.N * r.w.stride, j = (int)(i / slot);
+            plan_traj_element(r.w, j, (int)(i - (long long)j * slot));
+            continue;
+        }
+        i -= r.n_traj;
+        if (i < r.n_T) {
+            const int j = (int)(i / r.w.stride);
+            plan_time_element(r.w, j, (int)(i - (long long)j * r.w.stride));
+            continue;
+        }
+        i -= r.n_T;
+        if (i < r.n_gather) {
+            const int per = 25 * r.g.N, j = (int)(i / per);
+            mission_gather_element(r.g, j, (int)(i - (long long)j * per));
+            continue;
+        }
+        i -= r.n_gather;
+        if (i < r.n_desc) {
+            r.worlds[i] = r.st_worlds[i];
+            const int j = (int)(i / WORLD_WORDS);
+            if (i == (long long)j * WORLD_WORDS) r.Mk[j] = r.w.Mj[j], r.MBk[j] = r.st_MBk[j], r.status[j] = 0, r.qp_order[j] = 0;
+            continue;
+        }
+        i -= r.n_desc;
+        if (i < r.n_count) {
+            r.sfc_count[i] = 0;
+            continue;
+        }
+        i -= r.n_count;
+        if (i < r.n_normal) {
+            r.rsfc_normal[i] = 0.0f;
+            continue;
+        }
+        i -= r.n_normal;
+#pragma unroll
+        for (int z = 0; z < REFILL_Z64; ++z) {
+            if (i >= 0 && i < r.n64[z]) r.z64[z][i] = 0ull;
+            i -= r.n64[z];
+        }
+    }
 }
 
 int launched(const char* who) {
@@ -131,4 +217,42 @@ int launch_ecbs_mission_gather(const rbp_dev_ecbs& e, int n, const int* src, dou
     if (n <= 0 || blocks > 0x7fffffffLL) return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "ecbs_mission_gather_kernel: nothing to gather, or more than 2^31 blocks");
     hipLaunchKernelGGL(ecbs_mission_gather_kernel, dim3((unsigned)blocks), dim3(HANDOFF_THREADS), 0, st, g);
     return launched("ecbs_mission_gather_kernel");
+}
+
+int launch_session_refill(const rbp_dev_ecbs& e, const DevSession& d, int n, const char* staged, int capacity_K, int max_blocks, hipStream_t st) {
+    const RefillStage L(capacity_K);
+    const int N = d.N, M = d.M, MB = d.max_boxes, PS = M + 1;
+    const long long slot = 3LL * N * PS;
+    if (n <= 0 || n > capacity_K || slot > 0x7fffffffLL)
+        return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "session_refill_kernel: nothing to refill, more missions than the capacity, or more than 2^31 floats per mission");
+    SessionRefill r{};
+    const int* src = reinterpret_cast<const int*>(staged + L.src());
+    const int* Mj = reinterpret_cast<const int*>(staged + L.Mk());
+    PlanWrite& w = r.w;
+    w.n = n, w.N = N, w.stride = PS, w.path_stride = e.path_stride, w.compact = 1;
+    for (int a = 0; a < 3; ++a) w.gmin[a] = e.gmin[a], w.gres[a] = e.gres[a];
+    w.time_step = e.time_step;
+    w.src = src, w.Mj = Mj, w.out_len = e.out_len, w.out_path = e.out_path, w.start = e.start, w.goal = e.goal;
+    w.T = d.T, w.init_traj = const_cast<float*>(d.init_traj);
+    MissionGather& g = r.g;
+    g.n = n, g.N = N, g.src = src;
+    g.start = e.start, g.goal = e.goal, g.radius = e.radius, g.max_vel = e.max_vel, g.max_acc = e.max_acc;
+    g.d_start = const_cast<double*>(d.start), g.d_goal = const_cast<double*>(d.goal), g.d_radius = const_cast<double*>(d.radius);
+    g.d_max_vel = const_cast<double*>(d.max_vel), g.d_max_acc = const_cast<double*>(d.max_acc);
+    r.st_worlds = reinterpret_cast<const unsigned long long*>(staged + L.worlds());
+    r.st_MBk = reinterpret_cast<const int*>(staged + L.MBk());
+    r.worlds = reinterpret_cast<unsigned long long*>(const_cast<DevWorld*>(d.worlds));
+    r.Mk = const_cast<int*>(d.Mk), r.MBk = const_cast<int*>(d.MBk), r.status = d.status, r.qp_order = d.qp_order, r.sfc_count = d.sfc_count;
+    r.rsfc_normal = d.rsfc_normal;
+    const long long oq = 6LL * M;
+    auto z64 = [&](int z, void* p, long long per_slot) { r.z64[z] = static_cast<unsigned long long*>(p), r.n64[z] = per_slot * n; };
+    z64(0, d.scalars, SC_N), z64(1, d.counters, CT_N), z64(2, d.qp_cost, 1), z64(3, d.sfc_box, 6LL * N * MB), z64(4, d.sfc_time, (long long)N * MB);
+    z64(5, d.rsfc_time, M), z64(6, d.ctrl, 3LL * N * oq), z64(7, d.coef, 3LL * N * oq);
+    r.n_traj = slot * n, r.n_T = (long long)PS * n, r.n_gather = 25LL * N * n, r.n_desc = (long long)WORLD_WORDS * n;
+    r.n_count = (long long)N * n, r.n_normal = 3LL * d.npair * M * n;
+    r.total = r.n_traj + r.n_T + r.n_gather + r.n_desc + r.n_count + r.n_normal;
+    for (int z = 0; z < REFILL_Z64; ++z) r.total += r.n64[z];
+    const long long blocks = std::min<long long>((r.total + REFILL_THREADS - 1) / REFILL_THREADS, std::max(max_blocks, 1));
+    hipLaunchKernelGGL(session_refill_kernel, dim3((unsigned)blocks), dim3(REFILL_THREADS), 0, st, r);
+    return launched("session_refill_kernel");
 }

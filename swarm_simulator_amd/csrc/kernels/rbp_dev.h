@@ -201,6 +201,26 @@ int launch_ecbs_plan_write(const rbp_dev_ecbs& e, int n, const int* src, const i
 int launch_ecbs_mission_gather(const rbp_dev_ecbs& e, int n, const int* src, double* start, double* goal, double* radius, double* max_vel,
                                double* max_acc, hipStream_t st);
 
+// kernels/handoff.hip: a session's slots 0 .. n-1 refilled from the resident results of `e` in ONE launch (rbp_session_refill_from_ecbs).
+// `staged` is the device twin of the session's staging block, laid out by RefillStage for the session's capacity K: the world
+// descriptors, then the source list, Mk and MBk of the n missions.  session_refill_kernel copies descriptors, Mk and MBk into the
+// session's arrays, writes T / init_traj (the element bodies of ecbs_plan_write_kernel, compact, stride d.M + 1) and the five mission
+// arrays (the element body of ecbs_mission_gather_kernel), and clears, for those slots, what a run reads before it writes or a download
+// hands out beyond what a run writes: status, scalars, counters, qp_order, qp_cost, sfc_count, sfc_box, sfc_time, rsfc_normal, rsfc_time,
+// ctrl and coef.  `d` holds the session's pointers and STRIDES (d.K is not read).  No allocation, no synchronisation.
+struct RefillStage {
+    int K;  // capacity
+    explicit RefillStage(int capacity) : K(capacity) {}
+    size_t worlds() const { return 0; }
+    size_t src() const { return sizeof(DevWorld) * (size_t)K; }
+    size_t Mk() const { return src() + sizeof(int) * (size_t)K; }
+    size_t MBk() const { return Mk() + sizeof(int) * (size_t)K; }
+    size_t bytes() const { return MBk() + sizeof(int) * (size_t)K; }
+};
+int launch_session_refill(const rbp_dev_ecbs& e, const DevSession& d, int n, const char* staged, int capacity_K, int max_blocks, hipStream_t st);
+// kernels/edt.hip: the device a set of worlds lies on
+int dev_worlds_device(const rbp_dev_worlds* ws);
+
 // kernels/report.hip: the safety ratio and flight distance of K missions (rbp_report of include/rbp.h) from device arrays in a session's
 // layout.  launch_report enqueues its two kernels on `st`; the K reports are then at the front of `workspace` (report_workspace_bytes(K)
 // bytes of device memory, nothing to initialise).  report_tile(N) == 0: more agents than one sample's positions fit the LDS budget for,

@@ -159,6 +159,11 @@ def lib():
                                          A.c_double_p, C.c_int32, C.c_double, P(A.rbp_limits), C.c_void_p]
             if L.rbp_sizeof(A.RBP_SIZEOF_LIMITS) != C.sizeof(A.rbp_limits):
                 raise RbpLibraryMissing(f"{path}: sizeof(rbp_limits) is {L.rbp_sizeof(A.RBP_SIZEOF_LIMITS)} in the library, {C.sizeof(A.rbp_limits)} in this binding")
+            L.rbp_session_create_reserved.argtypes = [P(C.c_void_p), C.c_void_p, P(A.rbp_session_capacity), P(A.rbp_param)]
+            L.rbp_session_capacity_of.argtypes = [C.c_void_p, P(A.rbp_session_capacity)]
+            L.rbp_session_refill_from_ecbs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, A.c_int32_p, C.c_void_p]
+            if L.rbp_sizeof(A.RBP_SIZEOF_SESSION_CAPACITY) != C.sizeof(A.rbp_session_capacity):
+                raise RbpLibraryMissing(f"{path}: sizeof(rbp_session_capacity) is {L.rbp_sizeof(A.RBP_SIZEOF_SESSION_CAPACITY)} in the library, {C.sizeof(A.rbp_session_capacity)} in this binding")
         except AttributeError:
             if not os.environ.get("RBP_HIP_LIB"):
                 raise
@@ -201,6 +206,7 @@ EXPORTED_SYMBOLS = [
     "rbp_session_separation", "rbp_dev_separation",
     "rbp_session_swept_clearance", "rbp_dev_swept_clearance",
     "rbp_session_limits", "rbp_dev_limits",
+    "rbp_session_create_reserved", "rbp_session_capacity_of", "rbp_session_refill_from_ecbs",
 ]
 
 
@@ -320,6 +326,7 @@ class Session:
         K = len(plans)
         assert len(worlds) == K and len(missions) == K
         self.K, self.plans, self.param, self.device = K, plans, param, device
+        self._N = plans[0].N
         self._keep = (worlds, missions)
         self._w = (A.rbp_world * K)(*[w.c_struct() for w in worlds])
         self._m = (A.rbp_mission * K)(*[m.c_struct() for m in missions])
@@ -352,15 +359,85 @@ class Session:
             raise ValueError(f"rbp_session_create_from_ecbs rc={rc}: {last_error()}")
         if rc:
             raise RuntimeError(f"rbp_session_create_from_ecbs failed rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
-        self.slot_of = slot_of
-        N = dev_ecbs.N
-        self.plans = [PlanResult(np.zeros((N, int(M) + 1, 3), np.float32), np.zeros(int(M) + 1), max_boxes) for M, st in zip(dev_ecbs.M, dev_ecbs.status) if st == 0]
-        self.K, self.param, self.device = len(self.plans), param, dev_ecbs.device
-        self._keep = (dev_ecbs._worlds,)
-        self._pl = (A.rbp_plan * self.K)(*[p.c_struct() for p in self.plans])
+        self.param, self.device = param, dev_ecbs.device
+        self._missions_of(dev_ecbs, slot_of, max_boxes)
         if opts is not None:
             self.set_solver_opts(opts)
         return self
+
+    def _missions_of(self, dev_ecbs, slot_of, max_boxes):
+        """what from_ecbs and refill share: slot_of, K, and the shapes of the search's missions with status 0, of which `plans` makes empty
+        PlanResults for download() when they are first asked for -- a caller that only reads reports never pays for them"""
+        self.slot_of = slot_of
+        self._N = dev_ecbs.N
+        self._shapes = [(int(M), max_boxes) for M, st in zip(dev_ecbs.M, dev_ecbs.status) if st == 0]
+        self.K = len(self._shapes)
+        self._keep = (dev_ecbs._worlds,)
+        self._plans = self._pl = None
+
+    @property
+    def plans(self):
+        if self._plans is None:
+            import numpy as np
+            self._plans = [PlanResult(np.zeros((self._N, M + 1, 3), np.float32), np.zeros(M + 1), mb) for M, mb in self._shapes]
+            self._pl = (A.rbp_plan * self.K)(*[p.c_struct() for p in self._plans])
+        return self._plans
+
+    @plans.setter
+    def plans(self, plans):
+        self._plans = plans
+
+    @classmethod
+    def reserved(cls, dev_worlds, K, N, M, max_boxes, param: Param, opts=None):
+        """an EMPTY session with room for K missions of N agents, M segments and max_boxes boxes per agent on the device of a DeviceWorlds
+        (rbp_session_create_reserved), to be given its missions by refill().  Until then run, download and the reports raise ValueError.
+        The DeviceWorlds must outlive the session."""
+        if not isinstance(dev_worlds, DeviceWorlds):
+            raise TypeError("Session.reserved takes a DeviceWorlds")
+        if not dev_worlds._h:
+            raise RuntimeError("DeviceWorlds is closed")
+        self = cls.__new__(cls)
+        self._p = param.c_struct()
+        self._h = C.c_void_p()
+        cap = A.rbp_session_capacity(int(K), int(N), int(M), int(max_boxes))
+        rc = lib().rbp_session_create_reserved(C.byref(self._h), dev_worlds._h, C.byref(cap), C.byref(self._p))
+        if rc == A.RBP_ERR_BAD_ARGUMENT:
+            raise ValueError(f"rbp_session_create_reserved rc={rc}: {last_error()}")
+        if rc:
+            raise RuntimeError(f"rbp_session_create_reserved failed rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+        self.param, self.device = param, dev_worlds.device
+        self.K, self.plans, self.slot_of, self._N = 0, [], None, int(N)
+        self._keep = (dev_worlds,)
+        self._pl = (A.rbp_plan * 0)()
+        if opts is not None:
+            self.set_solver_opts(opts)
+        return self
+
+    def refill(self, search, max_boxes=None, stream=None):
+        """replace the session's missions by those a device search solved (rbp_session_refill_from_ecbs): one staged copy and one kernel
+        on `stream`, nothing allocated, nothing synchronised.  `plans`, `K` and `slot_of` are rebuilt as by from_ecbs; the search may be
+        closed once `stream` has been synchronised (run + download or a report do).  A refusal (ValueError) leaves the session as it was."""
+        import numpy as np
+        if not isinstance(search, DeviceEcbs):
+            raise TypeError("Session.refill takes a DeviceEcbs")
+        if not search._h:
+            raise RuntimeError("DeviceEcbs is closed")
+        slot_of = np.zeros(search.K, np.int32)
+        rc = lib().rbp_session_refill_from_ecbs(self._h, search._h, int(max_boxes or 0), A.ptr(slot_of, A.c_int32_p), C.c_void_p(stream or 0))
+        if rc == A.RBP_ERR_BAD_ARGUMENT:
+            raise ValueError(f"rbp_session_refill_from_ecbs rc={rc}: {last_error()}")
+        if rc:
+            raise RuntimeError(f"rbp_session_refill_from_ecbs failed rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+        self._missions_of(search, slot_of, max_boxes)
+
+    @property
+    def capacity(self):
+        """(K, N, M, max_boxes) the session's arena was laid out for (rbp_session_capacity_of): what a refill may bring"""
+        cap = A.rbp_session_capacity()
+        rc = lib().rbp_session_capacity_of(self._h, C.byref(cap))
+        if rc:
+            raise RuntimeError(f"rbp_session_capacity_of rc={rc}: {last_error()}")
+        return (cap.K, cap.N, cap.M, cap.max_boxes)
 
     def set_solver_opts(self, opts=None, **kw):
         """rbp_solver_opts of this session (before its next run): Session.set_solver_opts(qp_schedule=2) or an object from solver_opts()"""
@@ -454,8 +531,11 @@ class Session:
         """copies outputs into the PlanResult objects; returns per-mission status list."""
         import numpy as np
         st = np.zeros(self.K, np.int32)
-        lib().rbp_session_download(self._h, self._pl, A.ptr(st, A.c_int32_p), C.c_void_p(stream or 0))
-        for p, c in zip(self.plans, self._pl):
+        plans = self.plans   # (made now if nobody has asked for them yet)
+        rc = lib().rbp_session_download(self._h, self._pl, A.ptr(st, A.c_int32_p), C.c_void_p(stream or 0))
+        if rc == A.RBP_ERR_BAD_ARGUMENT and self.K == 0:   # (a reserved session before its first refill; a mission's status is never this code)
+            raise ValueError(f"rbp_session_download rc={rc}: {last_error()}")
+        for p, c in zip(plans, self._pl):
             p.sync_from(c)
         return st.tolist()
 
@@ -480,7 +560,7 @@ class Session:
         the kernels; otherwise numpy arrays.  Nothing of the session changes; a mission whose status is not 0 comes back with that
         status, nothing computed and nothing stored."""
         import numpy as np
-        S, N = 1, self.plans[0].N
+        S, N = 1, self._N
         if states or curves:
             S = max([1] + [r.samples for r in self.report(dt, stream)])
         out = (A.rbp_dynamics * self.K)()
@@ -509,7 +589,7 @@ class Session:
         on the session's device, written in place by the kernel; otherwise a numpy array.  The row of a mission that is not computed keeps
         its 1e9.  Nothing of the session changes; a mission whose status is not 0 comes back with that status and nothing computed."""
         import numpy as np
-        N = self.plans[0].N
+        N = self._N
         out = (A.rbp_clearance * self.K)()
         ag, ap = None, None
         if per_agent and device_out:
@@ -537,7 +617,7 @@ class Session:
         array.  The row of a mission that is not computed keeps its 1e9.  Nothing of the session changes; a mission whose status is not 0
         comes back with that status and nothing computed."""
         import numpy as np
-        N = self.plans[0].N
+        N = self._N
         npair = N * (N - 1) // 2
         out = (A.rbp_separation * self.K)()
         pl, pp = None, None
@@ -566,7 +646,7 @@ class Session:
         session's device, written in place by the kernels; otherwise a numpy array.  The row of a mission that is not computed keeps its
         1e9.  Nothing of the session changes; a mission whose status is not 0 comes back with that status and nothing computed."""
         import numpy as np
-        N = self.plans[0].N
+        N = self._N
         out = (A.rbp_swept_clearance * self.K)()
         ag, ap = None, None
         if per_agent and device_out:
@@ -594,7 +674,7 @@ class Session:
         otherwise a numpy array.  The row of a mission that is not computed keeps its zeros.  Nothing of the session changes; a mission
         whose status is not 0 comes back with that status and nothing computed."""
         import numpy as np
-        N = self.plans[0].N
+        N = self._N
         out = (A.rbp_limits * self.K)()
         ag, ap = None, None
         if per_agent and device_out:

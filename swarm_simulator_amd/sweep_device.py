@@ -7,6 +7,9 @@ With --device-ecbs (only with --device-worlds) the searches of all maps run on t
 initial trajectories, and one report line for the whole front-end instead of one per map.
 With --device-handoff (only with --device-ecbs and --mode batched) the searches' plans never come to the host: the session is built from
 them where they lie (planner.ecbs_search_batch, planner.Session.from_ecbs).  The same report lines.
+With --stream B (only with --device-handoff) the maps go through ONE reserved session in batches of B (planner.Session.reserved with room for
+B missions, planner.Session.refill per batch): search, refill, run, report lines, batch after batch, as a planning service would, with no
+session built or released in between.  The same per-map lines in map order for any B.
 With --device-report (only with --device-worlds --mode batched) the safety ratio and flight distance of every map's report line come from ONE
 planner.Session.report() on the resident plans instead of host.validate per downloaded plan: the same line format, the numbers of the
 rule the device and host.report share (csrc/common/report_rules.h; they differ from host.validate's by rounding).  Without --csv nothing
@@ -29,7 +32,7 @@ line per map with certified intervals for the largest velocity and acceleration,
 and how many (agent, segment) items are uncertified, violating and refined (csrc/common/limits_rules.h): whether the plan keeps max_vel and
 max_acc between the samples.
 
-usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff]] [--device-report] [--device-dynamics] [--device-clearance] [--device-separation] [--device-swept-clearance] [--device-limits]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
+usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff [--stream B]]] [--device-report] [--device-dynamics] [--device-clearance] [--device-separation] [--device-swept-clearance] [--device-limits]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
        [--batch-size 4] [--iteration 1] [--joint] [--csv DIR]
 """
 import argparse
@@ -48,6 +51,8 @@ def main(argv=None):
                     "with an error where the host search would go on")
     ap.add_argument("--device-handoff", action="store_true", help="with --device-worlds --device-ecbs --mode batched: the session is built on the device from the "
                     "search's resident results, no initial trajectory passes through the host")
+    ap.add_argument("--stream", type=int, default=0, metavar="B", help="with --device-handoff: the maps go through one reserved session in batches of B "
+                    "(planner.Session.reserved, planner.Session.refill), nothing is allocated between the batches")
     ap.add_argument("--device-report", action="store_true", help="with --device-worlds --mode batched: safety ratio and flight distance of all maps from one "
                     "report call on the device (planner.Session.report); without --csv the coefficients are not downloaded")
     ap.add_argument("--device-dynamics", action="store_true", help="with --device-worlds --mode batched: one more line per map with both limit peak ratios and "
@@ -87,6 +92,10 @@ def main(argv=None):
         ap.error("--device-ecbs needs --device-worlds")
     if args.device_handoff and not (args.device_ecbs and args.mode == "batched"):
         ap.error("--device-handoff needs --device-worlds --device-ecbs --mode batched")
+    if args.stream and not args.device_handoff:
+        ap.error("--stream needs --device-worlds --device-ecbs --device-handoff --mode batched")
+    if args.stream < 0:
+        ap.error("--stream takes a positive batch size")
     if not args.device_worlds:
         return test_all.main(argv)
     if rest:
@@ -149,6 +158,8 @@ def main(argv=None):
 
 def handoff_sweep(args, worlds, maps, mission, param):
     """--device-handoff: search, session and plan without an initial trajectory on the host; the report lines of the batched mode"""
+    if args.stream:
+        return stream_sweep(args, worlds, maps, mission, param)
     t0 = time.perf_counter()
     search = planner.ecbs_search_batch(worlds, list(range(len(maps))), [mission] * len(maps), param)
     print(f"Initial Trajectory Planner runtime, {len(maps)} maps in one device search: {time.perf_counter() - t0:.6f}")
@@ -164,9 +175,40 @@ def handoff_sweep(args, worlds, maps, mission, param):
     return run_and_report(args, sess, maps, sess.plans, mission, param)
 
 
-def run_and_report(args, sess, maps, plans, mission, param):
+def stream_sweep(args, worlds, maps, mission, param):
+    """--stream B: one reserved session with room for B missions; per batch of B maps a search, a refill, a run and the report lines"""
+    B, sess = args.stream, None
+    try:
+        for b0 in range(0, len(maps), B):
+            batch = maps[b0:b0 + B]
+            t0 = time.perf_counter()
+            search = planner.ecbs_search_batch(worlds, list(range(b0, b0 + len(batch))), [mission] * len(batch), param)
+            try:
+                print(f"Initial Trajectory Planner runtime, {len(batch)} maps in one device search: {time.perf_counter() - t0:.6f}")
+                for i, st in zip(batch, search.status):
+                    if st:  # (3: a capacity of the device search; the host search is the caller's choice, not a fallback)
+                        print(f"[ERROR] map{i}: {host.ECBS_ERROR_TEXT.get(int(st), 'ECBSPlanner: device search capacity exceeded (status 3)')}")
+                        return -1
+                for i in batch:
+                    print(f"Map: map{i}.bt")
+                if sess is None:
+                    sess = planner.Session.reserved(worlds, B, mission.qn, search.max_M, search.max_M, param)
+                sess.refill(search)
+                rc = run_and_report(args, sess, batch, sess.plans, mission, param, close=False)   # (ends synchronised: the search may go)
+            finally:
+                search.close()
+            if rc:
+                return rc
+        return 0
+    finally:
+        if sess is not None:
+            sess.close()
+
+
+def run_and_report(args, sess, maps, plans, mission, param, close=True):
     """the batched mode's run of a session and its report lines.  --device-report: the lines' two signals come from one Session.report(),
-    and without --csv each line's cost, time scale and makespan from the session's scalars and that record instead of a download."""
+    and without --csv each line's cost, time scale and makespan from the session's scalars and that record instead of a download.
+    close=False: the session is the caller's to refill."""
     download = not args.device_report or bool(args.csv)
     t0 = time.perf_counter()
     sess.run()
@@ -184,7 +226,8 @@ def run_and_report(args, sess, maps, plans, mission, param):
         sc = sess.scalars(n=2)   # (kernels/rbp_dev.h: SC_TIME_SCALE, SC_TOTAL_COST -- read as rbp_session_download reads them)
         status = [r.status for r in records]
         plans = [SimpleNamespace(total_cost=float(c), time_scale=float(ts) if ts > 0 else 1.0, T=[r.end_time]) for (ts, c), r in zip(sc, records)]
-    sess.close()
+    if close:
+        sess.close()
     for i, p, st, rec, pk, cl, sp, sw, lm in zip(maps, plans, status, records, peaks, clear, separ, swept, limit):
         if st:
             print(f"[ERROR] map{i}: status {st}")
