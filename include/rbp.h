@@ -483,6 +483,40 @@ int  rbp_session_create_reserved(rbp_session** out, const rbp_dev_worlds* ws, co
 int  rbp_session_capacity_of(const rbp_session* s, rbp_session_capacity* out);
 int  rbp_session_refill_from_ecbs(rbp_session* s, const rbp_dev_ecbs* e, int32_t max_boxes, int32_t* slot_of, void* stream);
 
+/* ---- ... refilled from a caller's own plans, staged in one copy -------------------------------------------
+ * The other source of a refill: host rbp_plans from any front-end, with their missions and worlds, as rbp_session_create takes them.
+ * rbp_session_refill_from_plans replaces the session's missions by the K given ones, which become slots 0 .. K-1.  It reads
+ *   plans[k].{N, M, max_boxes, T, init_traj}, all five arrays of missions[k] and worlds[k]; corridor arrays in a plan are ignored, and the
+ *   session has no corridor inputs afterwards, as after the other refill.  worlds[k].dist must be a DEVICE pointer on the session's device
+ *   -- a grid of a rbp_dev_worlds or any device allocation of that layout -- which is referenced in place and stays the caller's until
+ *   the next refill or the session's end; a host grid is refused, a refill uploads no grid.  The session is then as a fresh session of
+ *   rbp_session_create of those missions: after a run every output has that session's bits.
+ *   The host packs the missions tightly into a pinned staging block, as many consecutive missions as fit (per mission M, max_boxes, the
+ *   world descriptor, T, init_traj and the 25 N doubles of the mission arrays); ONE asynchronous copy per round sends the block up and ONE
+ *   kernel (kernels/handoff.hip session_refill_plans_kernel) on `stream` writes the round's slots and clears what
+ *   rbp_session_refill_from_ecbs clears.  A batch that does not fit the block goes in several rounds on `stream`; the host waits only on
+ *   the event behind the previous copy out of the block before it packs the next round -- for a one-round refill that is the previous
+ *   refill's copy.  After the last round one asynchronous clear covers the K blocks of the QP workspace if one has been reserved.
+ *   Nothing is allocated once the block exists, and nothing else synchronises.  The host arrays may be released on return (they are
+ *   copied into the block); the stream rule of rbp_session_refill_from_ecbs holds.  A session of any constructor is refillable within its
+ *   own capacity.
+ *   RBP_ERR_BAD_ARGUMENT, with a message that names the mission and the field and the session left exactly as it was: a null session,
+ *   K < 1, null worlds / missions / plans (before a device is looked for); a sharded session; K above the capacity's; a plan's or
+ *   mission's N other than the capacity's; M outside [2, capacity M]; max_boxes outside [1, capacity max_boxes]; a null T, init_traj,
+ *   start, goal, radius, max_vel, max_acc or dist; a grid that is not device memory of the session's device; grids whose occupancy mask
+ *   needs more LDS than the device has (as rbp_session_refill_from_ecbs checks it).
+ * rbp_plan_stage_bytes is a pure function (it looks for no device): the bytes K missions of the capacity's shape (N, M) occupy in the
+ *   staging block.  A mission of a smaller M occupies less.  A null or non-positive capacity, K < 1 or null bytes: RBP_ERR_BAD_ARGUMENT.
+ * rbp_session_reserve_plan_stage reserves the pinned block, its device twin and its event with `bytes` of room;
+ *   0 means min(rbp_plan_stage_bytes(capacity, capacity K), RBP_REFILL_STAGE_BYTES).  Less than one mission of the capacity's shape, or a
+ *   second call with another size, is RBP_ERR_BAD_ARGUMENT and leaves the block as it is.  The call is optional: the first
+ *   rbp_session_refill_from_plans makes it with 0 itself; a caller who reserves up front pays no allocation even in the first refill. */
+#define RBP_REFILL_STAGE_BYTES (64u << 20)
+int  rbp_plan_stage_bytes(const rbp_session_capacity* cap, int32_t K, size_t* bytes);
+int  rbp_session_reserve_plan_stage(rbp_session* s, size_t bytes);
+int  rbp_session_refill_from_plans(rbp_session* s, int32_t K, const rbp_world* worlds, const rbp_mission* missions,
+                                   const rbp_plan* plans, void* stream);
+
 /* ---- a mission's acceptance signals on the device ---------------------------
  * The two numbers the reference prints per plan (rbp_publisher.hpp:685-695, 769-798): the smallest safety ratio -- downwash-scaled
  * distance of two agents over the sum of their radii, should be >= 1 -- over all pairs at every sample t = j * dt, j < floor(T[M] / dt),

@@ -167,6 +167,7 @@ class rbp_limits(C.Structure):
 
 
 RBP_SIZEOF_SESSION_CAPACITY = 14
+RBP_REFILL_STAGE_BYTES = 64 << 20   # the most rbp_session_reserve_plan_stage reserves when it is given 0
 
 
 class rbp_session_capacity(C.Structure):

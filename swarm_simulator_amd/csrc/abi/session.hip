@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "../common/plan_stage.h"
 #include "../kernels/jqp.h"
 #include "../kernels/rbp_dev.h"
 
@@ -125,6 +126,12 @@ struct rbp_session {
     char *stage_h = nullptr, *stage_d = nullptr;
     hipEvent_t stage_ev = nullptr;
     bool stage_busy = false;  // stage_ev has been recorded
+    // rbp_session_refill_from_plans: the staging block of a caller's plans (common/plan_stage.h: pinned, pstage_bytes of room for one round),
+    // its device twin and the event behind the last copy out of it (rbp_session_reserve_plan_stage)
+    char *pstage_h = nullptr, *pstage_d = nullptr;
+    size_t pstage_bytes = 0;
+    hipEvent_t pstage_ev = nullptr;
+    bool pstage_busy = false;  // pstage_ev has been recorded
 };
 
 // what run, download and the reports answer for a reserved session that has not been refilled
@@ -714,6 +721,136 @@ int rbp_session_refill_from_ecbs(rbp_session* s, const rbp_dev_ecbs* e, int32_t 
     return RBP_OK;
 }
 
+// ---- the other source of a refill: a caller's own plans, staged (common/plan_stage.h) ------------------------------------------------
+static int check_capacity(const char* who, const rbp_session_capacity* cap) {
+    if (!cap) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "null capacity");
+    if (cap->K < 1 || cap->N < 1 || cap->M < 2 || cap->max_boxes < 1) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "need K >= 1, N >= 1, M >= 2, max_boxes >= 1");
+    return RBP_OK;
+}
+
+int rbp_plan_stage_bytes(const rbp_session_capacity* cap, int32_t K, size_t* bytes) {
+    const char* who = "rbp_plan_stage_bytes: ";
+    if (bytes) *bytes = 0;
+    if (int rc = check_capacity(who, cap)) return rc;
+    if (K < 1 || !bytes) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "need K >= 1 and bytes");
+    *bytes = plan_stage::mission_bytes(cap->N, cap->M) * (size_t)K;
+    return RBP_OK;
+}
+
+// the block a session reserves for `bytes` = 0: its capacity's missions in one round, up to RBP_REFILL_STAGE_BYTES (one mission at the least)
+static size_t default_plan_stage_bytes(const rbp_session* s) {
+    const size_t one = plan_stage::mission_bytes(s->cap.N, s->cap.M);
+    return std::max(one, std::min(one * (size_t)s->cap.K, (size_t)RBP_REFILL_STAGE_BYTES));
+}
+
+int rbp_session_reserve_plan_stage(rbp_session* s, size_t bytes) {
+    const char* who = "rbp_session_reserve_plan_stage: ";
+    if (!s) return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "null session");
+    const size_t one = plan_stage::mission_bytes(s->cap.N, s->cap.M), want = bytes ? bytes : default_plan_stage_bytes(s);
+    if (want < one)
+        return fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + std::to_string(want) + " bytes are less than one mission of the session's capacity takes (" + std::to_string(one) + ")");
+    if (s->pstage_h)
+        return want == s->pstage_bytes ? RBP_OK
+                                       : fail(RBP_ERR_BAD_ARGUMENT, std::string(who) + "the block has been reserved with " + std::to_string(s->pstage_bytes) + " bytes, not " + std::to_string(want));
+    HIP_TRY(hipSetDevice(s->device));
+    char *h = nullptr, *d = nullptr;
+    hipEvent_t ev = nullptr;
+    hipError_t e = hipHostMalloc((void**)&h, want, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&d, want);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) {  // all of the block or nothing
+        if (h) (void)hipHostFree(h);
+        if (d) (void)hipFree(d);
+        return fail(RBP_ERR_HIP, std::string(who) + std::to_string(want) + " bytes of pinned and device memory: " + hipGetErrorString(e));
+    }
+    s->pstage_h = h, s->pstage_d = d, s->pstage_ev = ev, s->pstage_bytes = want, s->pstage_busy = false;
+    return RBP_OK;
+}
+
+// K of a caller's missions into the slots 0 .. K-1 of a session that exists.  Every check comes before anything of the session changes;
+// then the missions go up in rounds of the staging block: pack, one asynchronous copy, one launch of session_refill_plans_kernel.
+int rbp_session_refill_from_plans(rbp_session* s, int32_t K, const rbp_world* worlds, const rbp_mission* missions, const rbp_plan* plans, void* stream) {
+    const std::string who = "rbp_session_refill_from_plans: ";
+    if (!s) return fail(RBP_ERR_BAD_ARGUMENT, who + "null session");
+    if (K < 1) return fail(RBP_ERR_BAD_ARGUMENT, who + "need K >= 1");
+    if (!worlds || !missions || !plans) return fail(RBP_ERR_BAD_ARGUMENT, who + "need worlds, missions and plans");
+    if (int jrc = join_worker(s)) return jrc;  // (a failed asynchronous solve: its error, and the session stays as it is)
+    if (s->shard.nranks == 2) return fail(RBP_ERR_BAD_ARGUMENT, who + "a session sharded over two ranks (rbp_session_shard_joint) is not refilled");
+    const rbp_session_capacity& cap = s->cap;
+    if (K > cap.K) return fail(RBP_ERR_BAD_ARGUMENT, who + std::to_string(K) + " missions, the session's capacity is " + std::to_string(cap.K));
+    auto refuse = [&](int k, const std::string& what) { return fail(RBP_ERR_BAD_ARGUMENT, who + "mission " + std::to_string(k) + ": " + what); };
+    for (int k = 0; k < K; ++k) {
+        const rbp_plan& p = plans[k];
+        const rbp_mission& m = missions[k];
+        if (p.N != cap.N) return refuse(k, "plan.N = " + std::to_string(p.N) + ", the session's missions have " + std::to_string(cap.N) + " agents");
+        if (m.N != cap.N) return refuse(k, "mission.N = " + std::to_string(m.N) + ", the session's missions have " + std::to_string(cap.N) + " agents");
+        if (p.M < 2 || p.M > cap.M) return refuse(k, "plan.M = " + std::to_string(p.M) + " outside [2, the session's stride " + std::to_string(cap.M) + "]");
+        if (p.max_boxes < 1 || p.max_boxes > cap.max_boxes)
+            return refuse(k, "plan.max_boxes = " + std::to_string(p.max_boxes) + " outside [1, the session's stride " + std::to_string(cap.max_boxes) + "]");
+        if (!p.T) return refuse(k, "plan.T is null");
+        if (!p.init_traj) return refuse(k, "plan.init_traj is null");
+        if (!m.start) return refuse(k, "mission.start is null");
+        if (!m.goal) return refuse(k, "mission.goal is null");
+        if (!m.radius) return refuse(k, "mission.radius is null");
+        if (!m.max_vel) return refuse(k, "mission.max_vel is null");
+        if (!m.max_acc) return refuse(k, "mission.max_acc is null");
+        if (!worlds[k].dist) return refuse(k, "world.dist is null");
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    for (int k = 0; k < K; ++k) {  // a refill uploads no grid: every grid lies on the session's device already
+        if (k > 0 && worlds[k].dist == worlds[k - 1].dist) continue;
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, worlds[k].dist) != hipSuccess) {  // a pointer the runtime does not know: host (the error is sticky)
+            (void)hipGetLastError();
+            return refuse(k, "world.dist is a host pointer; a refill takes grids that lie on the device (rbp_dev_worlds)");
+        }
+        if (at.type != hipMemoryTypeDevice) return refuse(k, "world.dist is a host pointer; a refill takes grids that lie on the device (rbp_dev_worlds)");
+        if (at.device != s->device) return refuse(k, "world.dist lies on device " + std::to_string(at.device) + ", the session on device " + std::to_string(s->device));
+    }
+    DevSession nd = s->d;  // the occupancy mask's words are those of the new missions' worlds, as in a fresh session of them
+    nd.K = K, nd.sfc_mask_words = session_mask_words(worlds, K);
+    if (corridor_lds_bytes(nd) > (size_t)std::max(s->lds_max, 64 * 1024))
+        return fail(RBP_ERR_BAD_ARGUMENT, who + "Corridor: " + std::to_string(corridor_lds_bytes(nd)) + " bytes of LDS per workgroup for the new missions' grids exceed the device's " +
+                                              std::to_string(s->lds_max));
+    if (!s->pstage_h)
+        if (int rc = rbp_session_reserve_plan_stage(s, 0)) return rc;  // (not reserved up front: the first refill from plans)
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int> Mk(K), MBk(K);
+    std::vector<DevWorld> wd(K);
+    for (int k = 0; k < K; ++k) {
+        Mk[k] = plans[k].M, MBk[k] = plans[k].max_boxes;
+        DevWorld& w = wd[k];
+        for (int a = 0; a < 3; ++a) w.dim[a] = worlds[k].dim[a], w.key_min[a] = worlds[k].key_min[a];
+        w.res = worlds[k].res;
+        w.dist = worlds[k].dist;  // referenced in place: the caller keeps it alive until the next refill (include/rbp.h)
+    }
+    std::vector<plan_stage::Source> src;
+    for (int j0 = 0; j0 < K;) {
+        const int j1 = plan_stage::round_end(Mk.data(), K, cap.N, j0, s->pstage_bytes);  // (> j0: the block holds a mission of the capacity's shape)
+        if (j1 <= j0) return fail(RBP_ERR_HIP, who + "a mission does not fit the staging block (internal sizing error)");
+        src.resize(j1 - j0);
+        for (int j = j0; j < j1; ++j)
+            src[j - j0] = plan_stage::Source{Mk[j], MBk[j], &wd[j], plans[j].T, plans[j].init_traj, missions[j].start, missions[j].goal, missions[j].radius,
+                                             missions[j].max_vel, missions[j].max_acc};
+        if (s->pstage_busy) HIP_TRY(hipEventSynchronize(s->pstage_ev));  // the previous copy has left the block; stream order protects its twin
+        const size_t bytes = plan_stage::pack_round(s->pstage_h, src.data(), j1 - j0, cap.N);
+        HIP_TRY(hipMemcpyAsync(s->pstage_d, s->pstage_h, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(s->pstage_ev, st));
+        s->pstage_busy = true;
+        if (int rc = launch_session_refill_plans(nd, j0, j1 - j0, s->pstage_d, 8 * s->n_cu, st)) return rc;
+        j0 = j1;
+    }
+    // (the QP workspace blocks of the refilled slots: as rbp_session_refill_from_ecbs clears them)
+    if (s->qp_ws) HIP_TRY(hipMemsetAsync(s->qp_ws, 0, s->qp_ws_per_mission * (size_t)K, st));
+    s->d = nd;
+    s->Mk = Mk, s->MBk = MBk;
+    s->worlds_h = wd;
+    s->have_corridor_inputs = false;
+    s->last_stages = 0;
+    s->empty = false;
+    return RBP_OK;
+}
+
 // T, the SFC end times and the RSFC times are never rescaled on the device (timescale_kernel only records the factor and
 // rescales the coefficients; rbp_session_download applies it to its host copies), so a session can be re-run as it is:
 // reset clears the per-run status / diagnostics and puts back corridor inputs the caller uploaded, in case a CORRIDOR
@@ -1296,6 +1433,12 @@ void rbp_session_destroy(rbp_session* s) {
         if (s->stage_ev) (void)hipEventDestroy(s->stage_ev);
         if (s->stage_h) (void)hipHostFree(s->stage_h);
         if (s->stage_d) (void)hipFree(s->stage_d);
+    }
+    if (s->pstage_h || s->pstage_d || s->pstage_ev) {
+        (void)hipSetDevice(s->device);
+        if (s->pstage_ev) (void)hipEventDestroy(s->pstage_ev);
+        if (s->pstage_h) (void)hipHostFree(s->pstage_h);
+        if (s->pstage_d) (void)hipFree(s->pstage_d);
     }
     if (s->ctx) {
         s->ctx->busy = false;  // the arena (and the QP workspace) stay with the context

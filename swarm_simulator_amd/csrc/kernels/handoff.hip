@@ -9,6 +9,8 @@
 //   ecbs_mission_gather_kernel  start / goal / radius / max_vel / max_acc of the chosen missions into the session's [n][N][...] arrays.
 //   session_refill_kernel       both of the above for the slots 0 .. n-1 of a session that already exists (rbp_session_refill_from_ecbs), with the
 //                               slots' descriptors and the clears a fresh arena would have provided, in one launch.
+//   session_refill_plans_kernel the same for the slots [j0, j0 + n) from a caller's own plans (rbp_session_refill_from_plans), which the host
+//                               packed into a staging block: layout and element rules are common/plan_stage.h.
 // All are one element per lane, consecutive lanes on consecutive elements of a row: plain vector loads and stores, no LDS, no atomics.  The
 // element bodies (plan_time_element, plan_traj_element, mission_gather_element) are stated once and called by the kernels that need them.
 // Every value of the first is a rule of common/ecbs_rules.h (plan_time, plan_waypoint) -- the text the host's write_plan loops over -- and
@@ -18,6 +20,7 @@
 #include <string>
 
 #include "common/ecbs_rules.h"
+#include "common/plan_stage.h"
 
 namespace {
 
@@ -118,20 +121,60 @@ __global__ __launch_bounds__(HANDOFF_THREADS) void ecbs_mission_gather_kernel(Mi
 constexpr int REFILL_THREADS = 256;
 constexpr int REFILL_Z64 = 8;  // ranges of 8-byte words cleared from their base: scalars, counters, qp_cost, sfc_box, sfc_time, rsfc_time, ctrl, coef
 
+// the clears a fresh arena would hold as zeros, for a run of consecutive slots: every array's range starts at its first slot
+struct SlotClears {
+    int* sfc_count;
+    float* rsfc_normal;
+    unsigned long long* z64[REFILL_Z64];
+    long long n64[REFILL_Z64];
+    long long n_count, n_normal;
+};
+
 struct SessionRefill {
     PlanWrite w;      // n slots, compact, stride = the session's M + 1; src and Mj are the STAGED lists
     MissionGather g;  // (src: the staged list)
     const unsigned long long* st_worlds;  // staged descriptors, WORLD_WORDS words each
     const int* st_MBk;
     unsigned long long* worlds;
-    int *Mk, *MBk, *status, *qp_order, *sfc_count;
-    float* rsfc_normal;
-    unsigned long long* z64[REFILL_Z64];
-    long long n64[REFILL_Z64];
-    long long n_traj, n_T, n_gather, n_desc, n_count, n_normal, total;
+    int *Mk, *MBk, *status, *qp_order;
+    SlotClears c;
+    long long n_traj, n_T, n_gather, n_desc, total;
 };
 constexpr int WORLD_WORDS = (int)(sizeof(DevWorld) / sizeof(unsigned long long));
 static_assert(sizeof(DevWorld) % sizeof(unsigned long long) == 0, "a descriptor is copied in 8-byte words");
+
+// element i (< clear_elements) of the clears: sfc_count, the floats of rsfc_normal, then the 8-byte ranges
+__device__ __forceinline__ void slot_clear_element(const SlotClears& c, long long i) {
+    if (i < c.n_count) {
+        c.sfc_count[i] = 0;
+        return;
+    }
+    i -= c.n_count;
+    if (i < c.n_normal) {
+        c.rsfc_normal[i] = 0.0f;
+        return;
+    }
+    i -= c.n_normal;
+#pragma unroll
+    for (int z = 0; z < REFILL_Z64; ++z) {
+        if (i >= 0 && i < c.n64[z]) c.z64[z][i] = 0ull;
+        i -= c.n64[z];
+    }
+}
+
+// the clears of the slots [j0, j0 + n) of a session with the pointers and strides of `d`; returns their element count
+long long slot_clears(SlotClears& c, const DevSession& d, int j0, int n) {
+    const long long N = d.N, M = d.M, MB = d.max_boxes, oq = 6LL * M;
+    c.sfc_count = d.sfc_count + N * j0, c.n_count = N * n;
+    c.rsfc_normal = d.rsfc_normal + 3LL * d.npair * M * j0, c.n_normal = 3LL * d.npair * M * n;
+    long long total = c.n_count + c.n_normal;
+    auto z64 = [&](int z, void* p, long long per_slot) {
+        c.z64[z] = static_cast<unsigned long long*>(p) + per_slot * j0, c.n64[z] = per_slot * n, total += c.n64[z];
+    };
+    z64(0, d.scalars, SC_N), z64(1, d.counters, CT_N), z64(2, d.qp_cost, 1), z64(3, d.sfc_box, 6 * N * MB), z64(4, d.sfc_time, N * MB);
+    z64(5, d.rsfc_time, M), z64(6, d.ctrl, 3 * N * oq), z64(7, d.coef, 3 * N * oq);
+    return total;
+}
 
 // One flat index space, walked by a grid-stride loop, one element per lane and step: the floats of init_traj, the doubles of T, the
 // gathered doubles, the descriptors' words with each slot's Mk / MBk / status / qp_order, sfc_count, the floats of rsfc_normal, and the
@@ -165,21 +208,59 @@ __global__ __launch_bounds__(REFILL_THREADS) void session_refill_kernel(SessionR
             continue;
         }
         i -= r.n_desc;
-        if (i < r.n_count) {
-            r.sfc_count[i] = 0;
+        slot_clear_element(r.c, i);
+    }
+}
+
+// ---- the same from a caller's plans, staged (common/plan_stage.h) ------------------------------------------------------------------------
+static_assert(plan_stage::WORLD_WORDS == WORLD_WORDS, "common/plan_stage.h stages a DevWorld word by word");
+
+struct SessionRefillPlans {
+    const char* block;     // the device twin of the staging block, holding one round
+    plan_stage::Round R;   // the slots [j0, j0 + n) and the session's N and stride M + 1
+    MissionGather g;       // n missions from the round's tables (src: its list 0 .. n-1) into the slots from j0
+    float* init_traj;      // the session's arrays, from slot 0 (the element rules give indices from there)
+    double* T;
+    unsigned long long* worlds;  // ... and from slot j0
+    int *Mk, *MBk, *status, *qp_order;
+    SlotClears c;          // of the slots [j0, j0 + n)
+    long long n_traj, n_T, n_gather, n_desc, total;
+};
+
+// session_refill_kernel's index space and walk.  init_traj and T are the two element rules of common/plan_stage.h, the 25 N doubles go
+// through mission_gather_element, the descriptors' words come out of the round's entries, the clears are slot_clear_element.  Every
+// index derives from the round's tables, which the host packed from checked shapes.
+__global__ __launch_bounds__(REFILL_THREADS) void session_refill_plans_kernel(SessionRefillPlans r) {
+    const long long step = (long long)gridDim.x * REFILL_THREADS;
+    for (long long t = (long long)blockIdx.x * REFILL_THREADS + threadIdx.x; t < r.total; t += step) {
+        long long i = t, dst;
+        if (i < r.n_traj) {
+            const float v = plan_stage::traj_element(r.block, r.R, i, &dst);
+            r.init_traj[dst] = v;
             continue;
         }
-        i -= r.n_count;
-        if (i < r.n_normal) {
-            r.rsfc_normal[i] = 0.0f;
+        i -= r.n_traj;
+        if (i < r.n_T) {
+            const double v = plan_stage::time_element(r.block, r.R, i, &dst);
+            r.T[dst] = v;
             continue;
         }
-        i -= r.n_normal;
-#pragma unroll
-        for (int z = 0; z < REFILL_Z64; ++z) {
-            if (i >= 0 && i < r.n64[z]) r.z64[z][i] = 0ull;
-            i -= r.n64[z];
+        i -= r.n_T;
+        if (i < r.n_gather) {
+            const int per = 25 * r.g.N, j = (int)(i / per);
+            mission_gather_element(r.g, j, (int)(i - (long long)j * per));
+            continue;
         }
+        i -= r.n_gather;
+        if (i < r.n_desc) {
+            const int j = (int)(i / WORLD_WORDS), w = (int)(i - (long long)j * WORLD_WORDS);
+            const plan_stage::Entry& e = plan_stage::entry(r.block, j);
+            r.worlds[i] = e.world[w];
+            if (w == 0) r.Mk[j] = e.Mk, r.MBk[j] = e.MBk, r.status[j] = 0, r.qp_order[j] = 0;
+            continue;
+        }
+        i -= r.n_desc;
+        slot_clear_element(r.c, i);
     }
 }
 
@@ -221,7 +302,7 @@ int launch_ecbs_mission_gather(const rbp_dev_ecbs& e, int n, const int* src, dou
 
 int launch_session_refill(const rbp_dev_ecbs& e, const DevSession& d, int n, const char* staged, int capacity_K, int max_blocks, hipStream_t st) {
     const RefillStage L(capacity_K);
-    const int N = d.N, M = d.M, MB = d.max_boxes, PS = M + 1;
+    const int N = d.N, PS = d.M + 1;
     const long long slot = 3LL * N * PS;
     if (n <= 0 || n > capacity_K || slot > 0x7fffffffLL)
         return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "session_refill_kernel: nothing to refill, more missions than the capacity, or more than 2^31 floats per mission");
@@ -242,17 +323,37 @@ int launch_session_refill(const rbp_dev_ecbs& e, const DevSession& d, int n, con
     r.st_worlds = reinterpret_cast<const unsigned long long*>(staged + L.worlds());
     r.st_MBk = reinterpret_cast<const int*>(staged + L.MBk());
     r.worlds = reinterpret_cast<unsigned long long*>(const_cast<DevWorld*>(d.worlds));
-    r.Mk = const_cast<int*>(d.Mk), r.MBk = const_cast<int*>(d.MBk), r.status = d.status, r.qp_order = d.qp_order, r.sfc_count = d.sfc_count;
-    r.rsfc_normal = d.rsfc_normal;
-    const long long oq = 6LL * M;
-    auto z64 = [&](int z, void* p, long long per_slot) { r.z64[z] = static_cast<unsigned long long*>(p), r.n64[z] = per_slot * n; };
-    z64(0, d.scalars, SC_N), z64(1, d.counters, CT_N), z64(2, d.qp_cost, 1), z64(3, d.sfc_box, 6LL * N * MB), z64(4, d.sfc_time, (long long)N * MB);
-    z64(5, d.rsfc_time, M), z64(6, d.ctrl, 3LL * N * oq), z64(7, d.coef, 3LL * N * oq);
+    r.Mk = const_cast<int*>(d.Mk), r.MBk = const_cast<int*>(d.MBk), r.status = d.status, r.qp_order = d.qp_order;
     r.n_traj = slot * n, r.n_T = (long long)PS * n, r.n_gather = 25LL * N * n, r.n_desc = (long long)WORLD_WORDS * n;
-    r.n_count = (long long)N * n, r.n_normal = 3LL * d.npair * M * n;
-    r.total = r.n_traj + r.n_T + r.n_gather + r.n_desc + r.n_count + r.n_normal;
-    for (int z = 0; z < REFILL_Z64; ++z) r.total += r.n64[z];
+    r.total = r.n_traj + r.n_T + r.n_gather + r.n_desc + slot_clears(r.c, d, 0, n);
     const long long blocks = std::min<long long>((r.total + REFILL_THREADS - 1) / REFILL_THREADS, std::max(max_blocks, 1));
     hipLaunchKernelGGL(session_refill_kernel, dim3((unsigned)blocks), dim3(REFILL_THREADS), 0, st, r);
     return launched("session_refill_kernel");
+}
+
+int launch_session_refill_plans(const DevSession& d, int j0, int n, const char* staged, int max_blocks, hipStream_t st) {
+    namespace ps = plan_stage;
+    const int N = d.N, PS = d.M + 1;
+    const long long slot = 3LL * N * PS;
+    if (j0 < 0 || n <= 0 || slot > 0x7fffffffLL)
+        return rbp_set_error(RBP_ERR_BAD_ARGUMENT, "session_refill_plans_kernel: nothing to refill, or more than 2^31 floats per mission");
+    SessionRefillPlans r{};
+    r.block = staged;
+    r.R = ps::Round{j0, n, N, PS};
+    auto doubles = [&](size_t off) { return reinterpret_cast<const double*>(staged + off); };
+    MissionGather& g = r.g;
+    g.n = n, g.N = N, g.src = reinterpret_cast<const int*>(staged + ps::off_src(n));
+    g.start = doubles(ps::off_start(n)), g.goal = doubles(ps::off_goal(n, N)), g.radius = doubles(ps::off_radius(n, N));
+    g.max_vel = doubles(ps::off_max_vel(n, N)), g.max_acc = doubles(ps::off_max_acc(n, N));
+    const size_t a0 = (size_t)j0 * N;  // the first agent of slot j0
+    g.d_start = const_cast<double*>(d.start) + a0 * 9, g.d_goal = const_cast<double*>(d.goal) + a0 * 9, g.d_radius = const_cast<double*>(d.radius) + a0;
+    g.d_max_vel = const_cast<double*>(d.max_vel) + a0 * 3, g.d_max_acc = const_cast<double*>(d.max_acc) + a0 * 3;
+    r.init_traj = const_cast<float*>(d.init_traj), r.T = d.T;
+    r.worlds = reinterpret_cast<unsigned long long*>(const_cast<DevWorld*>(d.worlds) + j0);
+    r.Mk = const_cast<int*>(d.Mk) + j0, r.MBk = const_cast<int*>(d.MBk) + j0, r.status = d.status + j0, r.qp_order = d.qp_order + j0;
+    r.n_traj = ps::traj_elements(r.R), r.n_T = ps::time_elements(r.R), r.n_gather = 25LL * N * n, r.n_desc = (long long)WORLD_WORDS * n;
+    r.total = r.n_traj + r.n_T + r.n_gather + r.n_desc + slot_clears(r.c, d, j0, n);
+    const long long blocks = std::min<long long>((r.total + REFILL_THREADS - 1) / REFILL_THREADS, std::max(max_blocks, 1));
+    hipLaunchKernelGGL(session_refill_plans_kernel, dim3((unsigned)blocks), dim3(REFILL_THREADS), 0, st, r);
+    return launched("session_refill_plans_kernel");
 }

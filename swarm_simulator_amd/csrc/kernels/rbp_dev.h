@@ -218,6 +218,11 @@ struct RefillStage {
     size_t bytes() const { return MBk() + sizeof(int) * (size_t)K; }
 };
 int launch_session_refill(const rbp_dev_ecbs& e, const DevSession& d, int n, const char* staged, int capacity_K, int max_blocks, hipStream_t st);
+// kernels/handoff.hip: a session's slots [j0, j0 + n) refilled from ONE ROUND of a caller's plans (rbp_session_refill_from_plans) in one
+// launch.  `staged` is the device twin of the plans' staging block holding that round as common/plan_stage.h lays it out (pack_round);
+// session_refill_plans_kernel writes init_traj and T by that header's element rules, the mission arrays, the descriptors with Mk / MBk and
+// the clears of session_refill_kernel, for those slots only.  `d` holds the session's pointers and STRIDES.
+int launch_session_refill_plans(const DevSession& d, int j0, int n, const char* staged, int max_blocks, hipStream_t st);
 // kernels/edt.hip: the device a set of worlds lies on
 int dev_worlds_device(const rbp_dev_worlds* ws);
 

@@ -162,6 +162,9 @@ def lib():
             L.rbp_session_create_reserved.argtypes = [P(C.c_void_p), C.c_void_p, P(A.rbp_session_capacity), P(A.rbp_param)]
             L.rbp_session_capacity_of.argtypes = [C.c_void_p, P(A.rbp_session_capacity)]
             L.rbp_session_refill_from_ecbs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, A.c_int32_p, C.c_void_p]
+            L.rbp_plan_stage_bytes.argtypes = [P(A.rbp_session_capacity), C.c_int32, P(C.c_size_t)]
+            L.rbp_session_reserve_plan_stage.argtypes = [C.c_void_p, C.c_size_t]
+            L.rbp_session_refill_from_plans.argtypes = [C.c_void_p, C.c_int32, P(A.rbp_world), P(A.rbp_mission), P(A.rbp_plan), C.c_void_p]
             if L.rbp_sizeof(A.RBP_SIZEOF_SESSION_CAPACITY) != C.sizeof(A.rbp_session_capacity):
                 raise RbpLibraryMissing(f"{path}: sizeof(rbp_session_capacity) is {L.rbp_sizeof(A.RBP_SIZEOF_SESSION_CAPACITY)} in the library, {C.sizeof(A.rbp_session_capacity)} in this binding")
         except AttributeError:
@@ -207,7 +210,21 @@ EXPORTED_SYMBOLS = [
     "rbp_session_swept_clearance", "rbp_dev_swept_clearance",
     "rbp_session_limits", "rbp_dev_limits",
     "rbp_session_create_reserved", "rbp_session_capacity_of", "rbp_session_refill_from_ecbs",
+    "rbp_plan_stage_bytes", "rbp_session_reserve_plan_stage", "rbp_session_refill_from_plans",
 ]
+
+
+def plan_stage_bytes(capacity, K):
+    """bytes K missions of the shape (N, M) of `capacity` = (K, N, M, max_boxes) occupy in the staging block of Session.refill_plans
+    (rbp_plan_stage_bytes): what Session.reserve_plan_stage takes.  A pure function; needs no device."""
+    cap = A.rbp_session_capacity(*[int(v) for v in capacity])
+    n = C.c_size_t()
+    rc = lib().rbp_plan_stage_bytes(C.byref(cap), int(K), C.byref(n))
+    if rc == A.RBP_ERR_BAD_ARGUMENT:
+        raise ValueError(f"rbp_plan_stage_bytes rc={rc}: {last_error()}")
+    if rc:
+        raise RuntimeError(f"rbp_plan_stage_bytes failed rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+    return n.value
 
 
 def last_error():
@@ -429,6 +446,37 @@ class Session:
         if rc:
             raise RuntimeError(f"rbp_session_refill_from_ecbs failed rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
         self._missions_of(search, slot_of, max_boxes)
+
+    def reserve_plan_stage(self, bytes=0):
+        """reserve the pinned staging block of refill_plans, its device twin and its event with `bytes` of room
+        (rbp_session_reserve_plan_stage); 0: the capacity's missions in one round, up to 64 MiB.  Optional: the first refill_plans does it
+        with 0.  Less than one mission of the capacity's shape (plan_stage_bytes(capacity, 1)) or a second size: ValueError."""
+        rc = lib().rbp_session_reserve_plan_stage(self._h, int(bytes))
+        if rc == A.RBP_ERR_BAD_ARGUMENT:
+            raise ValueError(f"rbp_session_reserve_plan_stage rc={rc}: {last_error()}")
+        if rc:
+            raise RuntimeError(f"rbp_session_reserve_plan_stage failed rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+
+    def refill_plans(self, worlds, missions, plans, stream=None):
+        """replace the session's missions by a caller's own (rbp_session_refill_from_plans): host plans with T and init_traj from any
+        front-end, their missions, and worlds whose grids lie on the session's device (DeviceWorlds items), which must stay alive until
+        the next refill.  Staged copies and one kernel per round on `stream`, nothing allocated once the staging block exists, nothing
+        synchronised.  `plans` become the session's for download(), `K` follows, `slot_of` becomes None.  A refusal (ValueError) leaves
+        the session as it was."""
+        K = len(plans)
+        if len(worlds) != K or len(missions) != K:
+            raise ValueError("refill_plans: worlds, missions and plans must have one entry per mission")
+        w = (A.rbp_world * K)(*[x.c_struct() for x in worlds])
+        m = (A.rbp_mission * K)(*[x.c_struct() for x in missions])
+        pl = (A.rbp_plan * K)(*[p.c_struct() for p in plans])
+        rc = lib().rbp_session_refill_from_plans(self._h, K, w, m, pl, C.c_void_p(stream or 0))
+        if rc == A.RBP_ERR_BAD_ARGUMENT:
+            raise ValueError(f"rbp_session_refill_from_plans rc={rc}: {last_error()}")
+        if rc:
+            raise RuntimeError(f"rbp_session_refill_from_plans failed rc={rc}: {ERROR_TEXT.get(rc, '')} | {last_error()}")
+        self._keep_refill = (worlds, missions)   # (the grids are referenced in place)
+        self.K, self.slot_of, self._N = K, None, plans[0].N
+        self._plans, self._pl = list(plans), pl
 
     @property
     def capacity(self):

@@ -10,6 +10,10 @@ them where they lie (planner.ecbs_search_batch, planner.Session.from_ecbs).  The
 With --stream B (only with --device-handoff) the maps go through ONE reserved session in batches of B (planner.Session.reserved with room for
 B missions, planner.Session.refill per batch): search, refill, run, report lines, batch after batch, as a planning service would, with no
 session built or released in between.  The same per-map lines in map order for any B.
+With --stream-plans B (only with --device-worlds --mode batched, not with --device-handoff) the same service for a caller whose plans are on
+the HOST: per batch of B maps the initial trajectories come from the host search, or with --device-ecbs from that batch's downloaded device
+search, and are loaded into ONE reserved session with planner.Session.refill_plans (packed staging, one copy and one kernel per round).
+The same per-map lines in map order for any B.
 With --device-report (only with --device-worlds --mode batched) the safety ratio and flight distance of every map's report line come from ONE
 planner.Session.report() on the resident plans instead of host.validate per downloaded plan: the same line format, the numbers of the
 rule the device and host.report share (csrc/common/report_rules.h; they differ from host.validate's by rounding).  Without --csv nothing
@@ -32,7 +36,7 @@ line per map with certified intervals for the largest velocity and acceleration,
 and how many (agent, segment) items are uncertified, violating and refined (csrc/common/limits_rules.h): whether the plan keeps max_vel and
 max_acc between the samples.
 
-usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff [--stream B]]] [--device-report] [--device-dynamics] [--device-clearance] [--device-separation] [--device-swept-clearance] [--device-limits]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
+usage: python -m swarm_simulator_amd.sweep_device [--device-worlds [--device-ecbs [--device-handoff [--stream B]]] [--stream-plans B] [--device-report] [--device-dynamics] [--device-clearance] [--device-separation] [--device-swept-clearance] [--device-limits]] [--mission mission_64agents_15.json] [--maps 1-50] [--mode batched]
        [--batch-size 4] [--iteration 1] [--joint] [--csv DIR]
 """
 import argparse
@@ -53,6 +57,8 @@ def main(argv=None):
                     "search's resident results, no initial trajectory passes through the host")
     ap.add_argument("--stream", type=int, default=0, metavar="B", help="with --device-handoff: the maps go through one reserved session in batches of B "
                     "(planner.Session.reserved, planner.Session.refill), nothing is allocated between the batches")
+    ap.add_argument("--stream-plans", type=int, default=0, metavar="B", help="with --device-worlds --mode batched, without --device-handoff: the maps go "
+                    "through one reserved session in batches of B whose host plans are loaded with planner.Session.refill_plans")
     ap.add_argument("--device-report", action="store_true", help="with --device-worlds --mode batched: safety ratio and flight distance of all maps from one "
                     "report call on the device (planner.Session.report); without --csv the coefficients are not downloaded")
     ap.add_argument("--device-dynamics", action="store_true", help="with --device-worlds --mode batched: one more line per map with both limit peak ratios and "
@@ -96,6 +102,10 @@ def main(argv=None):
         ap.error("--stream needs --device-worlds --device-ecbs --device-handoff --mode batched")
     if args.stream < 0:
         ap.error("--stream takes a positive batch size")
+    if args.stream_plans < 0:
+        ap.error("--stream-plans takes a positive batch size")
+    if args.stream_plans and not (args.device_worlds and args.mode == "batched") or args.stream_plans and args.device_handoff:
+        ap.error("--stream-plans needs --device-worlds --mode batched and excludes --device-handoff (whose plans never reach the host: --stream)")
     if not args.device_worlds:
         return test_all.main(argv)
     if rest:
@@ -112,6 +122,8 @@ def main(argv=None):
         plans, inits = [], None
         if args.device_handoff:
             return handoff_sweep(args, worlds, maps, mission, param)
+        if args.stream_plans:
+            return stream_plans_sweep(args, worlds, maps, mission, param)
         if args.device_ecbs:
             t0 = time.perf_counter()
             inits = planner.ecbs_plan_batch(worlds, list(range(len(maps))), [mission] * len(maps), param)
@@ -203,6 +215,52 @@ def stream_sweep(args, worlds, maps, mission, param):
     finally:
         if sess is not None:
             sess.close()
+
+
+STREAM_PLANS_MAX_M = 64   # segments a slot of --stream-plans' session has room for: the device search's capacity (planner.ecbs_plan_batch)
+
+
+def stream_plans_sweep(args, worlds, maps, mission, param):
+    """--stream-plans B: one reserved session with room for B missions; per batch of B maps the host plans of a search, a refill_plans, a
+    run and the report lines"""
+    B = args.stream_plans
+    sess = planner.Session.reserved(worlds, B, mission.qn, STREAM_PLANS_MAX_M, STREAM_PLANS_MAX_M, param)
+    try:
+        for b0 in range(0, len(maps), B):
+            batch, idx = maps[b0:b0 + B], list(range(b0, min(b0 + B, len(maps))))
+            if args.device_ecbs:
+                t0 = time.perf_counter()
+                plans = planner.ecbs_plan_batch(worlds, idx, [mission] * len(batch), param, max_M=STREAM_PLANS_MAX_M)
+                print(f"Initial Trajectory Planner runtime, {len(batch)} maps in one device search: {time.perf_counter() - t0:.6f}")
+                for i, st in zip(batch, plans.status):
+                    if st:  # (3: a capacity of the device search; the host search is the caller's choice, not a fallback)
+                        print(f"[ERROR] map{i}: {host.ECBS_ERROR_TEXT.get(int(st), 'ECBSPlanner: device search capacity exceeded (status 3)')}")
+                        return -1
+                plans = list(plans)
+                for i in batch:
+                    print(f"Map: map{i}.bt")
+            else:
+                plans = []
+                for n, i in zip(idx, batch):
+                    print(f"Map: map{i}.bt")
+                    t0 = time.perf_counter()
+                    try:
+                        plans.append(planner.ecbs_plan(worlds[n], mission, param))
+                    except RuntimeError as e:
+                        print(f"[ERROR] {e}")
+                        return -1
+                    print(f"Initial Trajectory Planner runtime: {time.perf_counter() - t0:.6f}")
+            try:
+                sess.refill_plans([worlds[n] for n in idx], [mission] * len(batch), plans)
+            except ValueError as e:   # (a plan beyond the session's strides)
+                print(f"[ERROR] {e}")
+                return -1
+            rc = run_and_report(args, sess, batch, plans, mission, param, close=False)
+            if rc:
+                return rc
+        return 0
+    finally:
+        sess.close()
 
 
 def run_and_report(args, sess, maps, plans, mission, param, close=True):
